@@ -14,6 +14,12 @@ scattered into the full image.  Total work is fixed -> "scaling": "strong".
 
 value = Mrays/s over the whole job = (primary + extension + shadow rays of
 all ranks) / (max over ranks of the frame time).
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+buffers when --dump-outputs is given and prints the JSON line.  --full adds
+what takes runs of its own: the counter and stage frames, the roofline (with
+the gather micro-benchmark), the C++ drop-in cadence, the CPU baseline, the
+oracle checks of the timed frame and config 5's instance update.
 """
 from __future__ import annotations
 
@@ -50,13 +56,21 @@ def parse(argv=None):
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--max-depth", type=int, default=None)
     ap.add_argument("--tile", type=int, default=32)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle on rank 0 (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the counter and stage frames, the "
+                         "roofline, the C++ drop-in cadence, the CPU baseline, the oracle checks of the timed frame "
+                         "and (config 5) the instance update; off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step left in the pass's buffers as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of the pixels, listed in sample_pixels.npy, when all of it "
+                         "would exceed 60 MB; rank 0)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: time the CPU oracle on rank 0 (N=1 only)")
     ap.add_argument("--cpu-sample-stride", type=int, default=None,
                     help="CPU baseline renders every k-th pixel (default: full frame for configs 3/4, 1/16 for 5)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0: every CPU this process may run on, capped by the cgroup quota)")
     ap.add_argument("--dropin", type=int, default=1,
-                    help="also time the C++ drop-in cadence (build/pupil_path_tracer: spp x PTPass::OnRun of 1 spp, "
+                    help="--full: also time the C++ drop-in cadence (build/pupil_path_tracer: spp x PTPass::OnRun of 1 spp, "
                          "each synchronised) on the same scene exported as XML + OBJ (rank 0, N=1, configs 3/4)")
     ap.add_argument("--save", default="", help="write the frame as PNG (rank 0)")
     ap.add_argument("--dump", default="", help="write the full float32 frame as .npy (rank 0, after the timed steps)")
@@ -211,13 +225,15 @@ def main(argv=None):
         if gather is not None:  # overlapped with the next frame on a side stream (dist.FrameGather)
             handles.append(gather.gather_async(pt.buffers.get(FINAL_RESULT), stream))
 
-    # one instrumented frame (untimed, rendered on its own) for the traversal counters:
+    # --full: one instrumented frame (untimed, rendered on its own) for the traversal counters:
     # node visits / primitive tests per ray, the algorithmic bytes of SURVEY.md §8(d)
-    pt.mark_dirty()
-    pt.render(args.spp, collect_stats=1, stream=stream)
-    torch.cuda.synchronize(dev)
-    st_bytes = pt.stats()
-    rays_counter_frame = st_bytes["primary_rays"] + st_bytes["extension_rays"] + st_bytes["shadow_rays"]
+    st_bytes, rays_counter_frame = None, 0
+    if args.full:
+        pt.mark_dirty()
+        pt.render(args.spp, collect_stats=1, stream=stream)
+        torch.cuda.synchronize(dev)
+        st_bytes = pt.stats()
+        rays_counter_frame = st_bytes["primary_rays"] + st_bytes["extension_rays"] + st_bytes["shadow_rays"]
 
     pt.mark_dirty()  # the progressive render starts at seed 0
     for _ in range(args.warmup):
@@ -246,22 +262,28 @@ def main(argv=None):
              "frames_in_flight": c1["frames_in_flight"], "pipeline_slots": c1["pipeline_slots"],
              "ring_bytes": c1["ring_bytes"], "ring_budget_bytes": c1["ring_budget_bytes"]}
     # the last timed frame (seeds 0 .. seed_t0 + steps*spp - 1 accumulated), checked below
-    last_accum = pt.buffers.get("pt accum buffer").clone() if rank == 0 and world == 1 else None
+    last_accum = pt.buffers.get("pt accum buffer").clone() if rank == 0 and world == 1 and args.full else None
     last_frame = None
-    if rank == 0 and (args.dump or args.save):
+    if rank == 0 and (args.dump or args.save or args.dump_outputs):
         last_frame = handles[-1].synchronize() if gather is not None else pt.buffers.get(FINAL_RESULT).clone()
-    # one more frame, untimed, rendered on its own with HIP events around every stage
-    # launch (stage times; each event adds ~6 us of stream gap)
-    pt.mark_dirty()
-    pt.render(args.spp, collect_stats=2, stream=stream)
-    torch.cuda.synchronize(dev)
-    st = pt.stats()
-    rays_frame = st["primary_rays"] + st["extension_rays"] + st["shadow_rays"]
-    assert rays_frame == rays_counter_frame
-    ext_ms, trace_ms, shade_ms = st["extend_ms"], st["trace_ms"], st["shade_ms"]
+    if rank == 0 and args.dump_outputs:
+        # N > 1: the frame rank 0 assembled (the other buffers stay compact on their ranks)
+        dump_outputs(args.dump_outputs, dict(pt.buffers.buffers) if world == 1 else {FINAL_RESULT: last_frame})
     # rays traced by the plain (non-counter) traversal kernels over this process: the
     # denominator of the per-ray PMC figures (tools/pmc_summary.py --json)
-    rays_plain_process = st["rays_traced_total"] - rays_counter_frame
+    rays_plain_process = c1["rays_traced_total"] - rays_counter_frame
+    st = None
+    if args.full:
+        # one more frame, untimed, rendered on its own with HIP events around every stage
+        # launch (stage times; each event adds ~6 us of stream gap)
+        pt.mark_dirty()
+        pt.render(args.spp, collect_stats=2, stream=stream)
+        torch.cuda.synchronize(dev)
+        st = pt.stats()
+        rays_frame = st["primary_rays"] + st["extension_rays"] + st["shadow_rays"]
+        assert rays_frame == rays_counter_frame
+        ext_ms, trace_ms, shade_ms = st["extend_ms"], st["trace_ms"], st["shade_ms"]
+        rays_plain_process = st["rays_traced_total"] - rays_counter_frame
 
     # N > 1: what each rank saw, so a scaling run verifies itself (which rank was slow, that the
     # communicator held N ranks, what the tile gather cost per step on its side stream)
@@ -290,21 +312,22 @@ def main(argv=None):
     # gather ceiling measured on this box by build/ubench_gather), VALU issue and HBM
     # bytes (per-ray figures of the committed PMC passes of this config, times this
     # rank's rays per launch).  Launch time: HIP events around the timed steps' launches.
-    roof = roofline(args, st_bytes, timed) if rank == 0 else None
+    roof = roofline(args, st_bytes, timed) if rank == 0 and args.full else None
     dropin = None
-    if rank == 0 and world == 1 and args.dropin and args.config in (3, 4) and args.emissive_groups == 0:
+    if (args.full and rank == 0 and world == 1 and args.dropin and args.config in (3, 4)
+            and args.emissive_groups == 0):
         dropin = dropin_cadence(args, ms_per_step, last_accum)
 
     cpu = None
     timed_check = None
-    if rank == 0 and world == 1 and args.cpu_baseline and args.emissive_groups == 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline and args.emissive_groups == 0:
         cpu = cpu_baseline(desc, args, pt)
         timed_check = timed_frame_check(desc, args, last_accum, seed_t0 + args.steps * args.spp)
 
     # RenderInstanceUpdate cost (config 5): move instance 0, re-sync the accel.  Last: the
     # checks above compare the frames rendered before the move with the unmoved scene
     update = None
-    if args.config == 5 and rank == 0:
+    if args.full and args.config == 5 and rank == 0:
         from pupiloptixlab_amd import world as W
 
         t0 = time.perf_counter()
@@ -354,9 +377,17 @@ def main(argv=None):
                        "rays_traced_plain_process": int(rays_plain_process),
                        "parallelism": f"tiles{args.tile}x{world}",
                        "area_emitters": int(desc.num_area_emitters),
-                       "accel": "two_level" if st_bytes["two_level"] else "flat",
+                       "accel": "two_level" if c1["two_level"] else "flat",
                        "emitter_select": os.environ.get("PUPIL_EMITTER_SELECT", "guide"),
                        "rays_per_step": rays_total / args.steps,
+                       "path_samples_per_s": round(args.width * args.height * args.spp / (ms_per_step * 1e-3), 1),
+                       "bvh_build_ms": round(c1["build_ms"], 3),
+                       "bvh_nodes": int(c1["bvh_nodes"])},
+            "ranks": per_rank,
+            "comm": comm,
+        }
+        if args.full:  # the counter frame's and the stage frame's figures, and the legs run after the timed steps
+            out["config"].update({
                        "rays_per_frame_rank0": int(rays_frame_local),
                        # shadow rays the reference would trace (one per loop iteration past RR,
                        # main.cu:119-123); the engine and the oracle trace one only when the
@@ -366,9 +397,6 @@ def main(argv=None):
                        "shadow_rays_reference_count": int(st_bytes["shadow_rays_reference"]),
                        "rays_per_frame_reference_count": int(st_bytes["primary_rays"] + st_bytes["extension_rays"] +
                                                              st_bytes["shadow_rays_reference"]),
-                       "path_samples_per_s": round(args.width * args.height * args.spp / (ms_per_step * 1e-3), 1),
-                       "bvh_build_ms": round(st_bytes["build_ms"], 3),
-                       "bvh_nodes": int(st_bytes["bvh_nodes"]),
                        "avg_node_visits_per_ray": round(st_bytes["node_visits"] / max(1, rays_frame_local), 2),
                        "avg_prim_tests_per_ray": round(st_bytes["prim_tests"] / max(1, rays_frame_local), 2),
                        "extend_rays_nodes_prims": [
@@ -381,18 +409,36 @@ def main(argv=None):
                            round((st_bytes["prim_tests"] - st_bytes["extend_prim_tests"]) / max(1, st_bytes["shadow_rays"]), 2)],
                        "stage_ms_per_frame": {"primary_extend": round(ext_ms, 3),
                                               "bounce_trace": round(trace_ms - ext_ms, 3),
-                                              "shade": round(shade_ms, 3)}},
-            "ranks": per_rank,
-            "comm": comm,
-            "dropin_cpp": dropin,
-            "instance_update_ms": update,
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "timed_frame_bit_exact": timed_check,
-        }
+                                              "shade": round(shade_ms, 3)}})
+            out.update({"dropin_cpp": dropin, "instance_update_ms": update, "roofline": roof, "cpu_baseline": cpu,
+                        "timed_frame_bit_exact": timed_check})
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs writes at most this much (the limit is 64 MB)
+
+
+def dump_outputs(dirname, buffers):
+    """--dump-outputs: the pass's named buffers (n pixels x channels, float32 device tensors) as
+    dirname/<name with _ for spaces>.npy.  When all of them exceed the budget, the same fixed
+    sample of pixel rows (PCG64 seed 0, ascending) of every buffer is written instead, with the
+    sampled pixel indices as sample_pixels.npy (float64)."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    n = min(t.shape[0] for t in buffers.values())
+    row_bytes = sum(4 * t.shape[1] for t in buffers.values())
+    idx = None
+    if n * row_bytes > DUMP_BUDGET_BYTES:
+        k = DUMP_BUDGET_BYTES // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        np.save(os.path.join(dirname, "sample_pixels.npy"), idx.astype(np.float64))
+    for name, t in buffers.items():
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name.replace(" ", "_") + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
 
 def rank_report(elapsed_s, rays_local, gather_ms, device):
     """Every rank's timed-region view, gathered to all ranks (a collective: every rank calls it):

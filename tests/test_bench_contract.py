@@ -76,6 +76,44 @@ def test_roofline_rank_of_an_8_way_shard_stays_below_one(monkeypatch):
     assert abs(rank["traffic"] - one["traffic"] / 8) < 1e3
 
 
+# ---------------------------------------------------------------- plain run / --full / --dump-outputs
+def test_full_is_off_by_default_and_steps_are_taken_as_given():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and (a.steps, a.warmup) == (7, 2)
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True
+
+
+def test_dump_outputs_small_buffers_are_written_whole(tmp_path):
+    import numpy as np
+    import torch
+
+    bufs = {"final result": torch.arange(40, dtype=torch.float32).reshape(10, 4),
+            "albedo": torch.arange(30, dtype=torch.float32).reshape(10, 3)}
+    bench.dump_outputs(str(tmp_path / "o"), bufs)
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["albedo.npy", "final_result.npy"]
+    got = np.load(tmp_path / "o" / "final_result.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, bufs["final result"].numpy())
+
+
+def test_dump_outputs_samples_the_same_pixels_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    n = 1001  # 28 B a row: 28 kB, over the budget
+    bufs = {"final result": torch.arange(4 * n, dtype=torch.float32).reshape(n, 4),
+            "normal": -torch.arange(3 * n, dtype=torch.float32).reshape(n, 3)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), bufs)
+    idx = np.load(tmp_path / "a" / "sample_pixels.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "sample_pixels.npy"))
+    rows = idx.astype(np.int64)
+    assert len(rows) == 4000 // (28 + 8) and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert np.array_equal(np.load(tmp_path / "a" / "final_result.npy"), bufs["final result"].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "normal.npy"), bufs["normal"].numpy()[rows])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 4000 + 3 * 128  # + .npy headers
+
+
 # ---------------------------------------------------------------- launcher (--gpus N)
 import json
 import os

@@ -1,8 +1,8 @@
 """The reference's own scene files (data/static/*.xml), as committed numeric fixtures
 (tests/golden/ref_scenes, made by tests/golden/make_ref_scenes.py from this repo's
-XML loader).  CPU: fixtures round-trip and the oracle renders them; when the
-reference tree is mounted, a fixture and a fresh load of its XML render the same
-pixels.  GPU: the engine renders every scene bit-identically to the oracle."""
+XML loader).  CPU: fixtures round-trip and the oracle renders them; a fixture renders
+the pixels recorded from a fresh load of its XML (ref_scenes_xml_render.npz).  GPU:
+the engine renders every scene bit-identically to the oracle."""
 import glob
 import os
 
@@ -10,11 +10,13 @@ import numpy as np
 import pytest
 
 import oracle
-from pupiloptixlab_amd import World, scene_io
+from pupiloptixlab_amd import scene_io
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_scenes")
 SCENES = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLD, "*.npz")))
-REF_XML = "/root/reference/data/static"
+# the oracle's render of each freshly loaded XML (make_ref_scenes.py): every XML_STRIDE-th pixel, XML_SPP spp
+XML_RENDER = os.path.join(os.path.dirname(GOLD), "ref_scenes_xml_render.npz")
+XML_STRIDE, XML_SPP = 13, 2
 
 # film sizes for the parity renders (the reference's aspect ratios, a quarter of the width)
 SMALL = {"cornellbox": (128, 128), "default": (180, 180), "denoised_scene": (180, 180),
@@ -42,17 +44,17 @@ def test_fixture_round_trip_and_oracle(name, tmp_path):
     assert r["accum"][:, :3].max() > 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_XML), reason="reference tree not mounted")
 @pytest.mark.parametrize("name", SCENES)
 def test_fixture_matches_fresh_xml_load(name):
+    """The fixture renders the pixels that a fresh load of the reference's XML rendered when
+    the fixtures were made (recorded by make_ref_scenes.py: every 13th pixel, 2 spp)."""
     fix = scene_io.LoadedScene(os.path.join(GOLD, name + ".npz")).resized(*SMALL[name])
-    w = World().load_scene(os.path.join(REF_XML, name + ".xml"))
-    xml = scene_io.LoadedScene.__new__(scene_io.LoadedScene)
-    xml.desc = w.desc()
-    xml_small = scene_io.LoadedScene.resized(xml, *SMALL[name])
-    px = np.arange(0, fix.width * fix.height, 13, dtype=np.uint32)
-    ra = oracle.OracleScene(fix).render(spp=2, pixels=px)["accum"]
-    rb = oracle.OracleScene(xml_small).render(spp=2, pixels=px)["accum"]
+    with np.load(XML_RENDER) as rec:
+        assert tuple(rec[name + "_size"]) == SMALL[name]
+        rb = rec[name]
+    px = np.arange(0, fix.width * fix.height, XML_STRIDE, dtype=np.uint32)
+    ra = oracle.OracleScene(fix).render(spp=XML_SPP, pixels=px)["accum"]
+    assert ra.shape == rb.shape and rb.dtype == np.float32
     assert np.array_equal(ra.view(np.uint32), rb.view(np.uint32))
 
 

@@ -9,7 +9,7 @@ O=$R/${OUT:-gpurun_out/pmc_sets}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 [ -n "${PUPIL_LIB:-}" ] && case "$PUPIL_LIB" in /*) ;; *) export PUPIL_LIB=$R/$PUPIL_LIB ;; esac
-ARGS="--steps 3 --warmup 4 --cpu-baseline 0 --dropin 0 --config ${CONFIG:-4}"
+ARGS="--full --steps 3 --warmup 4 --cpu-baseline 0 --dropin 0 --config ${CONFIG:-4}"
 i=0
 for set in $SETS; do
   i=$((i+1))

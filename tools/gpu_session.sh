@@ -9,7 +9,7 @@
 #   parity         only the hot-path parity files           -> $OUT/pytest_parity.txt
 #   smoke          __graft_entry__.smoke()                  -> $OUT/smoke.txt
 #   pmc<k>         PMC passes of config k (tools/gpu_pmc.sh) -> $OUT/pmc_config<k>.json (+ profiles/ when COMMIT_PMC=1)
-#   bench<k>       bench.py --config k (k = 4: the default line with its CPU / drop-in checks)
+#   bench<k>       bench.py --full --config k (k = 4: the default line with its CPU / drop-in checks)
 #   ab             alternating same-box A/B of builds / env (tools/gpu_lib_sweep.sh, $LIBS, $ROUNDS)
 #   probe          OnRun shard probe (tools/shard_probe.py; PROBE_ARGS)
 #   dropin         C++ drop-in cadence A/B (tools/gpu_dropin_ab.sh)
@@ -45,11 +45,11 @@ for step in ${STEPS:-suite smoke}; do
     mv gpurun_out/pmc_summary.txt $O/pmc_summary$k.txt; rm -rf gpurun_out/pmc
     python3 -c "import json; d=json.load(open('$O/pmc_config$k.json')); print('pmc$k', round(d['traffic_bytes_per_ray'],1), 'B/ray', round(d['valu_insts_per_ray'],2), 'VALU/ray')" ;;
   bench4)
-    timeout -k 10 500 python bench.py ${BENCH4_ARGS:-} > $O/bench4.log 2>&1 || { tail -5 $O/bench4.log; exit 1; }
+    timeout -k 10 500 python bench.py --full ${BENCH4_ARGS:-} > $O/bench4.log 2>&1 || { tail -5 $O/bench4.log; exit 1; }
     grep '^{' $O/bench4.log | tail -1 > $O/bench4.json; cut -c1-300 $O/bench4.json ;;
   bench[0-9])
     k=${step#bench}
-    timeout -k 10 900 python bench.py --config $k --steps ${BENCH_STEPS:-3} --warmup ${BENCH_WARMUP:-6} > $O/bench$k.log 2>&1 || { tail -5 $O/bench$k.log; exit 1; }
+    timeout -k 10 900 python bench.py --full --config $k --steps ${BENCH_STEPS:-3} --warmup ${BENCH_WARMUP:-6} > $O/bench$k.log 2>&1 || { tail -5 $O/bench$k.log; exit 1; }
     grep '^{' $O/bench$k.log | tail -1 > $O/bench$k.json; cut -c1-300 $O/bench$k.json ;;
   ab)
     bash tools/gpu_lib_sweep.sh > $O/ab.txt 2>&1; rc=$?; cut -c1-160 $O/ab.txt; [ $rc -eq 0 ] || exit $rc ;;
@@ -62,7 +62,7 @@ for step in ${STEPS:-suite smoke}; do
     OUT=${OUT:-gpurun_out/session} bash tools/gpu_pacing.sh > $O/pacing.log 2>&1; rc=$?; cut -c1-220 $O/pacing.log; [ $rc -eq 0 ] || exit $rc ;;
   prof)
     cd /tmp
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 4 --cpu-baseline 0 --dropin 0 ${BENCH4_ARGS:-} > $O/prof.log 2>&1
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 4 --cpu-baseline 0 --dropin 0 ${BENCH4_ARGS:-} > $O/prof.log 2>&1
     rc=$?; cd $R; [ $rc -eq 0 ] || { tail -5 $O/prof.log; exit $rc; }
     python3 tools/kstats.py $O/prof/run_kernel_stats.csv > $O/kernel_stats.txt
     python3 tools/timed_kernels.py $O/prof/run_kernel_trace.csv "${PROF_KERNEL:-k_trace4<4, false, false, false>}" 5 > $O/timed_kernels.txt
