@@ -6,6 +6,8 @@
 //
 // usage: pupil_path_tracer <scene.xml> [frames=16] [out.exr|.hdr|.pfm] [device=0]
 //        PUPIL_BENCH=warmup,frames,spp pupil_path_tracer <scene.xml>   (drop-in cadence benchmark)
+//        PUPIL_DENOISE=temporal PUPIL_BENCH_MOVING=1 pupil_path_tracer <scene.xml> [frames] [out]
+//                                                   (moving camera, every OnRun denoised with flow)
 #include <algorithm>
 #include <chrono>
 #include <string>
@@ -227,6 +229,68 @@ static int ThreadTest(Pupil::System &system, Pupil::pt::PTPass &pass, const char
     return 0;
 }
 
+// PUPIL_DENOISE=temporal with PUPIL_BENCH_MOVING=1: the interactive cadence with the temporal
+// denoiser.  The camera moves before every OnRun (each frame is 1 spp, accumulation restarts);
+// after it PTPass::ComputeMotionVectors fills "motion vector" and optix::Denoiser runs in
+// UseTemporal mode with the previous output and the flow, as the reference's Execute requires
+// (denoiser.cpp:203-209).  The last denoised frame is written to `out`.
+static int TemporalMoving(Pupil::System &system, Pupil::pt::PTPass &pass, int frames, const char *out) {
+    if (system.Gather()) {
+        std::fprintf(stderr, "PUPIL_DENOISE=temporal runs on one GPU\n");
+        return 2;
+    }
+    using Pupil::optix::Denoiser;
+    Pupil::world::World *w = system.GetWorld();
+    const uint32_t width = (uint32_t)w->scene->sensor.film.w, height = (uint32_t)w->scene->sensor.film.h;
+    auto *bm = Pupil::BufferManager::instance();
+    Pupil::Buffer *denoised[2];
+    for (int k = 0; k < 2; k++) {
+        Pupil::BufferDesc desc;
+        desc.name = k ? "denoised 1" : "denoised 0";
+        desc.width = width;
+        desc.height = height;
+        desc.stride_in_byte = sizeof(float) * 4;
+        if (!(denoised[k] = bm->AllocBuffer(desc))) return 1;
+    }
+    Denoiser denoiser(Denoiser::UseAlbedo | Denoiser::UseNormal | Denoiser::UseTemporal);
+    denoiser.Setup(width, height);
+    denoiser.ResetHistory();
+    float s2c[16], c2w[16];
+    w->camera->Snapshot(s2c, c2w);
+    frames = std::max(frames, 1);
+    for (int k = 0; k < frames; k++) {
+        float c[16];
+        std::memcpy(c, c2w, sizeof(c));
+        c[3] += 2e-3f * (float)(k + 1);
+        w->camera->SetCameraToWorld(c);
+        system.Run(1);
+        if (!pass.ComputeMotionVectors()) return 1;
+        Denoiser::ExecutionData data;
+        data.input = bm->GetBuffer(Pupil::BufferManager::DEFAULT_FINAL_RESULT_BUFFER_NAME)->cuda_ptr;
+        data.output = denoised[k & 1]->cuda_ptr;
+        data.albedo = bm->GetBuffer("albedo")->cuda_ptr;
+        data.normal = bm->GetBuffer("normal")->cuda_ptr;
+        if (k) {
+            data.prev_output = denoised[(k - 1) & 1]->cuda_ptr;
+            data.motion_vector = bm->GetBuffer("motion vector")->cuda_ptr;
+        }
+        if (!denoiser.Execute(data) || hipDeviceSynchronize() != hipSuccess) return 1;
+    }
+    std::vector<float> host(4 * (size_t)width * height);
+    if (hipMemcpy(host.data(), denoised[(frames - 1) & 1]->cuda_ptr, host.size() * sizeof(float), hipMemcpyDeviceToHost) !=
+        hipSuccess)
+        return 1;
+    if (out[0] && pupil_image_save(out, width, height, host.data(), PUPIL_IMAGE_AUTO) != PUPIL_OK) {
+        Pupil::Log("%s", pupil_last_error());
+        return 1;
+    }
+    double mean = 0.0;
+    for (size_t i = 0; i < host.size(); i += 4) mean += host[i] + host[i + 1] + host[i + 2];
+    std::printf("frames %d (moving camera, temporal denoiser with flow), %ux%u, mean radiance %.6f\n", frames, width,
+                height, mean / (3.0 * width * height));
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene.xml> [frames=16] [out.exr|.hdr|.pfm] [device=0]\n", argv[0]);
@@ -257,6 +321,9 @@ int main(int argc, char **argv) {
             rc = BenchWaste(*system, *pt_pass, waste);
         } else if (const char *tt = std::getenv("PUPIL_THREAD_TEST")) {
             rc = ThreadTest(*system, *pt_pass, tt);
+        } else if (std::getenv("PUPIL_DENOISE") && std::strcmp(std::getenv("PUPIL_DENOISE"), "temporal") == 0 &&
+                   std::getenv("PUPIL_BENCH_MOVING") && std::atoi(std::getenv("PUPIL_BENCH_MOVING"))) {
+            rc = TemporalMoving(*system, *pt_pass, frames, out);
         } else {
             system->Run((uint32_t)frames);
             pt_pass->Inspector();

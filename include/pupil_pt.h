@@ -342,6 +342,23 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out);
 int pupil_pt_local_pixels(uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tile_rank,
                           uint32_t tile_world, uint32_t *out_pixels, uint32_t *inout_count);
 void pupil_pt_destroy(pupil_pt *pt);
+/* ABI 7.  Screen-space flow for OptixDenoiserGuideLayer::flow (denoiser.cpp:207): for every pixel
+ * i = y*width + x, out[2i..2i+1] = (cur_x - prev_x, cur_y - prev_y) in pixels, in the index
+ * space of the frame buffers (compact = rank-local pixel order, as pupil_pt_frame.compact),
+ * of the surface point seen through the pixel centre now, against where that point was
+ * under the previous camera and the previous instance transforms.  An environment miss is the
+ * point at infinity along the ray; a point at or behind the previous camera plane has no
+ * previous pixel and gets (NaN, NaN).  Flow is that of the primary hit (nothing is followed
+ * through reflections or refractions), and only rigid instance motion is covered.
+ * prev_to_world: num_instances * 12 floats (row-major 3x4, host) or NULL = no instance moved.
+ * Asynchronous on hip_stream, ordered after every render enqueued so far; the current camera
+ * and instance transforms are the engine's (pupil_pt_set_camera / pupil_pt_update_instances).
+ * Adds nothing to the ray counters of pupil_pt_stats. */
+int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
+                            const float prev_camera_to_world[16], const float *prev_to_world,
+                            void *out_flow /* device float2 per pixel */, uint32_t compact,
+                            uint32_t tile_size, uint32_t tile_rank, uint32_t tile_world,
+                            void *hip_stream);
 
 /* ---- verification entry points (used by the parity tests) ----
  * closest (any_hit = 0) or any hit (any_hit = 1) for n host rays packed as
@@ -388,11 +405,20 @@ int pupil_image_load(const char *path, uint32_t *width, uint32_t *height, float 
  * a-trous wavelet filter (Dammertz et al. 2010): five passes of a 5x5 B3-spline
  * kernel at strides 1, 2, 4, 8, 16, each tap weighted by colour, normal and
  * albedo similarity.  Mode bits and Execute's data follow the reference:
- * UseAlbedo / UseNormal select the guides, UseTemporal blends with prev_output
- * (no motion vectors: static camera), Tiled is accepted (the whole frame is
+ * UseAlbedo / UseNormal select the guides, UseTemporal blends with prev_output:
+ * without motion_vector the fixed blend out = prev + 0.2 (filtered - prev) of a
+ * static camera; with motion_vector (pupil_pt_motion_vectors' flow) the history is
+ * fetched where each pixel's surface point was in the previous frame (bilinear, each
+ * tap weighted by the similarity of the previous call's guides to this call's),
+ * rejected where it is disoccluded (summed tap weight <= 0.05, non-finite flow or a
+ * source outside the image) and blended with a per-pixel history length,
+ * alpha = max(0.2, 1 / (n + 1)).  The denoiser keeps the previous call's guides and
+ * the history length between calls; pupil_denoiser_setup with a new size and
+ * pupil_denoiser_reset_history forget them.  Tiled is accepted (the whole frame is
  * filtered at once), ApplyToAOV and UseUpscale2X return PUPIL_ERR_UNSUPPORTED.
  * Buffers are device pointers: input/output/prev_output float4 per pixel,
- * albedo/normal float3 per pixel (the "albedo"/"normal" AOVs). */
+ * albedo/normal float3 per pixel (the "albedo"/"normal" AOVs), motion_vector float2
+ * per pixel. */
 enum {
     PUPIL_DENOISE_USE_ALBEDO = 1,
     PUPIL_DENOISE_USE_NORMAL = 1 << 1,
@@ -407,7 +433,8 @@ typedef struct pupil_denoise_data {
     const void *prev_output;  /* float4, UseTemporal only (NULL: first frame) */
     const void *albedo;       /* float3, UseAlbedo */
     const void *normal;       /* float3, UseNormal */
-    const void *motion_vector; /* unused (must be NULL) */
+    const void *motion_vector; /* float2 (cur - prev, pixels), UseTemporal with prev_output: reprojected
+                                * history; NULL = fixed blend.  output must then not alias prev_output */
 } pupil_denoise_data;
 typedef struct pupil_denoiser pupil_denoiser;
 /* Denoiser(mode, stream) (denoiser.h:20-21) */
@@ -416,6 +443,9 @@ int pupil_denoiser_create(int device, uint32_t mode, pupil_denoiser **out);
 int pupil_denoiser_setup(pupil_denoiser *d, uint32_t mode, uint32_t width, uint32_t height, float sigma_color);
 /* Execute(ExecutionData) (denoiser.h:31-40); asynchronous on hip_stream */
 int pupil_denoiser_execute(pupil_denoiser *d, const pupil_denoise_data *data, void *hip_stream);
+/* ABI 7.  Forgets the temporal history (previous guides, history length): the next reprojecting
+ * execute behaves as a first frame (a scene load or a camera cut) */
+int pupil_denoiser_reset_history(pupil_denoiser *d);
 void pupil_denoiser_destroy(pupil_denoiser *d);
 
 /* ---- host world (the reference's resource::Scene + world::World, C++ inside) ---- */

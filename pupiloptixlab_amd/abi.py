@@ -131,6 +131,8 @@ SIGNATURES = {
     "pupil_pt_local_pixels": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          u32p, u32p]),
     "pupil_pt_destroy": (None, [C.c_void_p]),
+    "pupil_pt_motion_vectors": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, C.c_void_p]),
     "pupil_pt_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, C.c_int]),
     "pupil_pt_export_bvh4": (C.c_int, [C.c_void_p, u32p, C.c_void_p, u32p, f32p, C.POINTER(C.c_int32)]),
     "pupil_debug_math": (C.c_int, [C.c_int, C.c_uint32, f32p, f32p, f32p]),
@@ -153,6 +155,7 @@ SIGNATURES = {
     "pupil_denoiser_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pupil_denoiser_setup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float]),
     "pupil_denoiser_execute": (C.c_int, [C.c_void_p, C.POINTER(DenoiseData), C.c_void_p]),
+    "pupil_denoiser_reset_history": (C.c_int, [C.c_void_p]),
     "pupil_denoiser_destroy": (None, [C.c_void_p]),
 }
 

@@ -12,8 +12,23 @@
 // sigma halved every pass (s_c = sigma_color * 2^-pass), the
 // normal / albedo terms only when the mode asks for those guides
 // (OptixDenoiserOptions::guideAlbedo / guideNormal, denoiser.cpp:46-60).
-// Taps outside the image are skipped.  UseTemporal blends the filtered frame
-// with prev_output (out = prev + 0.2 (filtered - prev)).
+// Taps outside the image are skipped.
+//
+// UseTemporal blends the filtered frame with prev_output.  Without a flow image it is the
+// fixed blend of a static camera, out = prev + 0.2 (filtered - prev).  With one
+// (motion_vector: cur - prev pixel position per pixel, pupil_pt_motion_vectors) the history
+// is reprojected: pixel (x, y) fetches prev_output at q = (x, y) - flow with the four
+// bilinear taps at floor(q), tap j weighted by
+//     w_j = b_j exp(-(|n_p - hn_j|^2 / s_n^2 + |a_p - ha_j|^2 / s_a^2))
+// (b_j the bilinear weight, hn / ha the guides of the previous call, the terms present only
+// for the guides the mode selects; taps outside the image are skipped).  The history is
+// valid when the flow is finite and W = sum w_j > kHistoryMinWeight; then, with the history
+// length n = sum w_j len_j / W,
+//     alpha = max(0.2, 1 / (n + 1)),  out = hist + alpha (filtered - hist),  len = min(n + 1, 5),
+// so a surface that just came into view converges as a running mean before it settles into
+// the exponential blend.  Otherwise (disocclusion, a source outside the image, NaN flow)
+// out = filtered and len = 1.  The denoiser keeps the previous call's packed guides (swapped
+// with the current ones after every execute) and a double-buffered history length.
 //
 // Layout: the guides are repacked once per call into float4 images (one 16-B
 // load per tap), colour ping-pongs between two float4 images; each pass is one
@@ -24,6 +39,7 @@
 
 #include <cmath>
 #include <string>
+#include <utility>
 
 #include "../../include/pupil_pt.h"
 
@@ -37,11 +53,24 @@ struct pupil_denoiser {
     uint32_t width = 0, height = 0;
     float sigma_color = 1.f;
     float4 *ping = nullptr, *pong = nullptr, *gn = nullptr, *ga = nullptr;
+    // temporal history (allocated by setup for UseTemporal modes only): the packed guides of the
+    // previous execute, the history length read by this execute (len[0]) and written by it
+    // (len[1]).  hist_guides = the guide bits hn / ha hold, -1 = none; len_valid = len[0] was
+    // written since the last setup with a new size / reset_history (a first frame or a
+    // reprojecting execute: the fixed blend and the non-temporal modes never write it).  A
+    // reprojecting execute uses the history only when both say so.
+    float4 *hn = nullptr, *ha = nullptr;
+    float *len[2] = {nullptr, nullptr};
+    int hist_guides = -1;
+    bool len_valid = false;
     void release() {
-        float4 *b[] = {ping, pong, gn, ga};
-        for (float4 *p : b)
+        void *b[] = {ping, pong, gn, ga, hn, ha, len[0], len[1]};
+        for (void *p : b)
             if (p) (void)hipFree(p);
-        ping = pong = gn = ga = nullptr;
+        ping = pong = gn = ga = hn = ha = nullptr;
+        len[0] = len[1] = nullptr;
+        hist_guides = -1;
+        len_valid = false;
     }
 };
 
@@ -50,6 +79,10 @@ namespace {
 constexpr float kSigmaNormal = 0.35f;
 constexpr float kSigmaAlbedo = 0.1f;
 constexpr float kTemporalAlpha = 0.2f;
+// reprojected history is used when the summed tap weight exceeds this: below it the taps are
+// mostly outside the image or on another surface (a bilinear footprint with one matching
+// corner tap of weight < 0.05 lies within a quarter pixel of that surface's edge)
+constexpr float kHistoryMinWeight = 0.05f;
 constexpr int kBlockX = 16, kBlockY = 16;
 
 int fail(int code, const char *msg) {
@@ -123,6 +156,74 @@ __global__ void k_temporal(const float4 *filtered, const float4 *prev, float4 *o
                          p.z + kTemporalAlpha * (f.z - p.z), f.w);
 }
 
+// UseTemporal with a flow image: reprojected, disocclusion-aware blend (see the file header).
+// One pixel per lane; four taps of prev / hn / ha / len_in around (x, y) - flow.
+template <bool N, bool A>
+__global__ __launch_bounds__(kBlockX *kBlockY) void k_temporal_reproject(
+    const float4 *filtered, const float4 *prev, const float2 *flow, const float4 *gn, const float4 *ga,
+    const float4 *hn, const float4 *ha, const float *len_in, float *len_out, float4 *out, uint32_t w, uint32_t h) {
+    const int x = blockIdx.x * kBlockX + threadIdx.x;
+    const int y = blockIdx.y * kBlockY + threadIdx.y;
+    if (x >= (int)w || y >= (int)h) return;
+    const size_t i = (size_t)y * w + x;
+    const float4 f = filtered[i];
+    const float2 mv = flow[i];
+    float4 np = make_float4(0.f, 0.f, 0.f, 0.f), ap = np;
+    if (N) np = gn[i];
+    if (A) ap = ga[i];
+    const float inv_sn2 = 1.f / (kSigmaNormal * kSigmaNormal);
+    const float inv_sa2 = 1.f / (kSigmaAlbedo * kSigmaAlbedo);
+    float sr = 0.f, sg = 0.f, sb = 0.f, sl = 0.f, ws = 0.f;
+    const float qx = (float)x - mv.x, qy = (float)y - mv.y;
+    const float fx = floorf(qx), fy = floorf(qy);
+    // NaN / infinite flow fails the comparisons; the range also keeps the int conversion defined
+    if (fx >= -1.f && fx < (float)w && fy >= -1.f && fy < (float)h) {
+        const int ix = (int)fx, iy = (int)fy;
+        const float tx = qx - fx, ty = qy - fy;
+        for (int dy = 0; dy <= 1; dy++) {
+            const int yy = iy + dy;
+            if (yy < 0 || yy >= (int)h) continue;
+            for (int dx = 0; dx <= 1; dx++) {
+                const int xx = ix + dx;
+                if (xx < 0 || xx >= (int)w) continue;
+                const size_t j = (size_t)yy * w + xx;
+                float e = 0.f;
+                if (N) {
+                    const float4 nq = hn[j];
+                    const float ux = np.x - nq.x, uy = np.y - nq.y, uz = np.z - nq.z;
+                    e += (ux * ux + uy * uy + uz * uz) * inv_sn2;
+                }
+                if (A) {
+                    const float4 aq = ha[j];
+                    const float ux = ap.x - aq.x, uy = ap.y - aq.y, uz = ap.z - aq.z;
+                    e += (ux * ux + uy * uy + uz * uz) * inv_sa2;
+                }
+                const float wgt = (dx ? tx : 1.f - tx) * (dy ? ty : 1.f - ty) * expf(-e);
+                const float4 pq = prev[j];
+                sr += wgt * pq.x;
+                sg += wgt * pq.y;
+                sb += wgt * pq.z;
+                sl += wgt * len_in[j];
+                ws += wgt;
+            }
+        }
+    }
+    if (ws > kHistoryMinWeight) {
+        const float hr = sr / ws, hg = sg / ws, hb = sb / ws, n = sl / ws;
+        const float alpha = fmaxf(kTemporalAlpha, 1.f / (n + 1.f));
+        out[i] = make_float4(hr + alpha * (f.x - hr), hg + alpha * (f.y - hg), hb + alpha * (f.z - hb), f.w);
+        len_out[i] = fminf(n + 1.f, 1.f / kTemporalAlpha);
+    } else {
+        out[i] = f;
+        len_out[i] = 1.f;
+    }
+}
+
+__global__ void k_fill(float *a, float v, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -163,13 +264,31 @@ int pupil_denoiser_setup(pupil_denoiser *d, uint32_t mode, uint32_t width, uint3
         d->width = width;
         d->height = height;
     }
+    // the history buffers, for the modes that can use them (a denoiser that never runs
+    // UseTemporal keeps the footprint of ping / pong and the guides)
+    if ((mode & PUPIL_DENOISE_USE_TEMPORAL) && !d->hn) {
+        const size_t n = (size_t)width * height;
+        if (hipMalloc((void **)&d->hn, sizeof(float4) * n) != hipSuccess ||
+            hipMalloc((void **)&d->ha, sizeof(float4) * n) != hipSuccess ||
+            hipMalloc((void **)&d->len[0], sizeof(float) * n) != hipSuccess ||
+            hipMalloc((void **)&d->len[1], sizeof(float) * n) != hipSuccess) {
+            d->release();
+            d->width = d->height = 0;
+            return fail(PUPIL_ERR_OOM, "denoiser history allocation failed");
+        }
+        d->hist_guides = -1;
+        d->len_valid = false;
+    }
     return PUPIL_OK;
 }
 
 int pupil_denoiser_execute(pupil_denoiser *d, const pupil_denoise_data *data, void *hip_stream) {
     if (!d || !data || !data->input || !data->output) return fail(PUPIL_ERR_INVALID, "null argument");
     if (!d->ping) return fail(PUPIL_ERR_INVALID, "denoiser not set up");
-    if (data->motion_vector) return fail(PUPIL_ERR_UNSUPPORTED, "motion vectors are not supported");
+    // reprojected history: UseTemporal with both the previous output and a flow image
+    const bool reproject = (d->mode & PUPIL_DENOISE_USE_TEMPORAL) && data->prev_output && data->motion_vector;
+    if (reproject && data->output == data->prev_output)
+        return fail(PUPIL_ERR_INVALID, "output must not alias prev_output when motion vectors are given");
     const bool use_n = (d->mode & PUPIL_DENOISE_USE_NORMAL) != 0;
     const bool use_a = (d->mode & PUPIL_DENOISE_USE_ALBEDO) != 0;
     if ((use_n && !data->normal) || (use_a && !data->albedo)) return fail(PUPIL_ERR_INVALID, "missing guide buffer");
@@ -196,13 +315,48 @@ int pupil_denoiser_execute(pupil_denoiser *d, const pupil_denoise_data *data, vo
 #undef ATROUS
         src = dst;
     }
-    if ((d->mode & PUPIL_DENOISE_USE_TEMPORAL) && data->prev_output) {
+    const int guides = (use_n ? PUPIL_DENOISE_USE_NORMAL : 0) | (use_a ? PUPIL_DENOISE_USE_ALBEDO : 0);
+    const bool temporal = (d->mode & PUPIL_DENOISE_USE_TEMPORAL) != 0;
+    // a reprojecting call without history (no execute has written the history length since the
+    // last setup with a new size or reset_history, or the history holds other guides than this
+    // call's) is a first frame
+    if (reproject && d->len_valid && d->hist_guides == guides) {
+#define REPROJECT(N, A)                                                                                           \
+    hipLaunchKernelGGL((k_temporal_reproject<N, A>), grid, block, 0, s, src, (const float4 *)data->prev_output,   \
+                       (const float2 *)data->motion_vector, d->gn, d->ga, d->hn, d->ha, d->len[0], d->len[1],     \
+                       (float4 *)data->output, w, h)
+        if (use_n && use_a) REPROJECT(true, true);
+        else if (use_n) REPROJECT(true, false);
+        else if (use_a) REPROJECT(false, true);
+        else REPROJECT(false, false);
+#undef REPROJECT
+        std::swap(d->len[0], d->len[1]);
+    } else if (temporal && data->prev_output && !reproject) {  // fixed blend; the history length stays
         hipLaunchKernelGGL(k_temporal, dim3((n + 255) / 256), dim3(256), 0, s, src, (const float4 *)data->prev_output,
                            (float4 *)data->output, n);
-    } else if (hipMemcpyAsync(data->output, src, sizeof(float4) * n, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-        return fail(PUPIL_ERR_HIP, "output copy failed");
+    } else {
+        if (hipMemcpyAsync(data->output, src, sizeof(float4) * n, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(PUPIL_ERR_HIP, "output copy failed");
+        if (temporal) {  // a first frame starts the history
+            hipLaunchKernelGGL(k_fill, dim3((n + 255) / 256), dim3(256), 0, s, d->len[0], 1.f, n);
+            d->len_valid = true;
+        }
+    }
+    if (temporal) {  // this call's guides are the next call's history
+        std::swap(d->gn, d->hn);
+        std::swap(d->ga, d->ha);
+        d->hist_guides = guides;
+    } else {
+        d->hist_guides = -1;  // hn / ha are no longer the previous call's
     }
     if (hipGetLastError() != hipSuccess) return fail(PUPIL_ERR_HIP, "denoiser launch failed");
+    return PUPIL_OK;
+}
+
+int pupil_denoiser_reset_history(pupil_denoiser *d) {
+    if (!d) return fail(PUPIL_ERR_INVALID, "null argument");
+    d->hist_guides = -1;
+    d->len_valid = false;
     return PUPIL_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -224,6 +225,13 @@ struct pupil_pt {
     uint8_t *d_moved = nullptr;
     std::vector<uint8_t> h_moved;
     float *refit_box = nullptr;
+    // flow pass scratch (pupil_pt_motion_vectors), sized on first use: the ray list (2 float4
+    // per pixel), the hit list, the previous instance transforms and their host staging copy;
+    // ev_flow: the upload of that copy has run (the next call may overwrite it)
+    float4 *flow_rays = nullptr, *flow_hits = nullptr;
+    float *flow_prev = nullptr;
+    std::vector<float> h_flow_prev;
+    hipEvent_t ev_flow = nullptr;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -272,6 +280,7 @@ struct pupil_pt {
         if (ev_begin) (void)hipEventDestroy(ev_begin);
         if (ev_end) (void)hipEventDestroy(ev_end);
         if (ev_sync) (void)hipEventDestroy(ev_sync);
+        if (ev_flow) (void)hipEventDestroy(ev_flow);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
 };
@@ -531,6 +540,55 @@ uint32_t local_pixels(uint32_t w, uint32_t h, uint32_t ts, uint32_t rank, uint32
             }
     }
     return n;
+}
+
+// The device pixel map of a tiling (key = w, h, tile size, rank, world), cached per tiling;
+// map = null (identity) for tile_world = 1.
+int local_pixel_map(pupil_pt *pt, const uint32_t key[5], const uint32_t **map, uint32_t *num_local) {
+    *map = nullptr;
+    *num_local = pt->width * pt->height;
+    if (key[4] <= 1) return PUPIL_OK;
+    if (!pt->pixel_map || std::memcmp(key, pt->pm_key, sizeof(pt->pm_key)) != 0) {
+        const uint32_t n = local_pixels(pt->width, pt->height, key[2], key[3], key[4], nullptr);
+        std::vector<uint32_t> host(n ? n : 1);
+        local_pixels(pt->width, pt->height, key[2], key[3], key[4], host.data());
+        if (pt->pixel_map) (void)hipFree(pt->pixel_map);
+        pt->pixel_map = nullptr;
+        HIP_TRY(hipMalloc((void **)&pt->pixel_map, sizeof(uint32_t) * host.size()));
+        HIP_TRY(hipMemcpy(pt->pixel_map, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice));
+        std::memcpy(pt->pm_key, key, sizeof(pt->pm_key));
+        pt->pm_count = n;
+    }
+    *map = pt->pixel_map;
+    *num_local = pt->pm_count;
+    return PUPIL_OK;
+}
+
+// inverse of a row-major 4x4 in double (Gauss-Jordan, partial pivoting); false = singular
+bool invert4(const float *m, double *inv) {
+    double a[4][8];
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) {
+            a[r][c] = (double)m[4 * r + c];
+            a[r][4 + c] = r == c ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < 4; c++) {
+        int piv = c;
+        for (int r = c + 1; r < 4; r++)
+            if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
+        if (!(std::fabs(a[piv][c]) > 0.0)) return false;
+        if (piv != c) std::swap_ranges(a[piv], a[piv] + 8, a[c]);
+        const double s = 1.0 / a[c][c];
+        for (int k = 0; k < 8; k++) a[c][k] *= s;
+        for (int r = 0; r < 4; r++) {
+            if (r == c) continue;
+            const double f = a[r][c];
+            for (int k = 0; k < 8; k++) a[r][k] -= f * a[c][k];
+        }
+    }
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) inv[4 * r + c] = a[r][4 + c];
+    return true;
 }
 
 // ------------------------------------------------------------------ frame schedules
@@ -889,7 +947,7 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
 extern "C" {
 
 const char *pupil_last_error(void) { return g_last_error.c_str(); }
-int pupil_abi_version(void) { return 6; }
+int pupil_abi_version(void) { return 7; }
 
 int pupil_pt_local_pixels(uint32_t width, uint32_t height, uint32_t tile_size, uint32_t tile_rank, uint32_t tile_world,
                           uint32_t *out_pixels, uint32_t *inout_count) {
@@ -1336,22 +1394,8 @@ int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_laun
     // local pixel map (cached per tiling)
     const uint32_t key[5] = {pt->width, pt->height, ts, launch->tile_rank, world};
     const uint32_t *map = nullptr;
-    uint32_t num_local = pt->width * pt->height;
-    if (world > 1) {
-        if (!pt->pixel_map || std::memcmp(key, pt->pm_key, sizeof(key)) != 0) {
-            num_local = local_pixels(pt->width, pt->height, ts, launch->tile_rank, world, nullptr);
-            std::vector<uint32_t> host(num_local ? num_local : 1);
-            local_pixels(pt->width, pt->height, ts, launch->tile_rank, world, host.data());
-            if (pt->pixel_map) (void)hipFree(pt->pixel_map);
-            pt->pixel_map = nullptr;
-            HIP_TRY(hipMalloc((void **)&pt->pixel_map, sizeof(uint32_t) * host.size()));
-            HIP_TRY(hipMemcpy(pt->pixel_map, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice));
-            std::memcpy(pt->pm_key, key, sizeof(key));
-            pt->pm_count = num_local;
-        }
-        map = pt->pixel_map;
-        num_local = pt->pm_count;
-    }
+    uint32_t num_local = 0;
+    if (const int rc = local_pixel_map(pt, key, &map, &num_local)) return rc;
     if (num_local == 0) return PUPIL_OK;
     const size_t paths = (size_t)num_local * launch->spp;
     if (paths >= (1ull << 31)) return fail(PUPIL_ERR_UNSUPPORTED, "too many paths in one batch");
@@ -1625,6 +1669,70 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
     (void)hipFree(d_rays);
     if (d_out) (void)hipFree(d_out);
     HIP_TRY(e);
+    return PUPIL_OK;
+}
+
+// Flow AOV (pt_flow.hip): camera rays through the pixel centres, the production traversal,
+// the projection of the hits through the previous camera.  Runs on hip_stream, ordered by
+// stream events after every render enqueued so far (the traversal's overflow stacks are shared
+// with them), and the renders after it order themselves behind it the same way.  Its traversal
+// has its own work-counter slot and adds to none of the ray totals pupil_pt_stats reports.
+int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16], const float prev_camera_to_world[16],
+                            const float *prev_to_world, void *out_flow, uint32_t compact, uint32_t tile_size,
+                            uint32_t tile_rank, uint32_t tile_world, void *hip_stream) {
+    if (!pt || !prev_sample_to_camera || !prev_camera_to_world || !out_flow)
+        return fail(PUPIL_ERR_INVALID, "null argument");
+    const uint32_t world = tile_world ? tile_world : 1u;
+    const uint32_t ts = tile_size ? tile_size : 32u;
+    if (tile_rank >= world) return fail(PUPIL_ERR_INVALID, "tile_rank >= tile_world");
+    // sample <- world of the previous camera, inverted and multiplied in double
+    double c2s[16], w2c[16];
+    if (!invert4(prev_sample_to_camera, c2s) || !invert4(prev_camera_to_world, w2c))
+        return fail(PUPIL_ERR_INVALID, "singular previous camera matrix");
+    FlowJob job{};
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) {
+            double v = 0.0;
+            for (int k = 0; k < 4; k++) v += c2s[4 * r + k] * w2c[4 * k + c];
+            job.world_to_sample[4 * r + c] = (float)v;
+        }
+    HIP_TRY(hipSetDevice(pt->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const uint32_t key[5] = {pt->width, pt->height, ts, tile_rank, world};
+    uint32_t num_local = 0;
+    if (const int rc = local_pixel_map(pt, key, &job.pixel_map, &num_local)) return rc;
+    if (num_local == 0) return PUPIL_OK;
+    if (!pt->flow_hits) {  // first use: lists for the whole image serve every tiling (num_local <= w * h)
+        const size_t cap = (size_t)pt->width * pt->height;
+        if (!pt->flow_rays) HIP_TRY(pt->alloc(&pt->flow_rays, 2 * cap));
+        HIP_TRY(pt->alloc(&pt->flow_hits, cap));
+    }
+    if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
+        HIP_TRY(hipEventRecord(pt->ev_sync, pt->last_stream));
+        HIP_TRY(hipStreamWaitEvent(s, pt->ev_sync, 0));
+    }
+    if (prev_to_world) {
+        const size_t nf = 12 * pt->h_insts.size();
+        if (!pt->flow_prev) HIP_TRY(pt->alloc(&pt->flow_prev, nf));
+        if (!pt->ev_flow) HIP_TRY(hipEventCreateWithFlags(&pt->ev_flow, hipEventDisableTiming));
+        else HIP_TRY(hipEventSynchronize(pt->ev_flow));  // the previous upload has left the staging copy
+        pt->h_flow_prev.assign(prev_to_world, prev_to_world + nf);
+        if (nf) HIP_TRY(hipMemcpyAsync(pt->flow_prev, pt->h_flow_prev.data(), sizeof(float) * nf, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(pt->ev_flow, s));
+        job.prev_to_world = pt->flow_prev;
+    }
+    job.width = pt->width;
+    job.height = pt->height;
+    job.n = num_local;
+    job.compact = compact;
+    HIP_TRY(hipMemsetAsync(pt->q.work + kWorkFlow, 0, kWorkKind * sizeof(uint32_t), s));
+    launch_flow_rays(pt->sc, pt->width, pt->height, job.pixel_map, num_local, pt->flow_rays, s);
+    launch_trace_debug(pt->sc, (const float *)pt->flow_rays, (float *)pt->flow_hits, num_local, 0, pt->ovf,
+                       pt->ovf_threads, pt->q.work + kWorkFlow, s);
+    launch_flow_project(pt->sc, job, pt->flow_rays, pt->flow_hits, (float2 *)out_flow, s);
+    HIP_TRY(hipGetLastError());
+    pt->last_stream = s;
+    pt->rendered = true;
     return PUPIL_OK;
 }
 

@@ -89,7 +89,8 @@ constexpr uint32_t kCntNext = 9, kCntShadow = 10;                      // queue 
 // puts them back to zero.
 constexpr uint32_t kWorkShards = 8, kWorkStride = 32, kWorkKind = (2 * kWorkShards + 1) * kWorkStride;
 constexpr uint32_t kWorkExtend = 0, kWorkShadow = kWorkKind, kWorkRays = 2 * kWorkKind, kWorkFrame = 3 * kWorkKind;
-constexpr uint32_t kWorkSlots = 4 * kWorkKind;
+constexpr uint32_t kWorkFlow = 4 * kWorkKind;  // the flow pass's traversal (pupil_pt_motion_vectors)
+constexpr uint32_t kWorkSlots = 5 * kWorkKind;
 constexpr uint32_t kStartBins = 16;                                    // [16..24] material bin starts
 constexpr uint32_t kStartNext = 25, kStartShadow = 26;                 // next / shadow regions of nxsh
 constexpr uint32_t kScratch = 27;
@@ -237,6 +238,21 @@ uint32_t trace_grid_blocks();
 // stats (or null): the persistent kernels' counter variants (queue accounting, node visits)
 void launch_trace_debug(const DeviceScene &sc, const float *rays, float *out, uint32_t n, int any, int *ovf,
                         uint32_t ovf_threads, uint32_t *work, hipStream_t s, const TraceStats *stats = nullptr);
+// flow AOV (pt_flow.hip): the camera rays through the centres of the n local pixels as a
+// kModeRays ray list (2 float4 per ray), and the projection of their hits (launch_trace_debug's
+// 4 floats per ray) through the previous camera into flow[compact ? local pixel : y*w+x]
+struct FlowJob {
+    float world_to_sample[16];   // previous camera: sample <- world, row-major (inverted in double on the host)
+    const float *prev_to_world;  // device, 12 floats per instance (row-major 3x4), null = no instance moved
+    const uint32_t *pixel_map;   // local -> global pixel (null = identity)
+    uint32_t width, height;
+    uint32_t n;                  // local pixels
+    uint32_t compact;
+};
+void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, const uint32_t *pixel_map, uint32_t n,
+                      float4 *rays, hipStream_t s);
+void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays, const float4 *hits,
+                         float2 *flow, hipStream_t s);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

@@ -6,6 +6,12 @@ the GPU (csrc/denoise.hip) standing in for the OptiX AI denoiser.
     dn.setup(w, h)
     dn.execute(pt.buffers.get("final result"), out, albedo=pt.buffers.get("albedo"),
                normal=pt.buffers.get("normal"))
+
+Moving camera (UseTemporal): feed the previous output and the flow of PTPass.motion_vectors();
+the history is then reprojected and rejected where it is disoccluded:
+
+    dn = Denoiser(Denoiser.USE_ALBEDO | Denoiser.USE_NORMAL | Denoiser.USE_TEMPORAL)
+    dn.execute(frame, out, albedo=..., normal=..., prev_output=prev, motion_vector=pt.motion_vectors())
 """
 from __future__ import annotations
 
@@ -43,8 +49,10 @@ class Denoiser:
         check(self._lib.pupil_denoiser_setup(self._h, self.mode, int(w), int(h), self.sigma_color))
         self.input_w, self.input_h = int(w), int(h)
 
-    def execute(self, input, output, albedo=None, normal=None, prev_output=None, stream=None):
-        """Tensors on the device: input/output/prev_output (w*h, 4) float32, albedo/normal (w*h, 3)."""
+    def execute(self, input, output, albedo=None, normal=None, prev_output=None, stream=None, motion_vector=None):
+        """Tensors on the device: input/output/prev_output (w*h, 4) float32, albedo/normal (w*h, 3),
+        motion_vector (w*h, 2) = current minus previous pixel position (UseTemporal with
+        prev_output: reprojected history; output must then be another tensor than prev_output)."""
         import torch
 
         d = abi.DenoiseData()
@@ -53,8 +61,13 @@ class Denoiser:
         d.prev_output = prev_output.data_ptr() if prev_output is not None else None
         d.albedo = albedo.data_ptr() if albedo is not None else None
         d.normal = normal.data_ptr() if normal is not None else None
+        d.motion_vector = motion_vector.data_ptr() if motion_vector is not None else None
         s = stream if stream is not None else torch.cuda.current_stream(input.device)
         check(self._lib.pupil_denoiser_execute(self._h, C.byref(d), C.c_void_p(s.cuda_stream)))
+
+    def reset_history(self):
+        """Forget the temporal history: the next reprojecting execute is a first frame."""
+        check(self._lib.pupil_denoiser_reset_history(self._h))
 
     def close(self):
         if self._h:

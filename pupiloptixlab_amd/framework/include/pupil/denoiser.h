@@ -2,7 +2,9 @@
 // (framework/optix/denoiser.h:7-66) over the engine's C ABI (pupil_denoiser_*):
 // the same EMode bits, Setup / SetMode / Execute(ExecutionData) and tile
 // settings, backed by the HIP a-trous filter (csrc/denoise.hip) because the
-// OptiX AI denoiser has no ROCm counterpart.  UseUpscale2X and ApplyToAOV are
+// OptiX AI denoiser has no ROCm counterpart.  UseTemporal with motion_vector (the
+// flow of PTPass::ComputeMotionVectors) reprojects the history and drops it where it
+// is disoccluded; without motion_vector it is a fixed blend.  UseUpscale2X and ApplyToAOV are
 // reported as unsupported; tiles are accepted and ignored (the whole frame is
 // filtered in one pass over HBM).
 #pragma once
@@ -65,6 +67,9 @@ public:
         const pupil_denoise_data data{d.input, d.output, d.prev_output, d.albedo, d.normal, d.motion_vector};
         return pupil_denoiser_execute(m_denoiser, &data, m_stream) == PUPIL_OK;
     }
+    // UseTemporal with motion_vector: forget the history (previous guides, history length), so the
+    // next Execute is a first frame -- after a scene load or a camera cut (framework/src/denoiser.cpp)
+    void ResetHistory() noexcept;
 
     unsigned int mode = EMode::UseAlbedo | EMode::UseNormal;
     unsigned int input_w = 0;

@@ -30,6 +30,12 @@ public:
     void SetMaxDepth(int depth) noexcept;
     void SetAccumulate(bool on) noexcept;
     bool Stats(pupil_pt_counters &out) noexcept;
+    // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
+    // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
+    // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in
+    // compact order when the frame is gathered) for optix::Denoiser::ExecutionData::motion_vector.
+    // Synchronised like OnRun.  After a single OnRun the flow is zero on every surface.
+    bool ComputeMotionVectors() noexcept;
 
 private:
     void BindingEventCallback() noexcept;
@@ -49,6 +55,12 @@ private:
     // reference's handler only sets m_dirty, pt_pass.cpp:216-218; OnRun refits once)
     std::mutex m_pending_mutex;
     std::vector<uint32_t> m_pending;
+    // what ComputeMotionVectors compares against: the cameras of the last two OnRuns, the
+    // instance transforms now in the engine and those before the last OnRun's update
+    float m_cam[2][2][16] = {};  // [0] last OnRun, [1] the one before; [.][0] sample_to_camera, [.][1] camera_to_world
+    bool m_have_cam = false;
+    std::vector<float> m_to_world, m_prev_to_world;  // 12 floats per instance
+    bool m_instances_moved = false;                 // by the last OnRun
 };
 
 }  // namespace Pupil::pt

@@ -24,6 +24,8 @@ PTPass::~PTPass() noexcept {
 // count.  Runs on the render thread; events may arrive from any other thread.
 void PTPass::OnRun() noexcept {
     if (!m_engine) return;
+    std::memcpy(m_cam[1], m_cam[0], sizeof(m_cam[0]));  // the previous OnRun's view, for ComputeMotionVectors
+    m_instances_moved = false;
     if (m_dirty) {
         m_dirty = false;  // an event after this point marks the next frame dirty again
         std::vector<uint32_t> moved;
@@ -34,6 +36,10 @@ void PTPass::OnRun() noexcept {
         float s2c[16], c2w[16];
         m_world->camera->Snapshot(s2c, c2w);
         pupil_pt_set_camera(m_engine, s2c, c2w);
+        std::memcpy(m_cam[0][0], s2c, sizeof(s2c));
+        std::memcpy(m_cam[0][1], c2w, sizeof(c2w));
+        if (!m_have_cam) std::memcpy(m_cam[1], m_cam[0], sizeof(m_cam[0]));  // first frame: no motion
+        m_have_cam = true;
         if (!moved.empty()) {  // m_world->GetIASHandle(2, true) + the emitter group (pt_pass.cpp:46-47)
             std::scoped_lock lock(m_world->Mutex());
             const pupil_scene_desc &d = m_world->Desc();
@@ -45,6 +51,11 @@ void PTPass::OnRun() noexcept {
                 std::memcpy(&to[12 * k], ins.to_object, sizeof(ins.to_object));
                 emissive = emissive || ins.emitter_offset >= 0;
             }
+            m_prev_to_world = m_to_world;
+            for (size_t k = 0; k < moved.size(); k++)
+                if (12 * (size_t)moved[k] + 12 <= m_to_world.size())
+                    std::memcpy(&m_to_world[12 * (size_t)moved[k]], &tw[12 * k], 12 * sizeof(float));
+            m_instances_moved = true;
             if (pupil_pt_update_instances(m_engine, (uint32_t)moved.size(), moved.data(), tw.data(), to.data()) !=
                 PUPIL_OK)
                 Log("%s: instance update failed: %s", name.c_str(), pupil_last_error());
@@ -136,7 +147,41 @@ void PTPass::SetScene(world::World *world) noexcept {
         m_engine = nullptr;
         return;
     }
+    const pupil_scene_desc &sd = world->Desc();
+    m_to_world.resize(12 * (size_t)sd.num_instances);
+    for (uint32_t i = 0; i < sd.num_instances; i++)
+        std::memcpy(&m_to_world[12 * (size_t)i], sd.instances[i].to_world, 12 * sizeof(float));
+    m_prev_to_world.clear();
+    m_instances_moved = false;
+    m_have_cam = false;
     m_dirty = true;
+}
+
+bool PTPass::ComputeMotionVectors() noexcept {
+    if (!m_engine || !m_have_cam) return false;
+    auto *bm = BufferManager::instance();
+    Buffer *mv = bm->GetBuffer("motion vector");
+    FrameGather *gather = util::Singleton<System>::instance()->Gather();
+    if (!mv) {
+        BufferDesc desc;
+        desc.name = "motion vector";
+        desc.width = gather ? std::max(1u, gather->LocalPixels()) : (uint32_t)m_world->scene->sensor.film.w;
+        desc.height = gather ? 1u : (uint32_t)m_world->scene->sensor.film.h;
+        desc.stride_in_byte = sizeof(float) * 2;
+        mv = bm->AllocBuffer(desc);
+        if (!mv) return false;
+    }
+    const float *prev_tw = m_instances_moved && m_prev_to_world.size() == m_to_world.size() && !m_to_world.empty()
+                               ? m_prev_to_world.data()
+                               : nullptr;
+    const uint32_t tile = gather ? gather->Info().tile : 0u, rank = gather ? (uint32_t)gather->Info().rank : 0u,
+                   world = gather ? (uint32_t)gather->Info().world : 1u;
+    if (pupil_pt_motion_vectors(m_engine, m_cam[1][0], m_cam[1][1], prev_tw, mv->cuda_ptr, gather ? 1u : 0u, tile,
+                                rank, world, m_stream) != PUPIL_OK) {
+        Log("%s: motion vectors failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    return hipStreamSynchronize(m_stream) == hipSuccess;
 }
 
 void PTPass::SetMaxDepth(int depth) noexcept {

@@ -7,7 +7,8 @@ Reference surface (the drop-in boundary):
     knobs ``max_depth`` (clamped 1..128) and ``accumulate``; camera / instance
     events mark it dirty, which resets ``random_seed`` and ``sample_cnt``.
   * ``BufferManager`` (framework/system/buffer.h:44-63): named device buffers
-    ("final result", "pt accum buffer", "albedo", "normal", "test").
+    ("final result", "pt accum buffer", "albedo", "normal", "test"; "motion vector"
+    once ``motion_vectors()`` was called).
   * ``System`` (framework/system/system.h:22-41), headless: ``add_pass``,
     ``set_scene``, ``run(frames)``.
 
@@ -103,6 +104,13 @@ class PTPass(Pass):
         self.tile = (32, 0, 1)  # tile_size, rank, world
         self._world = None  # the World the scene came from: its sensor is re-read when dirty
         self._pending = {}  # RenderInstanceUpdate events since the last render: id(world) -> (world, instances)
+        # what motion_vectors() compares against: the camera in the engine and those of the last
+        # two renders as (sample_to_camera, camera_to_world), the instance transforms now in the
+        # engine and, if any moved since the render before the last one, the transforms before
+        # that ((n, 12) float32)
+        self._cam = self._last_cam = self._prev_cam = None
+        self._to_world = self._prev_to_world = None
+        self._moved = False  # update_instances ran since the last render
         self.events = events or Events()
         self.events.bind(Events.CAMERA_CHANGE, lambda _: self.mark_dirty())
         self.events.bind(Events.RENDER_INSTANCE_UPDATE, self._on_instance_update)
@@ -138,6 +146,11 @@ class PTPass(Pass):
         check(self._lib.pupil_pt_update_instances(self._pt, len(ids), idv.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                   tw.ctypes.data_as(C.POINTER(C.c_float)),
                                                   to.ctypes.data_as(C.POINTER(C.c_float))))
+        if self._to_world is not None:
+            if not self._moved:  # several updates before one render: the first one's "before" stays
+                self._prev_to_world = self._to_world.copy()
+                self._moved = True
+            self._to_world[ids] = tw
         if any(desc.instances[i].emitter_offset >= 0 for i in ids):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
@@ -203,6 +216,13 @@ class PTPass(Pass):
         self.random_seed = 0
         self.sample_cnt = 0
         self.dirty = True
+        import numpy as np
+
+        self._cam = self._last_cam = self._prev_cam = (list(desc.sample_to_camera), list(desc.camera_to_world))
+        self._to_world = np.array([list(desc.instances[i].to_world) for i in range(desc.num_instances)],
+                                  np.float32).reshape(-1, 12)
+        self._prev_to_world = None
+        self._moved = False
         self._alloc_buffers()
 
     def _alloc_buffers(self):
@@ -231,6 +251,8 @@ class PTPass(Pass):
         continues: the next render() continues this one (progressive rendering), so the
         engine traces its camera rays ahead (PUPIL_HINT_CONTINUE; single-spp renders
         always do)."""
+        if not self._moved:
+            self._prev_to_world = None  # no instance moved between the last render and this one
         if self.dirty:  # pt_pass.cpp:40-49: camera re-uploaded, instances refitted, accumulation restarted
             pending, self._pending = self._pending, {}
             for world, ids in pending.values():
@@ -238,6 +260,7 @@ class PTPass(Pass):
             if self._world is not None:
                 d = self._world.desc()
                 check(self._lib.pupil_pt_set_camera(self._pt, d.sample_to_camera, d.camera_to_world))
+                self._cam = (list(d.sample_to_camera), list(d.camera_to_world))
             self.random_seed = 0
             self.sample_cnt = 0
             self.dirty = False
@@ -256,6 +279,45 @@ class PTPass(Pass):
         self.random_seed += spp  # pt_pass.cpp:55-56
         if self._accumulate:
             self.sample_cnt += spp
+        self._moved = False
+        self._prev_cam, self._last_cam = self._last_cam, self._cam  # the views of the last two renders
+
+    def motion_vectors(self, prev_camera=None, prev_to_world=None, stream=None):
+        """Screen-space flow (pupil_pt_motion_vectors) into the lazily allocated "motion vector"
+        buffer ((n, 2): current minus previous pixel position, NaN = no previous pixel), in the
+        index space of the other buffers; returns the buffer.  prev_camera: (sample_to_camera,
+        camera_to_world) of the previous frame, 16 floats each; prev_to_world: (num_instances, 12)
+        previous instance transforms, or None = no instance moved.  With no arguments both mean
+        "since my previous render": the camera of the render before the last one and, if
+        instances were moved between the two, the transforms they had before.  That needs the
+        engine to hold what the last render used: after update_instances, render first (or
+        pass prev_camera and prev_to_world)."""
+        import numpy as np
+
+        if prev_camera is None:
+            if self._moved:
+                raise RuntimeError("instances were updated since the last render: render before motion_vectors(), "
+                                   "or pass prev_camera / prev_to_world")
+            prev_camera = self._prev_cam
+            if prev_to_world is None:
+                prev_to_world = self._prev_to_world
+        n = self.local_pixel_count() if self.tile[2] > 1 else self.width * self.height
+        mv = self.buffers.buffers.get("motion vector")
+        if mv is None or mv.shape[0] != n:
+            mv = self.buffers.alloc("motion vector", n, 2)
+        s2c = (C.c_float * 16)(*np.asarray(prev_camera[0], np.float32).reshape(16).tolist())
+        c2w = (C.c_float * 16)(*np.asarray(prev_camera[1], np.float32).reshape(16).tolist())
+        ptw = None
+        if prev_to_world is not None:
+            ptw_np = np.ascontiguousarray(np.asarray(prev_to_world, np.float32).reshape(-1))
+            if ptw_np.size != self._to_world.size:
+                raise ValueError("prev_to_world needs 12 floats per instance")
+            ptw = ptw_np.ctypes.data_as(C.POINTER(C.c_float))
+        ts, rank, world = self.tile
+        s = stream if stream is not None else self._torch.cuda.current_stream(self.device_index)
+        check(self._lib.pupil_pt_motion_vectors(self._pt, s2c, c2w, ptw, C.c_void_p(mv.data_ptr()),
+                                                1 if world > 1 else 0, ts, rank, world, C.c_void_p(s.cuda_stream)))
+        return mv
 
     def on_run(self):
         self.render(1)
