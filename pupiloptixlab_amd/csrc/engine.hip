@@ -1217,7 +1217,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     std::memcpy(sc.camera.c2w, scene->camera_to_world, sizeof(sc.camera.c2w));
     // traversal overflow stacks, counters, events
     pt->ovf_threads = trace_grid_blocks() * (uint32_t)kTraceBlock;
-    if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * std::max(kStackOvf, kTraceStackOvf)) || pt->alloc(&pt->trace_counters, 32) ||
+    if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * kStackOvf) || pt->alloc(&pt->trace_counters, 32) ||
         pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->node_bound, 3) || pt->alloc(&pt->q.counts, kCountSlots) ||
         pt->alloc(&pt->q.work, kWorkSlots))
         return cleanup(fail(PUPIL_ERR_OOM, "workspace allocation failed"));
@@ -1570,12 +1570,6 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
                              100.0 * (double)d[3] / (64.0 * (double)std::max(1ull, d[2])), d[4],
                              (double)d[5] / (double)std::max(1ull, d[4]), visits, 100.0 * (double)tc[9] / visits,
                              100.0 * (double)tc[8] / visits);
-                if (tc[24])  // PUPIL_COOP builds: the cooperative node fetch
-                    std::fprintf(stderr,
-                                 "[pupil] coop fetch: %llu LDS-DMA wave-instructions (%.2f per node-loop iteration), "
-                                 "%llu node slots (%.1f%% of the node visits, %.1f per DMA)\n",
-                                 tc[24], (double)tc[24] / (double)std::max(1ull, d[0]), tc[25],
-                                 100.0 * (double)tc[25] / visits, (double)tc[25] / (double)tc[24]);
             }
             c.node_loop_iters = tc[2];  // trace4_body dg[0..5]
             c.node_loop_lanes = tc[3];
@@ -1587,8 +1581,6 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
             c.prim_tests = tc[1] + tc[15];
             c.shadow_rays_reference = tc[16];
             c.unique_node_fetches = tc[18];
-            c.coop_dma = tc[24];
-            c.coop_slots = tc[25];
             c.queue_handed = tc[20];
             c.queue_activated = tc[21];
             c.queue_retired = tc[22];

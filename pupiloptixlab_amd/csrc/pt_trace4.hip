@@ -45,14 +45,13 @@ __device__ __forceinline__ void enter_instance(const DevInstance &in, const RayP
 // kReturnLink switches back.  Spheres are tested at their TLAS leaf.
 // TOP: nodes [0, sc.top_nodes) are read from an LDS copy (DeviceScene::top_nodes; a separate
 // instance, since the per-visit LDS-or-global branch costs 1.1 % where the copy does not pay)
-// COOP: the wave-cooperative node fetch (pt_traverse.h CoopFetch; flat kernels only), staged in
-// s_coop (per wave: 64 node offsets, then the 16 * kCoopChunks node image); the stack ring is
-// RING entries (kTraceRing when COOP, leaving the LDS for the staging)
-template <int MODE, bool ANY, bool STATS, bool TL, bool TOP = false, bool COOP = false, int RING = kRing>
+// LDS: s_ring the stack columns (kRing entries per lane, pt_traverse.h LinStack), s_aux the
+// per-lane hit state, s_tst the entry distances of the stack entries (STATS kernels only)
+template <int MODE, bool ANY, bool STATS, bool TL, bool TOP = false>
 __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathState &ps, const Queues &q,
                                             const TraceJob &job, int *ovf, uint32_t ovf_threads,
                                             const TraceStats &stats, int *s_ring, float *s_aux, float *s_tst,
-                                            Bvh4Node *s_top, float4 *s_coop = nullptr) {
+                                            Bvh4Node *s_top) {
     constexpr float kInf = __builtin_huge_valf();
     // the top of the tree (nodes [0, top), breadth first) into LDS: every ray starts there
     const uint32_t top = TOP ? sc.top_nodes : 0u;
@@ -66,22 +65,13 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
     // mixed launches may carry the next render's camera rays (render-ahead, TraceJob::ahead_off)
     const uint32_t n_ahead = MODE == kModeMixedAhead ? job.static_count : 0u;
     const uint32_t count = kMixed ? n_next + q.counts[kCntShadow] : (job.count_ptr ? *job.count_ptr : job.static_count);
-    LinStackT<RING, RING == kRing ? kStackOvf : kTraceStackOvf> st;
+    LinStack st;
     st.lds = s_ring + threadIdx.x;
     st.ovf_blk = ovf + blockIdx.x * blockDim.x;
     st.lds0 = s_ring;
     st.ovf_stride = ovf_threads;
-    constexpr bool kDist = kDistStack && !TL;
-    if (STATS || kDist) st.tcol = s_tst + threadIdx.x;
+    if (STATS) st.tcol = s_tst + threadIdx.x;
     st.reset();
-    CoopFetch<kCoopChunks> cf;
-    if (COOP) {
-        // this wave's staging: 256 B of node offsets, then the node image (wave-uniform base)
-        const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        float4 *wbase = s_coop + w * (16u + 64u * kCoopChunks);
-        cf.addr = reinterpret_cast<uint32_t *>(wbase);
-        cf.stage = wbase + 16;
-    }
     // STATS: visits of a popped node whose entry distance already exceeds the ray's tmax (a
     // stack holding distances could skip them without the fetch), visits where no child was hit
     uint32_t n_cullable = 0, n_nohit = 0;
@@ -109,7 +99,6 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
     uint32_t best_key = 0;
     RayPre r{};
     float tmin = MODE == kModeRays ? 0.f : 0.001f, tmax = 0.f;  // tmin: a constant outside kModeRays
-    auto popn = [&]() { return kDist ? st.pop_live(tmax) : st.pop(); };
     // state read only at a hit update or at the retire lives in LDS (s_aux), not in VGPRs:
     // the path id and the best hit's barycentrics
     float &b1 = s_aux[threadIdx.x];
@@ -271,7 +260,7 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
             n_nohit += t[0] == kInf ? 1u : 0u;
         }
         if (t[0] == kInf) {
-            node = popn();
+            node = st.pop();
             if (STATS) t_node = st.tpop;
         } else {
             node = l[0];
@@ -279,36 +268,22 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
             st.reserve3();
             st.push3t(t[1], t[2], t[3], t[2] != kInf, t[3] != kInf);
             st.push3(l[1], l[2], l[3], t[1] != kInf, t[2] != kInf, t[3] != kInf);
-            if (node == kEmptyLink) node = popn();  // degenerate child boxes only (LinStack)
+            if (node == kEmptyLink) node = st.pop();  // degenerate child boxes only (LinStack)
         }
         if (node < 0 && leaf >= 0) {  // postpone the leaf, keep descending
             leaf = node;
-            node = popn();
+            node = st.pop();
             if (STATS) t_node = st.tpop;
         }
         };
-        if (COOP) {
-            // wave-uniform node phase: every lane takes part in the fetch, lanes that need a
-            // node visit it (the same visits in the same order per lane as the loop below)
-            for (;;) {
-                const bool want = active && (uint32_t)node < (uint32_t)kSentinel;
-                if (!__any(want)) break;
-                const Bvh4Node n = cf.template fetch<STATS>(sc.nodes4, node, want);
-                if (want) visit_node(n);
-                // leave for the leaf phase once fewer than node_min lanes still need a node
-                if ((uint32_t)__popcll(__ballot(want && leaf >= 0)) < job.node_min) break;
-            }
-        }
         if (active) {
-            if (!COOP) {
-                while ((uint32_t)node < (uint32_t)kSentinel) {
-                    Bvh4Node n;
-                    if (TOP && (uint32_t)node < top) n = s_top[node];
-                    else n = load_node4(sc, node);
-                    visit_node(n);
-                    // leave for the leaf phase once fewer than node_min lanes still need a node
-                    if ((uint32_t)__popcll(__ballot(leaf >= 0)) < job.node_min) break;
-                }
+            while ((uint32_t)node < (uint32_t)kSentinel) {
+                Bvh4Node n;
+                if (TOP && (uint32_t)node < top) n = s_top[node];
+                else n = load_node4(sc, node);
+                visit_node(n);
+                // leave for the leaf phase once fewer than node_min lanes still need a node
+                if ((uint32_t)__popcll(__ballot(leaf >= 0)) < job.node_min) break;
             }
             while (leaf < 0) {
                 if (STATS) {
@@ -361,7 +336,7 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
                     break;
                 }
                 leaf = node;
-                if (node < 0) node = popn();
+                if (node < 0) node = st.pop();
             }
             if (TL && node == kReturnLink && leaf >= 0 && !(any && found)) {  // BLAS exhausted: back to the TLAS
                 in_blas = false;
@@ -419,7 +394,6 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
     flush_stats<STATS>(&stats, nv, npt, 0);
     if (kMixed) flush_stats<STATS>(&stats, nv_sh, npt_sh, 14);
     flush_stats<STATS>(&stats, n_unique, 0u, 18);
-    if (COOP) flush_stats<STATS>(&stats, cf.n_dma, cf.n_slots, 24);
     flush_stats<STATS>(&stats, n_cullable, n_nohit, 8);
     if (STATS && stats.wave_times && lane_id() == 0) {
         unsigned long long *w = stats.wave_times + 4ull * (blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u);
@@ -462,15 +436,11 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
 template <int MODE, bool ANY, bool STATS, bool TOP>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(kTraceWavesPerSimd))) void k_trace4(
     DeviceScene sc, PathState ps, Queues q, TraceJob job, int *ovf, uint32_t ovf_threads, TraceStats stats) {
-    constexpr int ring = kCoopFetch || kDistStack ? kTraceRing : kRing;
-    __shared__ int s_ring[ring * kTraceBlock];
+    __shared__ int s_ring[kRing * kTraceBlock];
     __shared__ float s_aux[4 * kTraceBlock];
-    __shared__ float s_tst[STATS || kDistStack ? ring * kTraceBlock : 1];
-    __shared__ Bvh4Node s_top[kCoopFetch || kDistStack ? 1 : kTopNodes];
-    __shared__ float4 s_coop[kCoopFetch ? (kTraceBlock / 64) * (16 + 64 * kCoopChunks) : 1];
-    // the cooperative fetch replaces the LDS top-of-tree copy (its hot nodes are one shared DMA)
-    trace4_body<MODE, ANY, STATS, false, TOP && !kCoopFetch && !kDistStack, kCoopFetch, ring>(sc, ps, q, job, ovf, ovf_threads, stats,
-                                                                              s_ring, s_aux, s_tst, s_top, s_coop);
+    __shared__ float s_tst[STATS ? kRing * kTraceBlock : 1];
+    __shared__ Bvh4Node s_top[kTopNodes];
+    trace4_body<MODE, ANY, STATS, false, TOP>(sc, ps, q, job, ovf, ovf_threads, stats, s_ring, s_aux, s_tst, s_top);
 }
 
 // two-level variant: 9 more live registers (object-space box ray, margin,
