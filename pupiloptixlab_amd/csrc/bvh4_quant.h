@@ -42,12 +42,19 @@ PT_HD void quantize_axis_n(float lo, float hi, const float *clo, const float *ch
                            uint32_t &ebyte, uint32_t *qlo, uint32_t *qhi) {
     origin = lo;
     const float ext = hi - lo;
+    // The stored scale is the exponent byte alone, so it must be a normal float: a denormal
+    // scale (an extent below 254 * 2^-126) would be stored as 0 and an infinite one (hi - lo
+    // overflows) as inf, whose plane 0 decodes to NaN.  Clamped to [2^-126, 2^127]; with the
+    // largest scale a plane more than FLT_MAX above the origin decodes to +inf, which still
+    // encloses (8 bits cannot place a finite plane there: q * scale itself overflows).
+    const float smin = qfloat(1u << 23), smax = qfloat(254u << 23);
     float scale;
     if (!(ext > 0.f)) {
-        scale = qfloat(1u << 23);  // 2^-126
+        scale = smin;
     } else {
         scale = exp2f(ceilf(log2f(ext / 254.f)));
-        if (!(scale > 0.f)) scale = qfloat(1u << 23);
+        if (!(scale >= smin)) scale = smin;
+        if (!(scale <= smax)) scale = smax;
     }
     for (int attempt = 0; attempt < 8; attempt++) {
         bool ok = true;
@@ -69,7 +76,7 @@ PT_HD void quantize_axis_n(float lo, float hi, const float *clo, const float *ch
             qhi[k >> 2] |= b << (8 * (k & 3));
         }
         if (ok) break;
-        scale = scale * 2.f;
+        if (scale < smax) scale = scale * 2.f;
     }
     ebyte = (qbits(scale) >> 23) & 0xFFu;
 }

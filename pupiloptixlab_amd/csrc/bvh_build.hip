@@ -1171,6 +1171,15 @@ int build_lbvh(const BvhBuildInput &in, BvhBuildOutput &out, uint32_t leaf_size,
                 hipLaunchKernelGGL(k_emit4, dim3(gi), dim3(kBlock), 0, s, n, vi, boxes, children, ranges, node_boxes,
                                    flags4, idx4, leaf_size, out.nodes4);
             (void)hipStreamSynchronize(s);
+            if (!err && out.num_nodes4) {
+                // depth of the 4-wide tree (the stack-capacity check and the statistics read it): its
+                // nodes are the flagged binary nodes, at binary depth 2 j on 4-wide level j + 1
+                std::vector<uint32_t> hd((size_t)n - 1), hf((size_t)n - 1);
+                err = hipMemcpy(hd.data(), depth, sizeof(uint32_t) * hd.size(), hipMemcpyDeviceToHost);
+                if (!err) err = hipMemcpy(hf.data(), flags4, sizeof(uint32_t) * hf.size(), hipMemcpyDeviceToHost);
+                for (size_t i = 0; i < hd.size(); i++)
+                    if (hf[i]) out.depth4 = std::max(out.depth4, hd[i] / 2u + 1u);
+            }
             if (idx4) (void)hipFree(idx4);
             }
         } else {
@@ -1231,6 +1240,13 @@ int build_lbvh(const BvhBuildInput &in, BvhBuildOutput &out, uint32_t leaf_size,
         out.num_records = nslots;
         if (n == 1 || leaf_root) out.depth4 = 1;  // the root is a leaf
         out.root_link4 = leaf_root ? (uint32_t)make_leaf(0u, (uint32_t)n) : 0u;
+        if (leaf_root && !in.object_space) {
+            // the root leaf is the whole tree: the 4-wide root the collapse emitted for 1 < n <= leaf_size
+            // is referenced by nothing, so it is not counted, exported, refitted or part of the node
+            // bound (a two-level BLAS keeps its count, which the combined node array is laid out by)
+            out.num_nodes4 = 0;
+            out.level_start.clear();
+        }
         if (!err) err = hipGetLastError();
     }
     (void)hipEventRecord(e1, s);
