@@ -291,6 +291,24 @@ static int TemporalMoving(Pupil::System &system, Pupil::pt::PTPass &pass, int fr
     return 0;
 }
 
+// PUPIL_HIDE="i,j,...": those instances get visibility mask 0 (the inspector's "visibility"
+// checkbox, gui.cpp:780-784) before the first OnRun, which refits once for all of them
+static bool HideFromEnv(Pupil::System &system) {
+    const char *spec = std::getenv("PUPIL_HIDE");
+    if (!spec) return true;
+    Pupil::world::World *w = system.GetWorld();
+    for (const char *p = spec; *p;) {
+        const int i = std::atoi(p);
+        if (i < 0 || (uint32_t)i >= w->Desc().num_instances || !w->SetInstanceVisibility((uint32_t)i, 0u)) {
+            std::fprintf(stderr, "PUPIL_HIDE: no instance %d\n", i);
+            return false;
+        }
+        while (*p && *p != ',') p++;
+        if (*p == ',') p++;
+    }
+    return true;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene.xml> [frames=16] [out.exr|.hdr|.pfm] [device=0]\n", argv[0]);
@@ -315,6 +333,8 @@ int main(int argc, char **argv) {
         system->AddPass(pt_pass.get());
         if (!system->SetScene(argv[1])) {
             rc = 1;
+        } else if (!HideFromEnv(*system)) {
+            rc = 2;
         } else if (const char *bench = std::getenv("PUPIL_BENCH")) {
             rc = Bench(*system, *pt_pass, bench);
         } else if (const char *waste = std::getenv("PUPIL_BENCH_WASTE")) {

@@ -310,6 +310,9 @@ typedef struct pupil_pt_counters {
     double frame_ms;
     uint64_t coop_dma;   /* reserved, always 0 */
     uint64_t coop_slots; /* reserved, always 0 */
+    /* instances whose visibility mask hides them now (pupil_pt_update_instances_masked);
+     * appended without an ABI bump: detect the entry by its symbol */
+    uint64_t hidden_instances;
 } pupil_pt_counters;
 
 typedef struct pupil_pt pupil_pt;
@@ -329,6 +332,30 @@ int pupil_pt_update_instance(pupil_pt *pt, uint32_t instance, const float to_wor
  * when the structure is updated.  pupil_pt_update_instance = n = 1. */
 int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, const float *to_world,
                               const float *to_object);
+/* IASManager::UpdateInstance (ias_manager.cpp:187-197; SetInstance :174): transform and
+ * visibilityMask of n instances, ONE refit.  to_world/to_object NULL = transforms kept;
+ * visibility_mask NULL = masks kept (then identical to pupil_pt_update_instances).  Both NULL,
+ * or an id out of range: PUPIL_ERR_INVALID.  Every instance is visible at create.
+ *
+ * RenderObject::visibility_mask (world/render_object.h:16; the inspector's checkbox,
+ * gui.cpp:780-784, fires RenderInstanceUpdate).  An instance is visible iff (mask & 0xFF) != 0:
+ * every optixTrace of the reference passes mask 255 (main.cu:77-82,158-163, emitter.h:95-98),
+ * so rays carry no mask of their own.  A hidden instance is hit by no ray: camera, extension
+ * and shadow rays, pupil_pt_trace_rays, and pupil_pt_motion_vectors, which reports the flow
+ * of what lies behind it.  The structure is refitted, not rebuilt, and showing the instance
+ * again restores it bit for bit.
+ *
+ * The emitter table does NOT change: the reference resets its emitters only on
+ * RenderInstanceTransform (world/world.cpp:45-54), and a visibility change goes straight to
+ * RenderInstanceUpdate.  A hidden emissive instance is therefore still picked by next-event
+ * estimation, and its own hidden geometry does not block the shadow ray, so it still lights
+ * the scene; camera and BSDF-sampled rays never see it.
+ *
+ * Removing an instance is not provided: the reference's path tracer never binds
+ * RenderInstanceRemove, and its SBT offsets go stale after a removal. */
+int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *ids,
+                                     const float *to_world, const float *to_object,
+                                     const uint32_t *visibility_mask);
 /* replaces the area-emitter table, selection CDF and env emitter (after an emissive instance moved);
  * rewritten in place on the engine's stream when their shapes are unchanged */
 int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
@@ -471,6 +498,12 @@ int pupil_world_add_const_env(pupil_world *w, const float radiance[3]);
  * (index into pupil_scene_desc.instances); the next pupil_world_get_desc has the new
  * instance matrices and area emitters (world/world.cpp:45-54) */
 int pupil_world_set_instance_transform(pupil_world *w, uint32_t instance, const float to_world[16]);
+/* RenderObject::visibility_mask (world/render_object.h:16; 1 at creation) of instance `instance`:
+ * the world remembers it for the passes, which hand it to pupil_pt_update_instances_masked
+ * (visible iff (mask & 0xFF) != 0).  pupil_world_get_desc does not change: a hidden emitter
+ * stays in the emitter table, as in the reference. */
+int pupil_world_set_instance_visibility(pupil_world *w, uint32_t instance, uint32_t visibility_mask);
+int pupil_world_get_instance_visibility(pupil_world *w, uint32_t instance, uint32_t *visibility_mask);
 /* resolves emitters (EmitterHelper), camera matrices (CameraHelper) and fills desc;
  * pointers stay valid until the world is modified or destroyed */
 int pupil_world_get_desc(pupil_world *w, pupil_scene_desc *desc);

@@ -99,7 +99,9 @@ class Counters(C.Structure):
                 ("leaf_loop_lanes", C.c_uint64), ("refills", C.c_uint64), ("refill_lanes", C.c_uint64),
                 ("frame_launches", C.c_uint64),
                 # ABI 6
-                ("frame_ms", C.c_double), ("coop_dma", C.c_uint64), ("coop_slots", C.c_uint64)]
+                ("frame_ms", C.c_double), ("coop_dma", C.c_uint64), ("coop_slots", C.c_uint64),
+                # appended with pupil_pt_update_instances_masked (no ABI bump: detect the symbol)
+                ("hidden_instances", C.c_uint64)]
 
     def as_dict(self):
         d = {name: getattr(self, name) for name, _ in self._fields_ if name != "pad_counters"}
@@ -124,6 +126,7 @@ SIGNATURES = {
     "pupil_pt_set_camera": (C.c_int, [C.c_void_p, f32p, f32p]),
     "pupil_pt_update_instance": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
     "pupil_pt_update_instances": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p]),
+    "pupil_pt_update_instances_masked": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p, u32p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_debug_fill_tlas_reserve": (C.c_int, [C.c_void_p, C.c_float]),
     "pupil_pt_render": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Launch), C.c_void_p]),
@@ -150,6 +153,8 @@ SIGNATURES = {
                                            C.c_uint32, C.c_uint32, C.POINTER(Texture), u32p]),
     "pupil_world_add_const_env": (C.c_int, [C.c_void_p, f32p]),
     "pupil_world_set_instance_transform": (C.c_int, [C.c_void_p, C.c_uint32, f32p]),
+    "pupil_world_set_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
     "pupil_world_get_desc": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_world_destroy": (None, [C.c_void_p]),
     "pupil_denoiser_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -42,6 +42,7 @@ struct TwoLevelAccel {
     uint32_t num_wnodes = 0;
     std::vector<std::vector<std::pair<int, std::array<float, 6>>>> entries;  // per instance: TLAS entries
     std::vector<uint32_t> inst_shape;                  // shape of each instance (0xFFFFFFFF: sphere)
+    std::vector<uint8_t> in_tlas;  // world mode: the instance was visible when the TLAS topology was built
     // world-mode TLAS refits (GPU, one launch per level, deepest first): the TLAS node ids
     // ordered by level from the deepest (d_tlas_order) and where each level starts in it
     uint32_t *d_tlas_order = nullptr;

@@ -46,6 +46,13 @@ __global__ __launch_bounds__(kBlock) void k_inst_bounds(const DevInstance *insts
     const uint32_t id = list[blockIdx.x];
     const DevInstance &in = insts[id];
     float *o = out + 6 * (size_t)id;
+    if (in.hidden) {  // DevInstance::hidden: the empty box, which the refits' fminf / fmaxf leave out
+        if (threadIdx.x == 0) {
+            o[0] = o[1] = o[2] = __builtin_huge_valf();
+            o[3] = o[4] = o[5] = -__builtin_huge_valf();
+        }
+        return;
+    }
     if (in.kind == PUPIL_SHAPE_SPHERE) {
         if (threadIdx.x == 0) {
             const float *m = in.to_world;
@@ -111,9 +118,13 @@ __global__ __launch_bounds__(kBlock) void k_world_records(const DevInstance *ins
             o[1] = b;
             continue;
         }
-        const vec3 w0 = xform_point(in.to_world, v3(a.x, a.y, a.z));
-        const vec3 w1 = xform_point(in.to_world, v3(b.x, b.y, b.z));
-        const vec3 w2 = xform_point(in.to_world, v3(c.x, c.y, c.z));
+        vec3 w0 = xform_point(in.to_world, v3(a.x, a.y, a.z));
+        vec3 w1 = xform_point(in.to_world, v3(b.x, b.y, b.z));
+        vec3 w2 = xform_point(in.to_world, v3(c.x, c.y, c.z));
+        // a hidden instance (visibilityMask 0, ias_manager.cpp:174,192): NaN vertices, which no ray
+        // hits (intersect_triangle's range test) and k_world_refit / k_tlas_refit leave out of
+        // every box; the id words are written as ever, and showing it recomputes the vertices
+        if (in.hidden) w0 = w1 = w2 = v3(__builtin_nanf(""));
         // flat record format (bvh_build.hip k_prim_setup): a.w = global id, b.w = instance, c.w = material bin
         o[0] = make_float4(w0.x, w0.y, w0.z, __uint_as_float(in.prim_offset + __float_as_uint(a.w)));
         o[1] = make_float4(w1.x, w1.y, w1.z, __uint_as_float(id));
@@ -453,6 +464,7 @@ void instance_margin(DevInstance &d, float vmax) {
 bool world_entries(TwoLevelAccel &acc, const DevInstance &d, uint32_t id, uint32_t sphere_rec, hipStream_t s) {
     auto &out = acc.entries[id];
     out.clear();
+    if (d.hidden) return true;  // no entry: a TLAS built now cannot reach the instance
     const std::array<float, 6> ibox = {d.wlo[0], d.wlo[1], d.wlo[2], d.whi[0], d.whi[1], d.whi[2]};
     if (d.kind == PUPIL_SHAPE_SPHERE) {
         out.push_back({make_leaf(sphere_rec, 1u), ibox});
@@ -523,6 +535,7 @@ bool refit_world_tlas(TwoLevelAccel &acc, hipStream_t s) {
 int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
                  const std::vector<uint32_t> &changed, hipStream_t s, bool refit) {
     const uint32_t n = (uint32_t)insts.size();
+    std::vector<DevInstance> staged;  // device copies of the changed instances: every path below synchronises s
     if (!changed.empty()) {
         if (hipMemcpyAsync(acc.d_list, changed.data(), sizeof(uint32_t) * changed.size(), hipMemcpyHostToDevice, s) !=
             hipSuccess)
@@ -553,7 +566,13 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
                 insts[id].wlo[k] = h[6 * (size_t)id + k];
                 insts[id].whi[k] = h[6 * (size_t)id + 3 + k];
             }
-            if (hipMemcpyAsync(d_insts + id, &insts[id], sizeof(DevInstance), hipMemcpyHostToDevice, s) != hipSuccess)
+        }
+        // a hidden sphere is rejected through its device copy's to_object (pt_scene.h device_instance);
+        // its record carries no geometry, and k_tlas_refit bounds it by the empty instance box
+        staged.reserve(changed.size());
+        for (uint32_t id : changed) {
+            staged.push_back(device_instance(insts[id]));
+            if (hipMemcpyAsync(d_insts + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice, s) != hipSuccess)
                 return -1;
         }
     }
@@ -568,7 +587,14 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
             }
         for (uint32_t id : changed)
             if (!world_entries(acc, insts[id], id, sphere_rec[id], s)) return -1;
+        // A refit keeps the topology: hiding empties the instance's boxes (NaN records, the empty
+        // instance box) and every node above them is re-encoded without it.  Showing an instance
+        // that was hidden when this TLAS was BUILT needs its entries, i.e. a build.
+        if (acc.in_tlas.size() != n) acc.in_tlas.assign(n, 0);
+        for (uint32_t id : changed)
+            if (!insts[id].hidden && !acc.in_tlas[id]) refit = false;
         if (refit && refit_world_tlas(acc, s)) return 0;
+        for (uint32_t i = 0; i < n; i++) acc.in_tlas[i] = insts[i].hidden ? 0 : 1;
         std::vector<HostBox> eb;
         std::vector<int> links;
         for (uint32_t i = 0; i < n; i++)
@@ -649,9 +675,10 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
             boxes[i].lo[k] = insts[i].wlo[k];
             boxes[i].hi[k] = insts[i].whi[k];
         }
-    std::vector<uint32_t> ids;  // instances with geometry (an empty mesh has no BLAS)
+    std::vector<uint32_t> ids;  // visible instances with geometry (an empty mesh has no BLAS)
     for (uint32_t i = 0; i < n; i++)
-        if (insts[i].kind == PUPIL_SHAPE_SPHERE || insts[i].blas_root != kTraverseDone) ids.push_back(i);
+        if (!insts[i].hidden && (insts[i].kind == PUPIL_SHAPE_SPHERE || insts[i].blas_root != kTraverseDone))
+            ids.push_back(i);
     std::vector<Bvh4Node> nodes;
     uint32_t depth = 0, binned = 0;
     const int root = ids.empty() ? kTraverseDone

@@ -40,6 +40,22 @@ PT_HD float qdecode(float origin, uint32_t q, float scale) { return origin + (fl
 template <int N>
 PT_HD void quantize_axis_n(float lo, float hi, const float *clo, const float *chi, int nk, float &origin,
                            uint32_t &ebyte, uint32_t *qlo, uint32_t *qhi) {
+    if (!(lo <= hi)) {
+        // An empty node: every primitive under it belongs to a hidden instance, so the refit
+        // left it the box (+inf, -inf).  No plane is derived from the infinities: origin 0,
+        // scale 1 and every child's planes 255 / 0, an interval no ray passes through (the near
+        // plane lies 255 beyond the far one, against a slab slack of 2^-20 (|o_ray| + M)).
+        // The links stay, so a later refit can bring the children back.  An empty CHILD of a
+        // node that also has visible ones needs no case of its own: its interval (+inf, -inf)
+        // clamps to the same planes 255 / 0 below.
+        origin = 0.f;
+        ebyte = 127u;
+        for (int w = 0; w < N / 4; w++) {
+            qlo[w] = 0xFFFFFFFFu;
+            qhi[w] = 0u;
+        }
+        return;
+    }
     origin = lo;
     const float ext = hi - lo;
     // The stored scale is the exponent byte alone, so it must be a normal float: a denormal

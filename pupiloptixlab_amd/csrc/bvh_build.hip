@@ -1376,6 +1376,18 @@ __global__ void k_refit_records(BvhBuildInput in, uint32_t n, float4 *recs_base,
     if (id == kRecHole || !moved[id]) return;  // a hole slot, or an unmoved instance
     const uint32_t gid = __float_as_uint(recs[0].w) & ~kPrimSphereBit;
     const DevInstance &inst = in.instances[id];
+    if (inst.hidden) {
+        // visibilityMask 0 (ias_manager.cpp:174,192): vertices no ray hits (intersect_triangle's
+        // range test fails on NaN; a sphere is rejected through the NaN to_object of its instance's
+        // device copy, pt_scene.h device_instance: its record only has to stay out of the boxes)
+        // and that k_refit_level's fminf / fmaxf leave out of every box.  The id words stay:
+        // showing the instance again flags it moved and the branches below restore the record.
+        const float q = __builtin_nanf("");
+        recs[0] = make_float4(q, q, q, recs[0].w);
+        recs[1] = make_float4(q, q, q, recs[1].w);
+        if (inst.kind != PUPIL_SHAPE_SPHERE) recs[2] = make_float4(q, q, q, recs[2].w);
+        return;
+    }
     if (inst.kind == PUPIL_SHAPE_SPHERE) {
         const float *m = inst.to_world;
         const vec3 c = v3(m[3], m[7], m[11]);
@@ -1456,8 +1468,9 @@ __global__ void k_refit_level(Bvh4Node *nodes, uint32_t lo, uint32_t hi, const f
 }  // namespace
 
 int refit_bvh4(const BvhBuildInput &in, BvhBuildOutput &out, const uint8_t *moved, float *nbox, hipStream_t s,
-               double *ms) {
-    if (out.level_start.size() < 2 || !out.nodes4 || out.num_nodes4 == 0) return -1;
+               double *ms, bool records_only) {
+    const bool levels = out.level_start.size() >= 2 && out.nodes4 && out.num_nodes4 != 0;
+    if (!levels && !(records_only && out.num_nodes4 == 0 && out.prims)) return -1;
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
@@ -1465,8 +1478,8 @@ int refit_bvh4(const BvhBuildInput &in, BvhBuildOutput &out, const uint8_t *move
     hipError_t err = hipSuccess;
     {
         const uint32_t n = out.num_records;  // record slots (holes are skipped)
-        hipLaunchKernelGGL(k_refit_records, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, in, n, out.prims, moved);
-        for (size_t L = out.level_start.size() - 1; L-- > 0;) {
+        if (n) hipLaunchKernelGGL(k_refit_records, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, in, n, out.prims, moved);
+        for (size_t L = levels ? out.level_start.size() - 1 : 0; L-- > 0;) {
             const uint32_t lo = out.level_start[L], hi = out.level_start[L + 1];
             const uint32_t g = std::max(1u, std::min(4096u, (hi - lo + kBlock - 1) / kBlock));
             hipLaunchKernelGGL(k_refit_level, dim3(g), dim3(kBlock), 0, s, out.nodes4, lo, hi, out.prims, nbox);

@@ -1257,9 +1257,19 @@ int pupil_pt_set_camera(pupil_pt *pt, const float sample_to_camera[16], const fl
 // on the engine's stream after every render enqueued so far (no device-wide sync: other
 // streams of the process keep running); returns once the structure is updated.
 // Emitters follow with pupil_pt_update_emitters.
-int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, const float *to_world,
-                              const float *to_object) {
-    if (!pt || (n && (!ids || !to_world || !to_object))) return fail(PUPIL_ERR_INVALID, "null argument");
+// With visibility_mask: IASManager::UpdateInstance (ias_manager.cpp:187-197), which copies
+// RenderObject::visibility_mask into OptixInstance::visibilityMask next to the transform.  A
+// hidden instance ((mask & 0xFF) == 0; every optixTrace passes 255) is the same refit with "no
+// geometry" as the new geometry: its records get NaN vertices, which no ray hits and no box
+// includes, and keep their id words, so showing it again restores them (bvh_build.hip
+// k_refit_records; accel_two_level.hip k_world_records / rebuild_tlas).  The rebuild paths
+// (PUPIL_FLAT_UPDATE / PUPIL_TL_UPDATE = rebuild, the depth-overflow fallback, a tree without a
+// level order) build over all the geometry and then apply the masks the same way.  The emitter
+// table is not touched (world/world.cpp:45-54 resets it on RenderInstanceTransform only).
+int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *ids, const float *to_world,
+                                     const float *to_object, const uint32_t *visibility_mask) {
+    if (!pt || (n && (!ids || (!to_world && !visibility_mask) || !to_world != !to_object)))
+        return fail(PUPIL_ERR_INVALID, "null argument");
     for (uint32_t k = 0; k < n; k++)
         if (ids[k] >= pt->h_insts.size()) return fail(PUPIL_ERR_INVALID, "instance index out of range");
     if (n == 0) return PUPIL_OK;
@@ -1270,14 +1280,23 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
     for (uint32_t k = 0; k < n; k++) {
         const uint32_t id = ids[k];
         DevInstance &d = pt->h_insts[id];
-        std::memcpy(d.to_world, to_world + 12 * (size_t)k, sizeof(d.to_world));
-        std::memcpy(d.to_object, to_object + 12 * (size_t)k, sizeof(d.to_object));
-        if (pt->two_level) refresh_instance_margins(d);  // they depend on the transform
+        if (to_world) {
+            std::memcpy(d.to_world, to_world + 12 * (size_t)k, sizeof(d.to_world));
+            std::memcpy(d.to_object, to_object + 12 * (size_t)k, sizeof(d.to_object));
+            if (pt->two_level) refresh_instance_margins(d);  // they depend on the transform
+        }
+        if (visibility_mask) d.hidden = (visibility_mask[k] & 0xFFu) == 0u ? 1u : 0u;
         if (std::find(changed.begin(), changed.end(), id) == changed.end()) changed.push_back(id);
     }
-    for (uint32_t id : changed)  // h_insts outlives the copies (the stream is synchronised below)
-        HIP_TRY(hipMemcpyAsync(pt->d_insts + id, &pt->h_insts[id], sizeof(DevInstance), hipMemcpyHostToDevice,
+    // the device copies (pt_scene.h device_instance: a hidden sphere's to_object is NaN there);
+    // `staged` outlives the copies (the stream is synchronised below)
+    std::vector<DevInstance> staged;
+    staged.reserve(changed.size());
+    for (uint32_t id : changed) {
+        staged.push_back(device_instance(pt->h_insts[id]));
+        HIP_TRY(hipMemcpyAsync(pt->d_insts + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
                                pt->own_stream));
+    }
     pt->refits++;
     if (pt->two_level) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -1295,14 +1314,23 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
         return PUPIL_OK;
     }
     BvhBuildInput bin{pt->num_prims, pt->d_prim_inst, pt->d_insts, pt->d_mats};
-    // refit in place (PUPIL_FLAT_UPDATE=rebuild: full rebuild)
-    const char *fu = std::getenv("PUPIL_FLAT_UPDATE");
-    if (!(fu && std::strcmp(fu, "rebuild") == 0)) {
+    // the flags of the instances whose records are rewritten, and the node-box scratch
+    const auto refit_flags = [&](bool hidden_ones) -> int {
         if (!pt->d_moved) HIP_TRY(pt->alloc(&pt->d_moved, pt->h_insts.size()));
         if (!pt->refit_box) HIP_TRY(pt->alloc(&pt->refit_box, 6 * (size_t)std::max(1u, pt->bvh.num_nodes4)));
         pt->h_moved.assign(pt->h_insts.size(), 0);
-        for (uint32_t id : changed) pt->h_moved[id] = 1;
+        if (hidden_ones) {
+            for (size_t i = 0; i < pt->h_insts.size(); i++) pt->h_moved[i] = pt->h_insts[i].hidden ? 1 : 0;
+        } else {
+            for (uint32_t id : changed) pt->h_moved[id] = 1;
+        }
         HIP_TRY(hipMemcpyAsync(pt->d_moved, pt->h_moved.data(), pt->h_moved.size(), hipMemcpyHostToDevice, pt->own_stream));
+        return PUPIL_OK;
+    };
+    // refit in place (PUPIL_FLAT_UPDATE=rebuild: full rebuild)
+    const char *fu = std::getenv("PUPIL_FLAT_UPDATE");
+    if (!(fu && std::strcmp(fu, "rebuild") == 0)) {
+        if (const int rc = refit_flags(false)) return rc;
         double rms = 0.0;
         if (refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &rms) == 0) {
             pt->totals.build_ms = rms;
@@ -1329,8 +1357,24 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
     pt->sc.root_link4 = nb.root_link4;
     pt->totals.bvh_nodes = nb.num_nodes4;
     pt->totals.bvh_depth = nb.depth4;
+    bool any_hidden = false;
+    for (const DevInstance &d : pt->h_insts) any_hidden = any_hidden || d.hidden != 0u;
+    if (any_hidden) {  // the build covered every instance: the masks go on like a refit's
+        if (const int rc = refit_flags(true)) return rc;
+        double hms = 0.0;
+        const int hrc = refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &hms, true);
+        if (hrc == -1) return fail(PUPIL_ERR_UNSUPPORTED, "hidden instances need the BVH4 level order");
+        if (hrc != 0) return fail(PUPIL_ERR_HIP, "applying the visibility masks failed");
+        ms += hms;
+    }
     pt->totals.build_ms = ms;
     return refresh_node_bound(pt);
+}
+
+int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, const float *to_world,
+                              const float *to_object) {
+    if (!pt || (n && (!ids || !to_world || !to_object))) return fail(PUPIL_ERR_INVALID, "null argument");
+    return pupil_pt_update_instances_masked(pt, n, ids, to_world, to_object, nullptr);
 }
 
 int pupil_pt_update_instance(pupil_pt *pt, uint32_t instance, const float to_world[12], const float to_object[12]) {
@@ -1501,6 +1545,7 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     c.ring_bytes = pt->ring_bytes + sizeof(float) * (uint64_t)pt->aov_cap;
     c.ring_budget_bytes = (uint64_t)pt->pipe_budget;
     c.accel_refits = pt->refits;
+    for (const DevInstance &d : pt->h_insts) c.hidden_instances += d.hidden ? 1u : 0u;
     c.frame_launches = pt->frame_launches;
     for (int a = 0; a < 3; a++) c.node_bound[a] = pt->sc.node_bound[a];
     if (pt->last_paths) {

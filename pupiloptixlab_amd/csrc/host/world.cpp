@@ -937,6 +937,10 @@ struct pupil_world {
     // programmatic API keeps a table and copies into each instance
     std::vector<Pupil::resource::Material> materials;
     pupil_scene_desc desc{};
+    // RenderObject::visibility_mask (world/render_object.h:16: 1 at creation) per desc instance;
+    // instances never set have no entry.  Not part of the desc: the emitters of a hidden
+    // instance stay (world/world.cpp:45-54 resets them on RenderInstanceTransform only)
+    std::vector<uint32_t> visibility;
 };
 
 extern "C" {
@@ -953,6 +957,7 @@ int pupil_world_load_xml(pupil_world *w, const char *path) {
     if (!w || !path) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
     if (!std::filesystem::exists(path)) return Pupil::werr(PUPIL_ERR_IO, std::string("scene file does not exist: ") + path);
     w->w.scene = Pupil::resource::Scene{};
+    w->visibility.clear();  // a new scene: every instance visible
     std::string err;
     try {
         if (!w->w.scene.LoadFromXML(path, err)) return Pupil::werr(PUPIL_ERR_IO, "scene load failed: " + err);
@@ -1055,6 +1060,27 @@ int pupil_world_set_instance_transform(pupil_world *w, uint32_t instance, const 
         }
     }
     return Pupil::werr(PUPIL_ERR_INVALID, "instance out of range");
+}
+
+static uint32_t desc_instance_count(const pupil_world *w) {
+    uint32_t k = 0;  // desc instance k = k-th scene instance with a shape (World::Build skips the others)
+    for (const auto &ins : w->w.scene.instances) k += ins.shape >= 0 ? 1u : 0u;
+    return k;
+}
+
+int pupil_world_set_instance_visibility(pupil_world *w, uint32_t instance, uint32_t visibility_mask) {
+    if (!w) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    if (instance >= desc_instance_count(w)) return Pupil::werr(PUPIL_ERR_INVALID, "instance out of range");
+    if (w->visibility.size() <= instance) w->visibility.resize((size_t)instance + 1, 1u);
+    w->visibility[instance] = visibility_mask;
+    return PUPIL_OK;
+}
+
+int pupil_world_get_instance_visibility(pupil_world *w, uint32_t instance, uint32_t *visibility_mask) {
+    if (!w || !visibility_mask) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    if (instance >= desc_instance_count(w)) return Pupil::werr(PUPIL_ERR_INVALID, "instance out of range");
+    *visibility_mask = instance < w->visibility.size() ? w->visibility[instance] : 1u;
+    return PUPIL_OK;
 }
 
 int pupil_world_add_const_env(pupil_world *w, const float radiance[3]) {

@@ -274,8 +274,12 @@ void free_lbvh(BvhBuildOutput &out);
 // `moved` (device, one byte per instance) get their new world vertices and every BVH4 node
 // box is refitted bottom up (topology kept, like the reference's IAS update); nbox: device
 // scratch of 6 floats per node.  Needs the breadth-first level order; -1 when unavailable.
+// The records of a hidden instance (DevInstance::hidden) get NaN vertices instead, which no
+// ray hits and no box includes; a node with nothing visible under it is encoded empty
+// (bvh4_quant.h).  records_only: a tree that is one root leaf (no nodes) is accepted too and
+// only its records are rewritten (applying the masks to a fresh build).
 int refit_bvh4(const BvhBuildInput &in, BvhBuildOutput &out, const uint8_t *moved, float *nbox, hipStream_t s,
-               double *ms);
+               double *ms, bool records_only = false);
 // BVH4 over n >= 2 boxes (6 floats each: lo xyz, hi xyz) with the flattened build's PLOC +
 // SAH collapse, one box per leaf: nodes (root 0, parents first) and, for leaf link
 // make_leaf(p, 1), the box order[p]; depth = 4-wide levels

@@ -91,7 +91,24 @@ struct DevInstance {
     // [obj_nbase, obj_nbase + obj_ncount) -> world nodes from wnode_base
     uint32_t obj_nbase, obj_ncount, wnode_base;
     float vmax;  // largest |object-space vertex coordinate| of the shape (margins)
+    // OptixInstance::visibilityMask & 0xFF == 0 (ias_manager.cpp:174,192): no ray hits the
+    // instance.  The builders and refits give its records NaN vertices and leave it out of
+    // every box (in the struct's tail padding: the stride stays 224 B)
+    uint32_t hidden;
 };
+static_assert(sizeof(DevInstance) == 224, "DevInstance stride");
+
+// What the device holds for an instance.  A sphere is tested through its instance's to_object
+// and not through its record, so the device copy of a HIDDEN sphere gets a NaN to_object:
+// intersect_unit_sphere then fails both of its range tests and the traversal kernels need no
+// visibility test of their own.  Nothing else reads the transform of an instance no ray hits; the
+// host copy keeps the real one.
+inline DevInstance device_instance(const DevInstance &d) {
+    DevInstance o = d;
+    if (d.hidden && d.kind == PUPIL_SHAPE_SPHERE)
+        for (float &x : o.to_object) x = __builtin_nanf("");
+    return o;
+}
 
 // 4-wide node with 8-bit quantized child boxes: 64 B = one half L2 line holds
 // what four 64 B BVH2 nodes spread over two levels.  Child k's box is

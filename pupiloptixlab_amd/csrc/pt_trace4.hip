@@ -535,6 +535,9 @@ __global__ __launch_bounds__(256) void k_node_bound(const Bvh4Node *nodes, uint6
     float m[3] = {0.f, 0.f, 0.f};
     for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256ull) {
         const Bvh4Node &b = nodes[i];
+        // an empty node (all under it hidden, bvh4_quant.h: every x interval 255 / 0, which no
+        // node with a visible child has) bounds nothing and must not loosen every ray's slack
+        if (b.qlo_x == 0xFFFFFFFFu && b.qhi_x == 0u) continue;
         m[0] = fmaxf(m[0], fabsf(b.ox) + 512.f * b.sx);  // upward rounding: slack of slab_error
         m[1] = fmaxf(m[1], fabsf(b.oy) + 512.f * b.sy);
         m[2] = fmaxf(m[2], fabsf(b.oz) + 512.f * b.sz);

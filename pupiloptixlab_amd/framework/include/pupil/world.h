@@ -66,6 +66,12 @@ public:
     // matrices, area emitters) and fires EWorldEvent::RenderInstanceUpdate.  Safe from
     // any thread: the edit happens under Mutex(), the event is fired after it.
     bool SetInstanceTransform(uint32_t instance, const float to_world[16]) noexcept;
+    // RenderObject::visibility_mask (world/render_object.h:16; the inspector's checkbox,
+    // gui.cpp:780-784): visible iff mask & 0xFF.  Fires EWorldEvent::RenderInstanceUpdate; the
+    // pass picks the mask up at the top of its next OnRun.  Desc() does not change: a hidden
+    // emitter stays in the emitter table, as in the reference (world/world.cpp:45-54).
+    bool SetInstanceVisibility(uint32_t instance, uint32_t mask) noexcept;
+    uint32_t InstanceVisibility(uint32_t instance) noexcept;
 
     pupil_world *handle() noexcept { return m_world; }
     // Flattened scene for pupil_pt_create (valid until the world changes); a thread

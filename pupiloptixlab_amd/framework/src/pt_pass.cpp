@@ -44,9 +44,11 @@ void PTPass::OnRun() noexcept {
             std::scoped_lock lock(m_world->Mutex());
             const pupil_scene_desc &d = m_world->Desc();
             std::vector<float> tw(12 * moved.size()), to(12 * moved.size());
+            std::vector<uint32_t> vis(moved.size());  // ias_manager.cpp:187-197: transform and mask together
             bool emissive = false;
             for (size_t k = 0; k < moved.size(); k++) {
                 const pupil_instance &ins = d.instances[moved[k]];
+                vis[k] = m_world->InstanceVisibility(moved[k]);
                 std::memcpy(&tw[12 * k], ins.to_world, sizeof(ins.to_world));
                 std::memcpy(&to[12 * k], ins.to_object, sizeof(ins.to_object));
                 emissive = emissive || ins.emitter_offset >= 0;
@@ -56,8 +58,8 @@ void PTPass::OnRun() noexcept {
                 if (12 * (size_t)moved[k] + 12 <= m_to_world.size())
                     std::memcpy(&m_to_world[12 * (size_t)moved[k]], &tw[12 * k], 12 * sizeof(float));
             m_instances_moved = true;
-            if (pupil_pt_update_instances(m_engine, (uint32_t)moved.size(), moved.data(), tw.data(), to.data()) !=
-                PUPIL_OK)
+            if (pupil_pt_update_instances_masked(m_engine, (uint32_t)moved.size(), moved.data(), tw.data(), to.data(),
+                                                 vis.data()) != PUPIL_OK)
                 Log("%s: instance update failed: %s", name.c_str(), pupil_last_error());
             else if (emissive && pupil_pt_update_emitters(m_engine, &d) != PUPIL_OK)
                 Log("%s: emitter update failed: %s", name.c_str(), pupil_last_error());
@@ -155,6 +157,14 @@ void PTPass::SetScene(world::World *world) noexcept {
     m_instances_moved = false;
     m_have_cam = false;
     m_dirty = true;
+    // the engine creates every instance visible: instances hidden before the scene was set
+    std::vector<uint32_t> hidden, zero;
+    for (uint32_t i = 0; i < sd.num_instances; i++)
+        if ((world->InstanceVisibility(i) & 0xFFu) == 0u) hidden.push_back(i);
+    zero.assign(hidden.size(), 0u);
+    if (!hidden.empty() && pupil_pt_update_instances_masked(m_engine, (uint32_t)hidden.size(), hidden.data(), nullptr,
+                                                            nullptr, zero.data()) != PUPIL_OK)
+        Log("%s: instance visibility failed: %s", name.c_str(), pupil_last_error());
 }
 
 bool PTPass::ComputeMotionVectors() noexcept {

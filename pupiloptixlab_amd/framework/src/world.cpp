@@ -79,4 +79,24 @@ bool World::SetInstanceTransform(uint32_t instance, const float to_world[16]) no
     return true;
 }
 
+bool World::SetInstanceVisibility(uint32_t instance, uint32_t mask) noexcept {
+    {
+        std::scoped_lock lock(m_mutex);
+        if (!m_world || pupil_world_set_instance_visibility(m_world, instance, mask) != PUPIL_OK) {
+            Log("instance visibility failed: %s", pupil_last_error());
+            return false;
+        }
+    }
+    InstanceUpdate u{this, instance};
+    EventDispatcher<EWorldEvent::RenderInstanceUpdate>(&u);
+    return true;
+}
+
+// the caller holds Mutex() where another thread may edit the world
+uint32_t World::InstanceVisibility(uint32_t instance) noexcept {
+    uint32_t mask = 1u;
+    if (m_world) (void)pupil_world_get_instance_visibility(m_world, instance, &mask);
+    return mask;
+}
+
 }  // namespace Pupil::world

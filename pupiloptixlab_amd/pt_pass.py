@@ -132,8 +132,10 @@ class PTPass(Pass):
         self.update_instances(world, [instance])
 
     def update_instances(self, world, instances):
-        """Several moved instances with ONE refit of the acceleration structure
-        (pupil_pt_update_instances), then the emitter table if any of them emits."""
+        """Several moved, hidden or shown instances with ONE refit of the acceleration
+        structure: their transforms and visibility masks as the world holds them
+        (pupil_pt_update_instances_masked, IASManager::UpdateInstance), then the emitter table
+        if any of them emits (a hidden emitter stays in it, as in the reference)."""
         import numpy as np
 
         ids = sorted({int(i) for i in instances})
@@ -143,9 +145,13 @@ class PTPass(Pass):
         tw = np.array([list(desc.instances[i].to_world) for i in ids], np.float32)
         to = np.array([list(desc.instances[i].to_object) for i in ids], np.float32)
         idv = np.array(ids, np.uint32)
-        check(self._lib.pupil_pt_update_instances(self._pt, len(ids), idv.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  tw.ctypes.data_as(C.POINTER(C.c_float)),
-                                                  to.ctypes.data_as(C.POINTER(C.c_float))))
+        vis = np.array([world.instance_visibility(i) if hasattr(world, "instance_visibility") else 1 for i in ids],
+                       np.uint32)
+        check(self._lib.pupil_pt_update_instances_masked(self._pt, len(ids),
+                                                         idv.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         tw.ctypes.data_as(C.POINTER(C.c_float)),
+                                                         to.ctypes.data_as(C.POINTER(C.c_float)),
+                                                         vis.ctypes.data_as(C.POINTER(C.c_uint32))))
         if self._to_world is not None:
             if not self._moved:  # several updates before one render: the first one's "before" stays
                 self._prev_to_world = self._to_world.copy()
@@ -224,6 +230,15 @@ class PTPass(Pass):
         self._prev_to_world = None
         self._moved = False
         self._alloc_buffers()
+        # the engine creates every instance visible: the masks the world remembers go on now
+        if self._world is not None and hasattr(self._world, "instance_visibility"):
+            hidden = [i for i in range(desc.num_instances) if (self._world.instance_visibility(i) & 0xFF) == 0]
+            if hidden:
+                idv = np.array(hidden, np.uint32)
+                vis = np.zeros(len(hidden), np.uint32)
+                check(self._lib.pupil_pt_update_instances_masked(self._pt, len(hidden),
+                                                                 idv.ctypes.data_as(C.POINTER(C.c_uint32)), None, None,
+                                                                 vis.ctypes.data_as(C.POINTER(C.c_uint32))))
 
     def _alloc_buffers(self):
         n = self.local_pixel_count() if self.tile[2] > 1 else self.width * self.height

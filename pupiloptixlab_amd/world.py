@@ -198,6 +198,17 @@ class World:
         check(self._lib.pupil_world_set_instance_transform(self._h, int(instance), _ptr(m)))
         self._desc = None
 
+    def set_instance_visibility(self, instance: int, mask: int):
+        """RenderObject::visibility_mask of instance `instance` (world/render_object.h:16): visible
+        iff mask & 0xFF.  desc() does not change -- a hidden emitter stays in the emitter table,
+        as in the reference; PTPass.update_instances hands the mask to the engine."""
+        check(self._lib.pupil_world_set_instance_visibility(self._h, int(instance), int(mask) & 0xFFFFFFFF))
+
+    def instance_visibility(self, instance: int) -> int:
+        out = C.c_uint32()
+        check(self._lib.pupil_world_get_instance_visibility(self._h, int(instance), C.byref(out)))
+        return out.value
+
     def add_const_env(self, radiance):
         r = _f32(radiance, 3)
         check(self._lib.pupil_world_add_const_env(self._h, _ptr(r)))
