@@ -356,6 +356,37 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
 int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *ids,
                                      const float *to_world, const float *to_object,
                                      const uint32_t *visibility_mask);
+/* Deformable meshes: new vertices for mesh shape `shape` (index into pupil_scene_desc.shapes),
+ * the geometry-AS counterpart (OPTIX_BUILD_OPERATION_UPDATE) of the instance update above.
+ * positions: 3 * num_vertices floats as at create; normals: the same count, or NULL = the
+ * normals stay.  Vertex count, indices and texcoords never change.  Every instance of the
+ * shape follows with ONE refit (accel_refits + 1, build_ms = the call's time): records, node
+ * boxes and shading records are rewritten in place, hidden instances stay hidden and show the
+ * new vertices when shown.  The next render equals, bit for bit, a render of an engine created
+ * on the deformed mesh.
+ *   PUPIL_VERTS_DEVICE   positions / normals are device pointers: the copy (device to device,
+ *                        into the engine's own arrays) is ordered after the work enqueued so far
+ *                        on hip_stream (a hipStream_t, NULL = the null stream) by an event; the
+ *                        vertices never pass through the host.  hip_stream is ignored without it.
+ *   PUPIL_VERTS_REBUILD  rebuild the whole acceleration structure with the builders of
+ *                        pupil_pt_create instead of refitting: for deformations so large that
+ *                        the refitted tree traces badly.  There is no per-BLAS rebuild.
+ * PUPIL_ERR_INVALID: pt or positions NULL, shape out of range or a PUPIL_SHAPE_SPHERE, normals
+ * for a shape created without them, unknown flags.  If an instance of the shape is emissive
+ * (emitter_offset >= 0) its area emitters must follow through pupil_pt_update_emitters, as after
+ * a transform (pupil_world_set_mesh_vertices + pupil_world_get_desc produce them); the engine
+ * cannot derive that table from device vertices, so PUPIL_VERTS_DEVICE on such a shape returns
+ * PUPIL_ERR_UNSUPPORTED.  Ordered after every render enqueued so far; frames in flight are
+ * dropped; returns once the structure is updated.  accel_refits counts successful calls only.  If
+ * the call fails after the argument checks (PUPIL_ERR_HIP / _OOM / _UNSUPPORTED from the refit or
+ * the builders), the engine's vertex arrays already hold the new vertices while the acceleration
+ * structure still bounds the old ones: do not render until a later call for this shape succeeds
+ * (PUPIL_VERTS_REBUILD is the one that depends on nothing left behind).  pupil_pt_motion_vectors does not see vertex
+ * motion (camera and rigid instance motion only).  No ABI bump: detect the symbol. */
+#define PUPIL_VERTS_DEVICE 1u
+#define PUPIL_VERTS_REBUILD 2u
+int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *positions, const float *normals,
+                                   uint32_t flags, void *hip_stream);
 /* replaces the area-emitter table, selection CDF and env emitter (after an emissive instance moved);
  * rewritten in place on the engine's stream when their shapes are unchanged */
 int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
@@ -504,6 +535,14 @@ int pupil_world_set_instance_transform(pupil_world *w, uint32_t instance, const 
  * stays in the emitter table, as in the reference. */
 int pupil_world_set_instance_visibility(pupil_world *w, uint32_t instance, uint32_t visibility_mask);
 int pupil_world_get_instance_visibility(pupil_world *w, uint32_t instance, uint32_t *visibility_mask);
+/* Deformable meshes on the host side: new vertices of mesh shape `shape` (index into
+ * pupil_scene_desc.shapes), copied into the world's own mesh.  positions: 3 floats per vertex,
+ * the vertex count the shape has; normals: the same count, or NULL = kept (PUPIL_ERR_INVALID
+ * for a mesh without normals, a sphere, a shape out of range, a null argument).  The next
+ * pupil_world_get_desc has the new vertices and, for emissive instances of the shape, the new
+ * area emitters (world-space triangles, areas, select probabilities) that
+ * pupil_pt_update_emitters takes after pupil_pt_update_shape_vertices. */
+int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *positions, const float *normals);
 /* resolves emitters (EmitterHelper), camera matrices (CameraHelper) and fills desc;
  * pointers stay valid until the world is modified or destroyed */
 int pupil_world_get_desc(pupil_world *w, pupil_scene_desc *desc);

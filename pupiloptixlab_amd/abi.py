@@ -17,6 +17,7 @@ SHAPE_MESH, SHAPE_SPHERE = 0, 1
 
 PUPIL_OK = OK = 0
 ERR_INVALID, ERR_HIP, ERR_OOM, ERR_IO, ERR_UNSUPPORTED = -1, -2, -3, -4, -5
+VERTS_DEVICE, VERTS_REBUILD = 1, 2  # pupil_pt_update_shape_vertices flags
 IMAGE_AUTO, IMAGE_EXR, IMAGE_HDR, IMAGE_PFM = 0, 1, 2, 3
 ERR_NAMES = {-1: "PUPIL_ERR_INVALID", -2: "PUPIL_ERR_HIP", -3: "PUPIL_ERR_OOM", -4: "PUPIL_ERR_IO",
              -5: "PUPIL_ERR_UNSUPPORTED"}
@@ -127,6 +128,8 @@ SIGNATURES = {
     "pupil_pt_update_instance": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
     "pupil_pt_update_instances": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p]),
     "pupil_pt_update_instances_masked": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p, u32p]),
+    "pupil_pt_update_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                  C.c_void_p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_debug_fill_tlas_reserve": (C.c_int, [C.c_void_p, C.c_float]),
     "pupil_pt_render": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Launch), C.c_void_p]),
@@ -155,6 +158,7 @@ SIGNATURES = {
     "pupil_world_set_instance_transform": (C.c_int, [C.c_void_p, C.c_uint32, f32p]),
     "pupil_world_set_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
+    "pupil_world_set_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
     "pupil_world_get_desc": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_world_destroy": (None, [C.c_void_p]),
     "pupil_denoiser_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -48,6 +48,12 @@ struct TwoLevelAccel {
     uint32_t *d_tlas_order = nullptr;
     std::vector<uint32_t> tlas_level_start;
     std::vector<std::vector<uint32_t>> shape_levels;   // per shape: BVH4 level starts of its BLAS (+ end)
+    // per shape, for vertex updates (update_shape_blas): BLAS record slots (0 = no BLAS), first node /
+    // record slot / shading record in the combined arrays, and whether the BLAS is one root leaf
+    std::vector<uint32_t> shape_slots, shape_node_base, shape_rec_base, shape_attr_base;
+    std::vector<uint8_t> shape_root_leaf;
+    float *d_objbox = nullptr;     // exact box of every object-space node (6 floats), scratch of the BLAS refits
+    uint32_t *d_vmax = nullptr;    // update_shape_blas: the max |coordinate| reduction's result
     uint32_t root_link4 = (uint32_t)kTraverseDone;
     double build_ms = 0.0;
 };
@@ -74,6 +80,16 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
 // refit (world mode): keep the TLAS topology and refit its boxes instead of rebuilding.
 int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
                  const std::vector<uint32_t> &changed, hipStream_t s, bool refit = false);
+// Deformed mesh: shape `shape` (its device arrays in `sh` hold the new vertices) gets its
+// object-space BLAS records rewritten in place, its BLAS boxes refitted bottom up and its
+// shading records refreshed; topology, record slots and id words stay.  vmax (or null):
+// receives the new largest |coordinate|, reduced on the device (synchronises s).  The
+// instances' margins and rebuild_tlas over the shape's instances follow at the caller.
+int update_shape_blas(TwoLevelAccel &acc, uint32_t shape, const TwoLevelShape &sh, float *vmax, hipStream_t s);
+// Largest |coordinate| of the shape's device vertices as they are now, reduced on the device
+// (4 bytes come back; synchronises s): what TwoLevelShape::vmax holds, without the vertices
+// passing through the host.
+int shape_abs_max(TwoLevelAccel &acc, const TwoLevelShape &sh, float *vmax, hipStream_t s);
 void free_two_level(TwoLevelAccel &acc);
 // BLAS box margins of an instance after its transform changed (uses its stored vmax)
 void refresh_instance_margins(DevInstance &d);

@@ -15,8 +15,10 @@
 //
 // The TLAS is rebuilt on the host from the instance world boxes (binned SAH
 // over a few instances is microseconds); an instance update recomputes that
-// instance's box on the GPU and rebuilds the TLAS, the BLASes never change
-// (the reference refits its IAS, ias_manager.cpp:116-151).
+// instance's box on the GPU and rebuilds the TLAS (the reference refits its IAS,
+// ias_manager.cpp:116-151).  A BLAS changes only when its shape's vertices are
+// replaced (update_shape_blas): records, boxes and shading records in place,
+// topology kept.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -510,10 +512,70 @@ bool world_entries(TwoLevelAccel &acc, const DevInstance &d, uint32_t id, uint32
     return true;
 }
 
+// Deformed mesh: the n object-space BLAS record slots of one shape (from recs, BLAS leaf
+// order) get the vertices the shape holds now.  The local id in a.w picks the triangle and
+// is kept with the other id words; hole slots are untouched.
+__global__ __launch_bounds__(kBlock) void k_blas_records(float4 *recs, uint32_t n, const float *P,
+                                                         const uint32_t *idx) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    float4 *r = recs + kRecF4 * (size_t)j;
+    const float4 a = r[0], b = r[1], c = r[2];
+    const uint32_t local = __float_as_uint(a.w);
+    if (local == kRecHole) return;
+    const uint32_t i0 = idx[3 * local], i1 = idx[3 * local + 1], i2 = idx[3 * local + 2];
+    r[0] = make_float4(P[3 * i0], P[3 * i0 + 1], P[3 * i0 + 2], a.w);
+    r[1] = make_float4(P[3 * i1], P[3 * i1 + 1], P[3 * i1 + 2], b.w);
+    r[2] = make_float4(P[3 * i2], P[3 * i2 + 1], P[3 * i2 + 2], c.w);
+}
+
+// max |x| over n floats into *out (float bits; non-negative floats order like their bits,
+// fmaxf drops NaN as the host loop at create does).  *out is cleared by the caller.
+__global__ __launch_bounds__(kBlock) void k_abs_max(const float *x, size_t n, uint32_t *out) {
+    float m = 0.f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        m = fmaxf(m, fabsf(x[i]));
+    for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
+    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
+}
+
 }  // namespace
 
 void refresh_instance_margins(DevInstance &d) {
     if (d.kind != PUPIL_SHAPE_SPHERE) instance_margin(d, d.vmax);
+}
+
+int update_shape_blas(TwoLevelAccel &acc, uint32_t shape, const TwoLevelShape &sh, float *vmax, hipStream_t s) {
+    if (shape >= acc.shape_slots.size()) return -1;
+    const uint32_t slots = acc.shape_slots[shape];
+    if (slots == 0) return 0;  // no instance uses the shape: it has no BLAS
+    hipLaunchKernelGGL(k_blas_records, dim3((slots + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                       acc.prims + kRecF4 * (size_t)acc.shape_rec_base[shape], slots, sh.positions, sh.indices);
+    if (!acc.shape_root_leaf[shape] && acc.shape_levels[shape].size() >= 2) {
+        if (!acc.d_objbox && hipMalloc((void **)&acc.d_objbox, sizeof(float) * 6 * (size_t)std::max(1u, acc.num_nodes4)) !=
+                                 hipSuccess)
+            return -1;
+        launch_refit_levels(acc.nodes4, acc.shape_levels[shape], acc.shape_node_base[shape], acc.prims, acc.d_objbox, s);
+    }
+    launch_refresh_attrs_shape(acc.attrs + kAttrStride * (size_t)acc.shape_attr_base[shape], sh.num_faces, sh.positions,
+                               sh.normals, sh.indices, s);
+    if (vmax && shape_abs_max(acc, sh, vmax, s) != 0) return -1;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int shape_abs_max(TwoLevelAccel &acc, const TwoLevelShape &sh, float *vmax, hipStream_t s) {
+    if (!acc.d_vmax && hipMalloc((void **)&acc.d_vmax, sizeof(uint32_t)) != hipSuccess) return -1;
+    const size_t nf = 3 * (size_t)sh.num_vertices;
+    uint32_t bits = 0;
+    if (hipMemsetAsync(acc.d_vmax, 0, sizeof(uint32_t), s) != hipSuccess) return -1;
+    const uint32_t g = (uint32_t)std::max<size_t>(1, std::min<size_t>(1024, (nf + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_abs_max, dim3(g), dim3(kBlock), 0, s, sh.positions, nf, acc.d_vmax);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(&bits, acc.d_vmax, sizeof(bits), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return -1;
+    std::memcpy(vmax, &bits, sizeof(bits));
+    return 0;
 }
 
 // World mode, RenderInstanceUpdate: the TLAS keeps its topology and its boxes are
@@ -897,11 +959,21 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
                      (unsigned long long)wnodes);
         to_object_mode();
     }
+    // per shape, for refits (world BLAS copies, update_shape_blas): level order, record slots, bases
+    acc.inst_shape = shape_of;
+    acc.shape_levels.assign(shapes.size(), {});
+    acc.shape_slots.assign(shapes.size(), 0u);
+    acc.shape_root_leaf.assign(shapes.size(), 0);
+    acc.shape_node_base = node_base;
+    acc.shape_rec_base = rec_base;
+    acc.shape_attr_base = prim_base;
+    for (size_t k = 0; k < shapes.size(); k++) {
+        acc.shape_levels[k] = blas[k].level_start;
+        acc.shape_slots[k] = used[k] && shapes[k].num_faces ? blas[k].num_records : 0u;
+        acc.shape_root_leaf[k] = (int)blas[k].root_link4 < 0 ? 1 : 0;
+    }
     if (acc.world) {  // world BLAS copies + sphere records appended to the world records
         acc.entries.assign(n, {});
-        acc.inst_shape = shape_of;
-        acc.shape_levels.assign(shapes.size(), {});
-        for (size_t k = 0; k < shapes.size(); k++) acc.shape_levels[k] = blas[k].level_start;
         // one leaf (2 slots: the record, then a hole) per sphere
         const float4 hole = make_float4(qfloat(kRecHole), qfloat(kRecHole), qfloat(kRecHole), qfloat(kRecHole));
         std::vector<float4> sph(2 * kRecF4 * spheres, hole);
@@ -943,7 +1015,7 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
 
 void free_two_level(TwoLevelAccel &acc) {
     void *p[] = {acc.nodes4, acc.prims, acc.attrs, acc.d_boxes, acc.d_list, acc.d_verts, acc.wprims, acc.d_faces,
-                 acc.wnodes, acc.d_wbox, acc.d_tlas_order};
+                 acc.wnodes, acc.d_wbox, acc.d_tlas_order, acc.d_objbox, acc.d_vmax};
     for (void *x : p)
         if (x) (void)hipFree(x);
     acc = TwoLevelAccel{};

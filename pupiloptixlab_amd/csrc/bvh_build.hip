@@ -1465,7 +1465,76 @@ __global__ void k_refit_level(Bvh4Node *nodes, uint32_t lo, uint32_t hi, const f
     }
 }
 
+// The object-space part of a shading record (k_attrs: p0 p1 p2, n0 n1 n2) from the shape's
+// vertex arrays as they are now; the id words r[0].w / r[1].w and the texcoords stay.
+__device__ __forceinline__ void write_attr_geometry(float4 *r, const float *P, const float *N, const uint32_t *idx,
+                                                    uint32_t local) {
+    const uint32_t i0 = idx[3 * local], i1 = idx[3 * local + 1], i2 = idx[3 * local + 2];
+    float nn[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (N) {
+        const uint32_t id[3] = {i0, i1, i2};
+        for (int v = 0; v < 3; v++)
+            for (int c = 0; c < 3; c++) nn[3 * v + c] = N[3 * id[v] + c];
+    }
+    r[0] = make_float4(P[3 * i0], P[3 * i0 + 1], P[3 * i0 + 2], r[0].w);
+    r[1] = make_float4(P[3 * i1], P[3 * i1 + 1], P[3 * i1 + 2], r[1].w);
+    r[2] = make_float4(P[3 * i2], P[3 * i2 + 1], P[3 * i2 + 2], nn[0]);
+    r[3] = make_float4(nn[1], nn[2], nn[3], nn[4]);
+    r[4] = make_float4(nn[5], nn[6], nn[7], nn[8]);
+}
+
+// Deformed meshes, flattened BVH: the shading record of every record slot whose instance is
+// flagged in `moved` is rewritten from the instance's vertex arrays, exactly as k_attrs wrote
+// it.  The slot's primitive and instance are read from the traversal record beside it (the
+// same words as the shading record's r[0].w / r[1].w; a hole slot has no shading record).
+__global__ void k_refresh_attrs(BvhBuildInput in, uint32_t n, const float4 *recs_base, float4 *attrs,
+                                const uint8_t *moved) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const float4 *recs = recs_base + (size_t)kRecF4 * r;
+    const uint32_t id = __float_as_uint(recs[1].w);
+    if (id == kRecHole || !moved[id]) return;
+    const uint32_t w0 = __float_as_uint(recs[0].w);
+    if (w0 & kPrimSphereBit) return;
+    const DevInstance &inst = in.instances[id];
+    write_attr_geometry(attrs + (size_t)kAttrStride * r, inst.positions, inst.normals, inst.indices,
+                        w0 - inst.prim_offset);
+}
+
+// ... a two-level BLAS: the n shading records of one shape, in the mesh's own primitive order
+__global__ void k_refresh_attrs_shape(uint32_t n, float4 *attrs, const float *P, const float *N,
+                                      const uint32_t *idx) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    float4 *r = attrs + (size_t)kAttrStride * p;
+    write_attr_geometry(r, P, N, idx, __float_as_uint(r[0].w));
+}
+
 }  // namespace
+
+void launch_refit_levels(Bvh4Node *nodes, const std::vector<uint32_t> &level_start, uint32_t node_base,
+                         const float4 *recs, float *nbox, hipStream_t s) {
+    for (size_t L = level_start.size() < 2 ? 0 : level_start.size() - 1; L-- > 0;) {
+        const uint32_t lo = node_base + level_start[L], hi = node_base + level_start[L + 1];
+        if (hi <= lo) continue;
+        const uint32_t g = std::max(1u, std::min(4096u, (hi - lo + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL(k_refit_level, dim3(g), dim3(kBlock), 0, s, nodes, lo, hi, recs, nbox);
+    }
+}
+
+void launch_refresh_attrs(const BvhBuildInput &in, const BvhBuildOutput &out, const uint8_t *moved, hipStream_t s) {
+    const uint32_t n = out.num_records;
+    if (n && out.attrs)
+        hipLaunchKernelGGL(k_refresh_attrs, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, in, n, out.prims,
+                           out.attrs, moved);
+}
+
+void launch_refresh_attrs_shape(float4 *attrs, uint32_t n, const float *positions, const float *normals,
+                                const uint32_t *indices, hipStream_t s) {
+    if (n)
+        hipLaunchKernelGGL(k_refresh_attrs_shape, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, attrs,
+                           positions, normals, indices);
+}
 
 int refit_bvh4(const BvhBuildInput &in, BvhBuildOutput &out, const uint8_t *moved, float *nbox, hipStream_t s,
                double *ms, bool records_only) {

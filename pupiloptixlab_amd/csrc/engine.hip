@@ -225,6 +225,18 @@ struct pupil_pt {
     uint8_t *d_moved = nullptr;
     std::vector<uint8_t> h_moved;
     float *refit_box = nullptr;
+    // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
+    // (those the instances point at), the shape of each instance, the two-level build's input
+    // (PUPIL_VERTS_REBUILD) and the event that orders a caller's stream before the copy
+    struct ShapeDev {
+        uint32_t kind = PUPIL_SHAPE_MESH, num_vertices = 0, num_faces = 0;
+        float *pos = nullptr, *nrm = nullptr, *tex = nullptr;
+        uint32_t *idx = nullptr;
+    };
+    std::vector<ShapeDev> shapes;
+    std::vector<uint32_t> inst_shape;
+    std::vector<TwoLevelShape> tl_shapes;
+    hipEvent_t ev_verts = nullptr;
     // flow pass scratch (pupil_pt_motion_vectors), sized on first use: the ray list (2 float4
     // per pixel), the hit list, the previous instance transforms and their host staging copy;
     // ev_flow: the upload of that copy has run (the next call may overwrite it)
@@ -281,6 +293,7 @@ struct pupil_pt {
         if (ev_end) (void)hipEventDestroy(ev_end);
         if (ev_sync) (void)hipEventDestroy(ev_sync);
         if (ev_flow) (void)hipEventDestroy(ev_flow);
+        if (ev_verts) (void)hipEventDestroy(ev_verts);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
 };
@@ -942,6 +955,71 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
     return PUPIL_OK;
 }
 
+// The flattened BVH after the instances in `changed` moved, were hidden or shown, or had their
+// shape's vertices replaced (attrs: their shading records are rewritten too): one refit in
+// place, or a rebuild with the masks applied after it (refit = false, PUPIL_FLAT_UPDATE=rebuild,
+// a tree without a level order).  The instance table on the device is already up to date.
+int flat_update(pupil_pt *pt, const std::vector<uint32_t> &changed, bool refit, bool attrs) {
+    BvhBuildInput bin{pt->num_prims, pt->d_prim_inst, pt->d_insts, pt->d_mats};
+    // the flags of the instances whose records are rewritten, and the node-box scratch
+    const auto refit_flags = [&](bool hidden_ones) -> int {
+        if (!pt->d_moved) HIP_TRY(pt->alloc(&pt->d_moved, pt->h_insts.size()));
+        if (!pt->refit_box) HIP_TRY(pt->alloc(&pt->refit_box, 6 * (size_t)std::max(1u, pt->bvh.num_nodes4)));
+        pt->h_moved.assign(pt->h_insts.size(), 0);
+        if (hidden_ones) {
+            for (size_t i = 0; i < pt->h_insts.size(); i++) pt->h_moved[i] = pt->h_insts[i].hidden ? 1 : 0;
+        } else {
+            for (uint32_t id : changed) pt->h_moved[id] = 1;
+        }
+        HIP_TRY(hipMemcpyAsync(pt->d_moved, pt->h_moved.data(), pt->h_moved.size(), hipMemcpyHostToDevice, pt->own_stream));
+        return PUPIL_OK;
+    };
+    // refit in place (PUPIL_FLAT_UPDATE=rebuild: full rebuild)
+    const char *fu = std::getenv("PUPIL_FLAT_UPDATE");
+    if (refit && !(fu && std::strcmp(fu, "rebuild") == 0)) {
+        if (const int rc = refit_flags(false)) return rc;
+        double rms = 0.0;
+        if (refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &rms) == 0) {
+            // deformed meshes: the shading records follow (refresh_node_bound synchronises the stream)
+            if (attrs) launch_refresh_attrs(bin, pt->bvh, pt->d_moved, pt->own_stream);
+            pt->totals.build_ms = rms;
+            return refresh_node_bound(pt);
+        }
+    }
+    BvhBuildOutput nb{};
+    double ms = 0.0;
+    const int brc = build_bvh_bounded(bin, nb, pt->leaf_size, pt->own_stream, &ms, 0);
+    if (brc != 0) {
+        free_lbvh(nb);
+        return fail(brc == -3 ? PUPIL_ERR_UNSUPPORTED : PUPIL_ERR_HIP,
+                    brc == -3 ? "BVH deeper than the traversal stacks hold" : "LBVH rebuild failed");
+    }
+    free_lbvh(pt->bvh);
+    pt->bvh = nb;
+    if (pt->refit_box) {  // sized for the old tree
+        pt->release(pt->refit_box);
+        pt->refit_box = nullptr;
+    }
+    pt->sc.prims = nb.prims;
+    pt->sc.attrs = nb.attrs;
+    pt->sc.nodes4 = nb.nodes4;
+    pt->sc.root_link4 = nb.root_link4;
+    pt->totals.bvh_nodes = nb.num_nodes4;
+    pt->totals.bvh_depth = nb.depth4;
+    bool any_hidden = false;
+    for (const DevInstance &d : pt->h_insts) any_hidden = any_hidden || d.hidden != 0u;
+    if (any_hidden) {  // the build covered every instance: the masks go on like a refit's
+        if (const int rc = refit_flags(true)) return rc;
+        double hms = 0.0;
+        const int hrc = refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &hms, true);
+        if (hrc == -1) return fail(PUPIL_ERR_UNSUPPORTED, "hidden instances need the BVH4 level order");
+        if (hrc != 0) return fail(PUPIL_ERR_HIP, "applying the visibility masks failed");
+        ms += hms;
+    }
+    pt->totals.build_ms = ms;
+    return refresh_node_bound(pt);
+}
+
 }  // namespace
 
 extern "C" {
@@ -984,13 +1062,13 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     pt->max_depth = scene->max_depth ? scene->max_depth : 1;
 
     // shapes
-    struct ShapeDev {
-        float *pos = nullptr, *nrm = nullptr, *tex = nullptr;
-        uint32_t *idx = nullptr;
-    };
-    std::vector<ShapeDev> shapes(scene->num_shapes);
+    std::vector<pupil_pt::ShapeDev> &shapes = pt->shapes;
+    shapes.assign(scene->num_shapes, pupil_pt::ShapeDev{});
     for (uint32_t s = 0; s < scene->num_shapes; s++) {
         const pupil_shape &sh = scene->shapes[s];
+        shapes[s].kind = sh.kind;
+        shapes[s].num_vertices = sh.num_vertices;
+        shapes[s].num_faces = sh.num_faces;
         if (sh.kind == PUPIL_SHAPE_MESH) {
             if (!sh.positions || !sh.indices || sh.num_faces == 0)
                 return cleanup(fail(PUPIL_ERR_INVALID, "mesh without positions/indices"));
@@ -1115,6 +1193,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
             const pupil_shape &sh = scene->shapes[inst_shape[i]];
             flat_prims += sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
         }
+        pt->inst_shape = inst_shape;
         // leaf links hold 28-bit record slots, up to two per primitive (pt_scene.h kRecF4)
         pt->two_level = flat_prims >= (1ull << 27);
         if (const char *a = std::getenv("PUPIL_ACCEL")) {
@@ -1140,6 +1219,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
                 for (size_t v = 0; v < 3 * (size_t)sh.num_vertices; v++) vmax = std::max(vmax, std::fabs(sh.positions[v]));
                 t.vmax = vmax;
             }
+            pt->tl_shapes = tls;
             const int trc = build_two_level(tls, inst_shape, insts, d_insts, d_mats, pt->leaf_size, pt->own_stream, pt->tl);
             if (trc == -3) return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold"));
             if (trc == -4) return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "two-level record slots beyond the 28-bit leaf links"));
@@ -1225,7 +1305,8 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
         hipMemset(pt->ray_cum, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
         return cleanup(fail(PUPIL_ERR_HIP, "workspace clear failed"));
     if (hipEventCreate(&pt->ev_begin) != hipSuccess || hipEventCreate(&pt->ev_end) != hipSuccess ||
-        hipEventCreateWithFlags(&pt->ev_sync, hipEventDisableTiming) != hipSuccess)
+        hipEventCreateWithFlags(&pt->ev_sync, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&pt->ev_verts, hipEventDisableTiming) != hipSuccess)
         return cleanup(fail(PUPIL_ERR_HIP, "event creation failed"));
     if (refresh_node_bound(pt) != PUPIL_OK) return cleanup(PUPIL_ERR_HIP);
     pt->totals.bvh_nodes = pt->two_level ? two_level_nodes(pt->tl) : pt->bvh.num_nodes4;
@@ -1313,62 +1394,109 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
         pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return PUPIL_OK;
     }
-    BvhBuildInput bin{pt->num_prims, pt->d_prim_inst, pt->d_insts, pt->d_mats};
-    // the flags of the instances whose records are rewritten, and the node-box scratch
-    const auto refit_flags = [&](bool hidden_ones) -> int {
-        if (!pt->d_moved) HIP_TRY(pt->alloc(&pt->d_moved, pt->h_insts.size()));
-        if (!pt->refit_box) HIP_TRY(pt->alloc(&pt->refit_box, 6 * (size_t)std::max(1u, pt->bvh.num_nodes4)));
-        pt->h_moved.assign(pt->h_insts.size(), 0);
-        if (hidden_ones) {
-            for (size_t i = 0; i < pt->h_insts.size(); i++) pt->h_moved[i] = pt->h_insts[i].hidden ? 1 : 0;
-        } else {
-            for (uint32_t id : changed) pt->h_moved[id] = 1;
+    return flat_update(pt, changed, true, false);
+}
+
+// Geometry-AS update (OPTIX_BUILD_OPERATION_UPDATE next to the instance-AS update above): the
+// vertices of one mesh shape are replaced and every structure derived from them follows in
+// place.  Flattened BVH: the shape's instances are flagged moved, refit_bvh4 rewrites their world
+// records (a hidden instance's stay NaN) and refits every node, launch_refresh_attrs rewrites
+// their shading records.  Two-level: update_shape_blas rewrites the object-space BLAS records,
+// refits the BLAS and refreshes its shading records, the instances get the new vmax and margins,
+// and rebuild_tlas regenerates their world boxes, world records and world BLAS copies and refits
+// (world mode) or rebuilds (object mode) the TLAS.  PUPIL_VERTS_REBUILD builds everything anew
+// with the create-time builders and puts the masks back on.
+int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *positions, const float *normals,
+                                   uint32_t flags, void *hip_stream) {
+    if (!pt || !positions) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "shape index out of range");
+    const pupil_pt::ShapeDev &sd = pt->shapes[shape];
+    if (sd.kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
+    if (normals && !sd.nrm) return fail(PUPIL_ERR_INVALID, "the shape was created without normals");
+    if (flags & ~(PUPIL_VERTS_DEVICE | PUPIL_VERTS_REBUILD)) return fail(PUPIL_ERR_INVALID, "unknown flags");
+    const bool device = (flags & PUPIL_VERTS_DEVICE) != 0u, rebuild = (flags & PUPIL_VERTS_REBUILD) != 0u;
+    std::vector<uint32_t> changed;
+    bool emissive = false;
+    for (uint32_t i = 0; i < (uint32_t)pt->inst_shape.size(); i++)
+        if (pt->inst_shape[i] == shape && pt->h_insts[i].kind == PUPIL_SHAPE_MESH) {
+            changed.push_back(i);
+            emissive = emissive || pt->h_insts[i].emitter_offset >= 0;
         }
-        HIP_TRY(hipMemcpyAsync(pt->d_moved, pt->h_moved.data(), pt->h_moved.size(), hipMemcpyHostToDevice, pt->own_stream));
+    if (device && emissive)
+        return fail(PUPIL_ERR_UNSUPPORTED, "device vertices of an emissive shape: the emitter table needs the host path");
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(order_after_renders(pt));  // no render may still read the old vertices
+    pt->pipe_valid = false;             // frames in flight were traced against the old geometry
+    const size_t bytes = sizeof(float) * 3 * (size_t)sd.num_vertices;
+    if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
+        HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
+        HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    }
+    const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIP_TRY(hipMemcpyAsync(sd.pos, positions, bytes, kind, pt->own_stream));
+    if (normals) HIP_TRY(hipMemcpyAsync(sd.nrm, normals, bytes, kind, pt->own_stream));
+    // From here the shape's arrays hold the new vertices.  The refit counter ticks only once the
+    // structure has followed; after a failure below the structure still bounds the OLD vertices,
+    // and the engine must not render until an update of this shape succeeds (the header says so).
+    if (changed.empty()) {  // no instance shows the shape: only its arrays change
+        HIP_TRY(hipStreamSynchronize(pt->own_stream));
+        pt->refits++;
         return PUPIL_OK;
-    };
-    // refit in place (PUPIL_FLAT_UPDATE=rebuild: full rebuild)
-    const char *fu = std::getenv("PUPIL_FLAT_UPDATE");
-    if (!(fu && std::strcmp(fu, "rebuild") == 0)) {
-        if (const int rc = refit_flags(false)) return rc;
-        double rms = 0.0;
-        if (refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &rms) == 0) {
-            pt->totals.build_ms = rms;
-            return refresh_node_bound(pt);
+    }
+    if (!pt->two_level) {
+        const int rc = flat_update(pt, changed, !rebuild, true);
+        if (rc == PUPIL_OK) {
+            pt->refits++;
+            pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
+        return rc;
     }
-    BvhBuildOutput nb{};
-    double ms = 0.0;
-    const int brc = build_bvh_bounded(bin, nb, pt->leaf_size, pt->own_stream, &ms, 0);
-    if (brc != 0) {
-        free_lbvh(nb);
-        return fail(brc == -3 ? PUPIL_ERR_UNSUPPORTED : PUPIL_ERR_HIP,
-                    brc == -3 ? "BVH deeper than the traversal stacks hold" : "LBVH rebuild failed");
+    TwoLevelShape &ts = pt->tl_shapes[shape];
+    if (rebuild) {
+        // vmax as at create, from the engine's own device copy by a device reduction (the same
+        // maximum the host loop at create finds): host and device vertices take one path, and
+        // device vertices never come back to the host
+        float vmax = 0.f;
+        if (shape_abs_max(pt->tl, ts, &vmax, pt->own_stream) != 0) return fail(PUPIL_ERR_HIP, "vertex reduction failed");
+        ts.vmax = vmax;
+        std::vector<DevInstance> insts = pt->h_insts;  // build_two_level refills the two-level fields
+        TwoLevelAccel ntl{};
+        const int trc = build_two_level(pt->tl_shapes, pt->inst_shape, insts, pt->d_insts, pt->d_mats, pt->leaf_size,
+                                        pt->own_stream, ntl);
+        if (trc == -3) return fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold");
+        if (trc != 0) return fail(PUPIL_ERR_HIP, "two-level acceleration rebuild failed");
+        free_two_level(pt->tl);
+        pt->tl = ntl;
+        pt->h_insts = insts;
+        DeviceScene &sc = pt->sc;
+        sc.tl_world = pt->tl.world ? 1u : 0u;
+        sc.nodes4 = pt->tl.world ? pt->tl.wnodes : pt->tl.nodes4;
+        sc.prims = pt->tl.world ? pt->tl.wprims : pt->tl.prims;
+        sc.wprims = pt->tl.wprims;
+        sc.attrs = pt->tl.attrs;
+    } else {
+        float vmax = 0.f;
+        if (update_shape_blas(pt->tl, shape, ts, &vmax, pt->own_stream) != 0)
+            return fail(PUPIL_ERR_HIP, "BLAS refit failed");
+        ts.vmax = vmax;
+        for (uint32_t id : changed) {
+            pt->h_insts[id].vmax = vmax;
+            refresh_instance_margins(pt->h_insts[id]);
+        }
+        const char *um = std::getenv("PUPIL_TL_UPDATE");
+        const bool refit = !(um && std::strcmp(um, "rebuild") == 0);
+        const int trc = rebuild_tlas(pt->tl, pt->h_insts, pt->d_insts, changed, pt->own_stream, refit);
+        if (trc == -3) return fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold");
+        if (trc != 0) return fail(PUPIL_ERR_HIP, "TLAS rebuild failed");
     }
-    free_lbvh(pt->bvh);
-    pt->bvh = nb;
-    if (pt->refit_box) {  // sized for the old tree
-        pt->release(pt->refit_box);
-        pt->refit_box = nullptr;
-    }
-    pt->sc.prims = nb.prims;
-    pt->sc.attrs = nb.attrs;
-    pt->sc.nodes4 = nb.nodes4;
-    pt->sc.root_link4 = nb.root_link4;
-    pt->totals.bvh_nodes = nb.num_nodes4;
-    pt->totals.bvh_depth = nb.depth4;
-    bool any_hidden = false;
-    for (const DevInstance &d : pt->h_insts) any_hidden = any_hidden || d.hidden != 0u;
-    if (any_hidden) {  // the build covered every instance: the masks go on like a refit's
-        if (const int rc = refit_flags(true)) return rc;
-        double hms = 0.0;
-        const int hrc = refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &hms, true);
-        if (hrc == -1) return fail(PUPIL_ERR_UNSUPPORTED, "hidden instances need the BVH4 level order");
-        if (hrc != 0) return fail(PUPIL_ERR_HIP, "applying the visibility masks failed");
-        ms += hms;
-    }
-    pt->totals.build_ms = ms;
-    return refresh_node_bound(pt);
+    pt->sc.root_link4 = pt->tl.root_link4;
+    if (const int rc = refresh_node_bound(pt)) return rc;
+    pt->totals.bvh_nodes = two_level_nodes(pt->tl);
+    pt->totals.bvh_depth = pt->tl.tlas_depth + pt->tl.blas_depth;
+    pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->refits++;
+    return PUPIL_OK;
 }
 
 int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, const float *to_world,

@@ -1083,6 +1083,21 @@ int pupil_world_get_instance_visibility(pupil_world *w, uint32_t instance, uint3
     return PUPIL_OK;
 }
 
+int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *positions, const float *normals) {
+    if (!w || !positions) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    if (shape >= w->w.scene.shapes.size()) return Pupil::werr(PUPIL_ERR_INVALID, "shape out of range");
+    Pupil::resource::Shape &s = w->w.scene.shapes[shape];
+    if (s.kind != PUPIL_SHAPE_MESH || !s.mesh) return Pupil::werr(PUPIL_ERR_INVALID, "shape is not a mesh");
+    if (normals && s.mesh->normals.empty()) return Pupil::werr(PUPIL_ERR_INVALID, "the mesh has no normals");
+    // a mesh another shape shares keeps its vertices there
+    if (s.mesh.use_count() > 1) s.mesh = std::make_shared<Pupil::resource::Mesh>(*s.mesh);
+    // World::Build reads the mesh on every pupil_world_get_desc: vertices, and the area
+    // emitters of emissive instances with their areas and select probabilities
+    std::copy(positions, positions + s.mesh->positions.size(), s.mesh->positions.begin());
+    if (normals) std::copy(normals, normals + s.mesh->normals.size(), s.mesh->normals.begin());
+    return PUPIL_OK;
+}
+
 int pupil_world_add_const_env(pupil_world *w, const float radiance[3]) {
     if (!w || !radiance) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
     Pupil::resource::SceneEmitter e;

@@ -280,6 +280,18 @@ void free_lbvh(BvhBuildOutput &out);
 // only its records are rewritten (applying the masks to a fresh build).
 int refit_bvh4(const BvhBuildInput &in, BvhBuildOutput &out, const uint8_t *moved, float *nbox, hipStream_t s,
                double *ms, bool records_only = false);
+// Deformed meshes (pupil_pt_update_shape_vertices).  launch_refit_levels: the bottom-up box
+// refit of refit_bvh4 over one tree inside a larger node array -- level_start is relative to
+// node_base, the links and nbox (6 floats per node of the array) are absolute.
+// launch_refresh_attrs: the shading records of the instances flagged in `moved` (flattened
+// BVH) get the object-space positions and normals their shapes hold now;
+// launch_refresh_attrs_shape: the same for the n records of one two-level BLAS shape.  The id
+// words and texcoords of a record stay.
+void launch_refit_levels(Bvh4Node *nodes, const std::vector<uint32_t> &level_start, uint32_t node_base,
+                         const float4 *recs, float *nbox, hipStream_t s);
+void launch_refresh_attrs(const BvhBuildInput &in, const BvhBuildOutput &out, const uint8_t *moved, hipStream_t s);
+void launch_refresh_attrs_shape(float4 *attrs, uint32_t n, const float *positions, const float *normals,
+                                const uint32_t *indices, hipStream_t s);
 // BVH4 over n >= 2 boxes (6 floats each: lo xyz, hi xyz) with the flattened build's PLOC +
 // SAH collapse, one box per leaf: nodes (root 0, parents first) and, for leaf link
 // make_leaf(p, 1), the box order[p]; depth = 4-wide levels

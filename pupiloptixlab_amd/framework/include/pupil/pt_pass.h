@@ -30,6 +30,11 @@ public:
     void SetMaxDepth(int depth) noexcept;
     void SetAccumulate(bool on) noexcept;
     bool Stats(pupil_pt_counters &out) noexcept;
+    // Deformed mesh: the next OnRun hands the vertices the world holds for `shape` to the engine
+    // (pupil_pt_update_shape_vertices, then the emitter table if an instance of it emits) and
+    // restarts accumulation.  World::SetMeshVertices calls this through its event; several
+    // updates of a shape before one OnRun cost one refit.
+    void UpdateShape(uint32_t shape) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in
@@ -55,6 +60,7 @@ private:
     // reference's handler only sets m_dirty, pt_pass.cpp:216-218; OnRun refits once)
     std::mutex m_pending_mutex;
     std::vector<uint32_t> m_pending;
+    std::vector<uint32_t> m_pending_shapes;  // shapes deformed since the last OnRun (same mutex)
     // what ComputeMotionVectors compares against: the cameras of the last two OnRuns, the
     // instance transforms now in the engine and those before the last OnRun's update
     float m_cam[2][2][16] = {};  // [0] last OnRun, [1] the one before; [.][0] sample_to_camera, [.][1] camera_to_world

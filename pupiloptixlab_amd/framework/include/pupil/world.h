@@ -47,6 +47,9 @@ class World;
 struct InstanceUpdate {
     World *world;
     uint32_t instance;  // index into Desc().instances
+    // World::SetMeshVertices: the mesh shape (index into Desc().shapes) whose vertices changed;
+    // `instance` is unused then
+    uint32_t shape = 0xFFFFFFFFu;
 };
 
 class World {
@@ -72,6 +75,11 @@ public:
     // emitter stays in the emitter table, as in the reference (world/world.cpp:45-54).
     bool SetInstanceVisibility(uint32_t instance, uint32_t mask) noexcept;
     uint32_t InstanceVisibility(uint32_t instance) noexcept;
+    // Deformable meshes: new vertices of mesh shape `shape` (3 floats per vertex, the count the
+    // shape has; normals null = kept), copied into the world.  Refreshes Desc() (vertices, the
+    // area emitters of emissive instances) and fires EWorldEvent::RenderInstanceUpdate with
+    // InstanceUpdate::shape set; the pass refits once at the top of its next OnRun.
+    bool SetMeshVertices(uint32_t shape, const float *positions, const float *normals = nullptr) noexcept;
 
     pupil_world *handle() noexcept { return m_world; }
     // Flattened scene for pupil_pt_create (valid until the world changes); a thread

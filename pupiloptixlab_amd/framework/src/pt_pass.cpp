@@ -28,10 +28,11 @@ void PTPass::OnRun() noexcept {
     m_instances_moved = false;
     if (m_dirty) {
         m_dirty = false;  // an event after this point marks the next frame dirty again
-        std::vector<uint32_t> moved;
+        std::vector<uint32_t> moved, deformed;
         {
             std::scoped_lock lock(m_pending_mutex);
             moved.swap(m_pending);
+            deformed.swap(m_pending_shapes);
         }
         float s2c[16], c2w[16];
         m_world->camera->Snapshot(s2c, c2w);
@@ -40,28 +41,47 @@ void PTPass::OnRun() noexcept {
         std::memcpy(m_cam[0][1], c2w, sizeof(c2w));
         if (!m_have_cam) std::memcpy(m_cam[1], m_cam[0], sizeof(m_cam[0]));  // first frame: no motion
         m_have_cam = true;
-        if (!moved.empty()) {  // m_world->GetIASHandle(2, true) + the emitter group (pt_pass.cpp:46-47)
+        if (!moved.empty() || !deformed.empty()) {
             std::scoped_lock lock(m_world->Mutex());
             const pupil_scene_desc &d = m_world->Desc();
-            std::vector<float> tw(12 * moved.size()), to(12 * moved.size());
-            std::vector<uint32_t> vis(moved.size());  // ias_manager.cpp:187-197: transform and mask together
-            bool emissive = false;
-            for (size_t k = 0; k < moved.size(); k++) {
-                const pupil_instance &ins = d.instances[moved[k]];
-                vis[k] = m_world->InstanceVisibility(moved[k]);
-                std::memcpy(&tw[12 * k], ins.to_world, sizeof(ins.to_world));
-                std::memcpy(&to[12 * k], ins.to_object, sizeof(ins.to_object));
-                emissive = emissive || ins.emitter_offset >= 0;
+            // the desc's emitter table describes the whole scene as it is now: it goes up ONCE, after
+            // every geometry and instance update of this OnRun that changed an emitter and succeeded
+            bool emitters = false;
+            // deformed shapes first (one geometry refit each), so that the instance refit below and the
+            // emitter table meet the vertices they were made from
+            for (uint32_t shape : deformed) {
+                if (shape >= d.num_shapes) continue;
+                const pupil_shape &sh = d.shapes[shape];
+                if (pupil_pt_update_shape_vertices(m_engine, shape, sh.positions, sh.normals, 0u, nullptr) != PUPIL_OK) {
+                    Log("%s: shape update failed: %s", name.c_str(), pupil_last_error());
+                    continue;  // the other shapes and their emitters still follow
+                }
+                for (uint32_t i = 0; i < d.num_instances; i++)
+                    emitters = emitters || (d.instances[i].shape == shape && d.instances[i].emitter_offset >= 0);
             }
-            m_prev_to_world = m_to_world;
-            for (size_t k = 0; k < moved.size(); k++)
-                if (12 * (size_t)moved[k] + 12 <= m_to_world.size())
-                    std::memcpy(&m_to_world[12 * (size_t)moved[k]], &tw[12 * k], 12 * sizeof(float));
-            m_instances_moved = true;
-            if (pupil_pt_update_instances_masked(m_engine, (uint32_t)moved.size(), moved.data(), tw.data(), to.data(),
-                                                 vis.data()) != PUPIL_OK)
-                Log("%s: instance update failed: %s", name.c_str(), pupil_last_error());
-            else if (emissive && pupil_pt_update_emitters(m_engine, &d) != PUPIL_OK)
+            if (!moved.empty()) {  // m_world->GetIASHandle(2, true) + the emitter group (pt_pass.cpp:46-47)
+                std::vector<float> tw(12 * moved.size()), to(12 * moved.size());
+                std::vector<uint32_t> vis(moved.size());  // ias_manager.cpp:187-197: transform and mask together
+                bool emissive = false;
+                for (size_t k = 0; k < moved.size(); k++) {
+                    const pupil_instance &ins = d.instances[moved[k]];
+                    vis[k] = m_world->InstanceVisibility(moved[k]);
+                    std::memcpy(&tw[12 * k], ins.to_world, sizeof(ins.to_world));
+                    std::memcpy(&to[12 * k], ins.to_object, sizeof(ins.to_object));
+                    emissive = emissive || ins.emitter_offset >= 0;
+                }
+                m_prev_to_world = m_to_world;
+                for (size_t k = 0; k < moved.size(); k++)
+                    if (12 * (size_t)moved[k] + 12 <= m_to_world.size())
+                        std::memcpy(&m_to_world[12 * (size_t)moved[k]], &tw[12 * k], 12 * sizeof(float));
+                m_instances_moved = true;
+                if (pupil_pt_update_instances_masked(m_engine, (uint32_t)moved.size(), moved.data(), tw.data(), to.data(),
+                                                     vis.data()) != PUPIL_OK)
+                    Log("%s: instance update failed: %s", name.c_str(), pupil_last_error());
+                else
+                    emitters = emitters || emissive;
+            }
+            if (emitters && pupil_pt_update_emitters(m_engine, &d) != PUPIL_OK)
                 Log("%s: emitter update failed: %s", name.c_str(), pupil_last_error());
         }
         m_frame_max_depth = (uint32_t)m_max_depth;
@@ -99,6 +119,7 @@ void PTPass::SetScene(world::World *world) noexcept {
     {
         std::scoped_lock lock(m_pending_mutex);  // moves of the previous world
         m_pending.clear();
+        m_pending_shapes.clear();
     }
     if (m_engine) {
         pupil_pt_destroy(m_engine);
@@ -209,6 +230,15 @@ void PTPass::SetAccumulate(bool on) noexcept {
     }
 }
 
+void PTPass::UpdateShape(uint32_t shape) noexcept {
+    {
+        std::scoped_lock lock(m_pending_mutex);
+        if (std::find(m_pending_shapes.begin(), m_pending_shapes.end(), shape) == m_pending_shapes.end())
+            m_pending_shapes.push_back(shape);
+    }
+    m_dirty = true;
+}
+
 bool PTPass::Stats(pupil_pt_counters &out) noexcept { return m_engine && pupil_pt_stats(m_engine, &out) == PUPIL_OK; }
 
 void PTPass::BindingEventCallback() noexcept {
@@ -217,6 +247,10 @@ void PTPass::BindingEventCallback() noexcept {
         // only recorded: the next OnRun refits once for every instance moved since the last
         // (ias_manager.cpp:116-151, world.cpp:45-54) and restarts accumulation
         const auto *u = static_cast<const world::InstanceUpdate *>(p);
+        if (u && u->world == m_world && u->shape != 0xFFFFFFFFu) {
+            UpdateShape(u->shape);
+            return;
+        }
         if (u && u->world == m_world) {
             std::scoped_lock lock(m_pending_mutex);
             if (std::find(m_pending.begin(), m_pending.end(), u->instance) == m_pending.end())

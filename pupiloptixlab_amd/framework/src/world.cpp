@@ -92,6 +92,23 @@ bool World::SetInstanceVisibility(uint32_t instance, uint32_t mask) noexcept {
     return true;
 }
 
+bool World::SetMeshVertices(uint32_t shape, const float *positions, const float *normals) noexcept {
+    {
+        std::scoped_lock lock(m_mutex);
+        if (!m_world || pupil_world_set_mesh_vertices(m_world, shape, positions, normals) != PUPIL_OK) {
+            Log("mesh vertex update failed: %s", pupil_last_error());
+            return false;
+        }
+        if (pupil_world_get_desc(m_world, &m_desc) != PUPIL_OK) {
+            Log("scene description failed: %s", pupil_last_error());
+            return false;
+        }
+    }
+    InstanceUpdate u{this, 0u, shape};
+    EventDispatcher<EWorldEvent::RenderInstanceUpdate>(&u);
+    return true;
+}
+
 // the caller holds Mutex() where another thread may edit the world
 uint32_t World::InstanceVisibility(uint32_t instance) noexcept {
     uint32_t mask = 1u;

@@ -103,6 +103,7 @@ class PTPass(Pass):
         self.dirty = True
         self.tile = (32, 0, 1)  # tile_size, rank, world
         self._world = None  # the World the scene came from: its sensor is re-read when dirty
+        self._shape_verts = []  # vertices of each shape of the scene in the engine (update_shape_device)
         self._pending = {}  # RenderInstanceUpdate events since the last render: id(world) -> (world, instances)
         # what motion_vectors() compares against: the camera in the engine and those of the last
         # two renders as (sample_to_camera, camera_to_world), the instance transforms now in the
@@ -161,6 +162,50 @@ class PTPass(Pass):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
 
+    def update_shape(self, world, shape: int, rebuild: bool = False):
+        """Deformed mesh applied now: the vertices `world` holds for `shape` (World.set_mesh_vertices)
+        go into the engine with ONE refit over every instance of the shape
+        (pupil_pt_update_shape_vertices; rebuild: PUPIL_VERTS_REBUILD), then the emitter table if
+        an instance of the shape emits; restarts accumulation."""
+        desc = world.desc()
+        sh = desc.shapes[int(shape)] if 0 <= int(shape) < desc.num_shapes else None
+        check(self._lib.pupil_pt_update_shape_vertices(
+            self._pt, int(shape), C.cast(sh.positions, C.c_void_p) if sh is not None else None,
+            C.cast(sh.normals, C.c_void_p) if sh is not None and sh.normals else None,
+            abi.VERTS_REBUILD if rebuild else 0, None))
+        if any(desc.instances[i].shape == int(shape) and desc.instances[i].emitter_offset >= 0
+               for i in range(desc.num_instances)):
+            check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
+        self.dirty = True
+
+    def update_shape_device(self, shape: int, positions, normals=None, rebuild: bool = False, stream=None):
+        """The same from device tensors (float32, contiguous, 3 per vertex, on the pass's device):
+        the copy into the engine's arrays is ordered after the work enqueued so far on `stream`
+        (default: the current stream) and never passes through the host.  A shape with an
+        emissive instance raises PUPIL_ERR_UNSUPPORTED: use update_shape."""
+        torch = self._torch
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        if not 0 <= int(shape) < len(self._shape_verts):
+            raise abi.PupilError(abi.ERR_INVALID, "shape index out of range")
+        if positions is None:
+            raise abi.PupilError(abi.ERR_INVALID, "null argument")
+        for t in (positions, normals):
+            if t is None:
+                continue
+            if t.numel() != 3 * self._shape_verts[int(shape)]:
+                raise ValueError(f"shape {shape} has {self._shape_verts[int(shape)]} vertices")
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("update_shape_device needs contiguous float32 device tensors")
+            if t.device.index != self.device_index:  # the copy runs device to device on the engine's GPU
+                raise ValueError(f"update_shape_device needs tensors on {self.device}, got {t.device}")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        flags = abi.VERTS_DEVICE | (abi.VERTS_REBUILD if rebuild else 0)
+        check(self._lib.pupil_pt_update_shape_vertices(
+            self._pt, int(shape), C.c_void_p(positions.data_ptr()),
+            C.c_void_p(normals.data_ptr()) if normals is not None else None, flags, C.c_void_p(s.cuda_stream)))
+        self.dirty = True
+
     # ---- inspector knobs (pt_pass.cpp:225-237)
     @property
     def max_depth(self):
@@ -216,6 +261,7 @@ class PTPass(Pass):
         self._torch.cuda.set_device(self.device_index)
         check(self._lib.pupil_pt_create(C.byref(desc), self.device_index, C.byref(self._pt)))
         self.width, self.height = desc.width, desc.height
+        self._shape_verts = [desc.shapes[i].num_vertices for i in range(desc.num_shapes)]
         self.scene_max_depth = desc.max_depth
         self._max_depth = desc.max_depth
         self._accumulate = True

@@ -209,6 +209,22 @@ class World:
         check(self._lib.pupil_world_get_instance_visibility(self._h, int(instance), C.byref(out)))
         return out.value
 
+    def set_mesh_vertices(self, shape: int, positions, normals=None):
+        """Deform mesh shape `shape` (index into desc().shapes): new positions, and normals unless
+        None (kept).  The vertex count stays.  The next desc() carries the new vertices and the
+        area emitters of the shape's emissive instances; PTPass.update_shape hands them to the
+        engine."""
+        d = self._desc if self._desc is not None else self.desc()
+        if not 0 <= int(shape) < d.num_shapes:
+            raise abi.PupilError(abi.ERR_INVALID, "shape out of range")
+        nv = d.shapes[int(shape)].num_vertices
+        p = _f32(positions)
+        n = _f32(normals) if normals is not None else None
+        if p.size != 3 * nv or (n is not None and n.size != 3 * nv):
+            raise ValueError(f"shape {shape} has {nv} vertices")
+        check(self._lib.pupil_world_set_mesh_vertices(self._h, int(shape), _ptr(p), _ptr(n)))
+        self._desc = None
+
     def add_const_env(self, radiance):
         r = _f32(radiance, 3)
         check(self._lib.pupil_world_add_const_env(self._h, _ptr(r)))
