@@ -436,6 +436,17 @@ int pupil_debug_math(int device, uint32_t n, const float *x, const float *y2, fl
 /* the device's emitter pick (EmitterGroup::SelectOneEmiiter, render/emitter.h:110-135)
  * for n random numbers p: out[i] = area emitter index, -1 = env, -2 = none */
 int pupil_debug_select_emitter(pupil_pt *pt, uint32_t n, const float *p, int32_t *out);
+/* the device's env emitter on n inputs of 3 floats, from the shading point pos_nrm =
+ * (position xyz, normal xyz); out: 8 floats per input.
+ * mode 0: Emitter::SampleDirect (render/emitter/env.h:23-49, 70-79) with xi = (in.x, in.y),
+ *         both in [0, 1]: out = wi(3), pdf, distance, radiance(3);
+ * mode 1: Emitter::Eval as __miss__default reaches it (main.cu:196-212) for a ray from the
+ *         position along in.xyz: out = radiance(3), pdf, 0, 0, 0, 0.
+ * PUPIL_ERR_INVALID without an env emitter. */
+int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const float *pos_nrm, uint32_t mode, float *out);
+/* the device's cuda::Texture::Sample (framework/cuda/texture.h:33-57) of texture `slot`
+ * (0..3) of a material on n (u, v) pairs: out = rgb per input */
+int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out);
 /* two-level structure: fills the never-written TLAS reserve [tlas_nodes, tlas_cap) of the
  * node array with nodes whose every float is `value`, then recomputes node_bound (test of
  * the bound's live-node ranges); PUPIL_ERR_UNSUPPORTED for the flattened BVH */

@@ -54,6 +54,10 @@ def lib():
         L.oracle_bsdf.argtypes = [vp, C.c_uint32, C.c_float, C.c_float, f32p, f32p, C.c_uint32, f32p]
         L.oracle_emitter_sample.argtypes = [vp, C.c_uint32, f32p, f32p, C.c_float, C.c_float, f32p]
         L.oracle_emitter_sample.restype = C.c_int
+        L.oracle_env_eval.argtypes = [vp, C.c_uint32, f32p, f32p]
+        L.oracle_env_eval.restype = C.c_int
+        L.oracle_tex_sample.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p]
+        L.oracle_tex_sample.restype = C.c_int
         L.oracle_math.argtypes = [C.c_uint32, f32p, f32p, f32p]
         L.oracle_num_prims.restype = C.c_uint32
         L.oracle_num_prims.argtypes = [vp]
@@ -74,6 +78,8 @@ class OracleScene:
         self._desc = desc  # the desc's arrays must outlive the oracle scene
         self.width, self.height = desc.width, desc.height
         self._h = lib().oracle_scene_create(C.byref(desc))
+        if not self._h:
+            raise ValueError("invalid scene desc (an env map needs at least 2 x 2 texels)")
 
     def close(self):
         if self._h:
@@ -139,6 +145,23 @@ class OracleScene:
         n = np.ascontiguousarray(nrm, np.float32)
         if lib().oracle_emitter_sample(self._h, emitter, _fp(p), _fp(n), float(xi[0]), float(xi[1]), _fp(out)) != 0:
             raise ValueError("no such emitter")
+        return out
+
+    def env_eval(self, dirs):
+        """Emitter::Eval of the env emitter on world directions (n, 3), as a miss from the origin
+        reaches it: (n, 4) radiance(3), pdf."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros((len(dirs), 4), np.float32)
+        if lib().oracle_env_eval(self._h, len(dirs), _fp(dirs), _fp(out)) != 0:
+            raise ValueError("the scene has no env emitter")
+        return out
+
+    def tex_sample(self, material, slot, uv):
+        """cuda::Texture::Sample of texture `slot` of `material` on uv (n, 2): (n, 3) rgb."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 3), np.float32)
+        if lib().oracle_tex_sample(self._h, material, slot, len(uv), _fp(uv), _fp(out)) != 0:
+            raise ValueError("no such material texture")
         return out
 
     @property

@@ -34,6 +34,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -840,7 +841,11 @@ struct Emitter {
     float3 color{0, 0, 0};
     // env map
     unsigned int map_w = 0, map_h = 0;
-    std::vector<float> row_cdf, col_cdf, row_weight;
+    // one block col_cdf | row_cdf | row_weight | 0.0f, as the reference lays the tables out
+    // (world/emitter.cpp:364-375): SampleDirect's row map_h searches row_cdf for its column
+    // and reads the trailing 0 as its row weight (the reference reads allocator padding there)
+    std::shared_ptr<const std::vector<float>> env_tables;
+    const float *row_cdf = nullptr, *col_cdf = nullptr, *row_weight = nullptr;
     float3 to_world[3], to_local[3];
     float normalization = 0.f, scale = 1.f;
 
@@ -890,7 +895,7 @@ struct Emitter {
             } break;
             case PUPIL_EMITTER_ENV_MAP: {  // env.h:23-49
                 unsigned int row_index = 0;
-                for (; row_index < row_cdf.size() - 1; ++row_index)
+                for (; row_index < map_h; ++row_index)  // row_cdf has map_h + 1 entries
                     if (xi.x <= row_cdf[row_index]) break;
                 unsigned int col_index = 0;
                 for (int i = row_index * (map_w + 1); col_index < map_w - 1; ++i, ++col_index)
@@ -931,7 +936,8 @@ struct Emitter {
                 float3 dir = normalize(g.position - scatter_pos);
                 dir = make_float3(dot(to_local[0], dir), dot(to_local[1], dir), dot(to_local[2], dir));
                 const float phi = M_PIf_ - pupil_dm::dm_atan2(dir.x, dir.z);
-                const float theta = pupil_dm::dm_acos(dir.y);
+                // a to_local row of norm 1 + ulp takes dir.y past 1 at the poles (acos -> NaN)
+                const float theta = pupil_dm::dm_acos(std::fmin(std::fmax(dir.y, -1.f), 1.f));
                 const float2 tex = make_float2(phi * 0.5f * M_1_PIf_, theta * M_1_PIf_);
                 unsigned int row_index = static_cast<unsigned int>(tex.y * map_h);
                 row_index = std::min(row_index, map_h - 2u);
@@ -964,33 +970,37 @@ Emitter LoadEmitter(const pupil_emitter &e) {
     if (e.type == PUPIL_EMITTER_ENV_MAP && e.radiance.rgba) {  // BuildEnvMapCdfTable, emitter.cpp:107-149
         const size_t w = e.radiance.width, h = e.radiance.height;
         const float *data = e.radiance.rgba;
-        r.col_cdf.resize((w + 1) * h);
-        r.row_cdf.resize(h + 1);
-        r.row_weight.resize(h);
+        // the tail after col_cdf is never shorter than one column walk (w - 1 floats)
+        auto tables = std::make_shared<std::vector<float>>((w + 1) * h + std::max((h + 1) + h + 1, w), 0.f);
+        float *col_cdf = tables->data(), *row_cdf = col_cdf + (w + 1) * h, *row_weight = row_cdf + (h + 1);
         size_t col_index = 0, row_index = 0;
         float row_sum = 0.f;
-        r.row_cdf[row_index++] = 0.f;
+        row_cdf[row_index++] = 0.f;
         for (auto y = 0u; y < h; ++y) {
             float col_sum = 0.f;
-            r.col_cdf[col_index++] = 0.f;
+            col_cdf[col_index++] = 0.f;
             for (auto x = 0u; x < w; ++x) {
                 auto pixel_index = y * w + x;
                 col_sum += GetLuminance(make_float3(data[pixel_index * 4], data[pixel_index * 4 + 1],
                                                     data[pixel_index * 4 + 2]));
-                r.col_cdf[col_index++] = col_sum;
+                col_cdf[col_index++] = col_sum;
             }
-            for (auto x = 1u; x < w; ++x) r.col_cdf[col_index - x - 1] /= col_sum;
-            r.col_cdf[col_index - 1] = 1.f;
+            for (auto x = 1u; x < w; ++x) col_cdf[col_index - x - 1] /= col_sum;
+            col_cdf[col_index - 1] = 1.f;
             float weight = std::sin((y + 0.5f) * M_PIf_ / h);
-            r.row_weight[y] = weight;
+            row_weight[y] = weight;
             row_sum += col_sum * weight;
-            r.row_cdf[row_index++] = row_sum;
+            row_cdf[row_index++] = row_sum;
         }
-        for (auto y = 1u; y < h; ++y) r.row_cdf[row_index - y - 1] /= row_sum;
-        r.row_cdf[row_index - 1] = 1.f;
+        for (auto y = 1u; y < h; ++y) row_cdf[row_index - y - 1] /= row_sum;
+        row_cdf[row_index - 1] = 1.f;
         r.normalization = 1.f / (row_sum * (2.f * M_PIf_ / w) * (M_PIf_ / h));
         r.map_w = (unsigned int)w;
         r.map_h = (unsigned int)h;
+        r.env_tables = tables;
+        r.col_cdf = col_cdf;
+        r.row_cdf = row_cdf;
+        r.row_weight = row_weight;
     }
     return r;
 }
@@ -1516,6 +1526,9 @@ bool LoadScene(const pupil_scene_desc &d, Scene &sc) {
     if (!sc.prims.empty()) sc.Build(0, (unsigned int)sc.prims.size());
     for (unsigned int i = 0; i < d.num_area_emitters; i++) sc.emitters.areas.push_back(LoadEmitter(d.area_emitters[i]));
     if (d.env && d.env->type != PUPIL_EMITTER_NONE) {
+        // Eval lerps row_weight[row], row_weight[row + 1] with row <= map_h - 2: a one-row map has no such pair
+        if (d.env->type == PUPIL_EMITTER_ENV_MAP && (!d.env->radiance.rgba || d.env->radiance.width < 2 || d.env->radiance.height < 2))
+            return false;
         sc.env_storage = LoadEmitter(*d.env);
         sc.emitters.env = &sc.env_storage;
     }
@@ -1695,7 +1708,10 @@ typedef struct oracle_scene oracle_scene;
 
 oracle_scene *oracle_scene_create(const pupil_scene_desc *d) {
     auto *sc = new oracle::Scene();
-    oracle::LoadScene(*d, *sc);
+    if (!oracle::LoadScene(*d, *sc)) {  // a desc the engine rejects with PUPIL_ERR_INVALID
+        delete sc;
+        return nullptr;
+    }
     return reinterpret_cast<oracle_scene *>(sc);
 }
 
@@ -1906,6 +1922,38 @@ int oracle_emitter_sample(oracle_scene *s, uint32_t emitter, const float *pos, c
     out[3] = r.pdf;
     out[4] = r.distance;
     out[5] = r.radiance.x, out[6] = r.radiance.y, out[7] = r.radiance.z;
+    return 0;
+}
+
+// Emitter::Eval of the env emitter on n world directions, as __miss__default reaches it
+// (main.cu:196-212) for a ray from the origin: out = radiance(3), pdf
+int oracle_env_eval(oracle_scene *s, uint32_t n, const float *dirs, float *out) {
+    auto &sc = *reinterpret_cast<oracle::Scene *>(s);
+    using namespace oracle;
+    if (!sc.emitters.env) return -1;
+    const float3 o = make_float3(0.f);
+    for (uint32_t i = 0; i < n; i++) {
+        const float3 nd = normalize(make_float3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+        LocalGeometry env_local;
+        env_local.position = o + nd;
+        EmitEvalRecord er;
+        sc.emitters.env->Eval(er, env_local, o);
+        out[4 * i] = er.radiance.x, out[4 * i + 1] = er.radiance.y, out[4 * i + 2] = er.radiance.z;
+        out[4 * i + 3] = er.pdf;
+    }
+    return 0;
+}
+
+// cuda::Texture::Sample of texture `slot` of a material on n uv pairs: out = rgb
+int oracle_tex_sample(oracle_scene *s, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out) {
+    auto &sc = *reinterpret_cast<oracle::Scene *>(s);
+    using namespace oracle;
+    if (material >= sc.materials.size() || slot >= 4) return -1;
+    const Texture &t = sc.materials[material].tex[slot];
+    for (uint32_t i = 0; i < n; i++) {
+        const float3 c = t.Sample(make_float2(uv[2 * i], uv[2 * i + 1]));
+        out[3 * i] = c.x, out[3 * i + 1] = c.y, out[3 * i + 2] = c.z;
+    }
     return 0;
 }
 

@@ -212,6 +212,7 @@ struct pupil_pt {
     std::vector<DevInstance> h_insts;
     DevInstance *d_insts = nullptr;
     DevMaterial *d_mats = nullptr;
+    uint32_t num_mats = 0;
     uint32_t *d_prim_inst = nullptr;
     DevEmitter *d_areas = nullptr, *d_env = nullptr;
     float *d_cdf = nullptr;
@@ -325,6 +326,10 @@ int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
     return PUPIL_OK;
 }
 
+// EnvMap::Eval (env.h:58-62) lerps row_weight[row], row_weight[row + 1] with row <= h - 2,
+// and SampleDirect's column walk ends at w - 1: neither is defined for a one-texel side
+bool env_map_size_ok(uint32_t w, uint32_t h) { return w >= 2 && h >= 2; }
+
 int convert_emitter(pupil_pt *pt, const pupil_emitter &e, DevEmitter &d) {
     std::memset(&d, 0, sizeof(d));
     d.type = e.type;
@@ -350,7 +355,15 @@ int convert_emitter(pupil_pt *pt, const pupil_emitter &e, DevEmitter &d) {
         const pupil_texture &t = e.radiance;
         if (t.type != PUPIL_TEX_BITMAP || !t.rgba) return fail(PUPIL_ERR_INVALID, "env map needs a bitmap");
         const size_t w = t.width, h = t.height;
-        std::vector<float> col_cdf((w + 1) * h), row_cdf(h + 1), row_weight(h);
+        if (!env_map_size_ok(t.width, t.height)) return fail(PUPIL_ERR_INVALID, "env map smaller than 2 x 2 texels");
+        // One block col_cdf | row_cdf | row_weight | 0.0f, the reference's layout
+        // (world/emitter.cpp:364-375) plus a trailing zero.  SampleDirect's row index is h
+        // whenever xi.x > row_cdf[h - 1]: its column search then walks row_cdf, as in the
+        // reference, and row_weight[h] -- allocator padding there -- is the zero, so the
+        // sample has pdf 0.  The tail is never shorter than one column walk (w - 1 floats).
+        const size_t tail = std::max((h + 1) + h + 1, w);
+        std::vector<float> tables((w + 1) * h + tail, 0.f);
+        float *col_cdf = tables.data(), *row_cdf = col_cdf + (w + 1) * h, *row_weight = row_cdf + (h + 1);
         size_t ci = 0, ri = 0;
         float row_sum = 0.f;
         row_cdf[ri++] = 0.f;
@@ -374,13 +387,11 @@ int convert_emitter(pupil_pt *pt, const pupil_emitter &e, DevEmitter &d) {
         d.normalization = 1.f / (row_sum * (2.f * kPi / w) * (kPi / h));
         d.map_w = (uint32_t)w;
         d.map_h = (uint32_t)h;
-        float *a = nullptr, *b = nullptr, *c = nullptr;
-        HIP_TRY(pt->upload(&a, row_cdf.data(), row_cdf.size()));
-        HIP_TRY(pt->upload(&b, col_cdf.data(), col_cdf.size()));
-        HIP_TRY(pt->upload(&c, row_weight.data(), row_weight.size()));
-        d.row_cdf = a;
-        d.col_cdf = b;
-        d.row_weight = c;
+        float *block = nullptr;
+        HIP_TRY(pt->upload(&block, tables.data(), tables.size()));
+        d.col_cdf = block;
+        d.row_cdf = block + (row_cdf - col_cdf);
+        d.row_weight = block + (row_weight - col_cdf);
     }
     return PUPIL_OK;
 }
@@ -1045,6 +1056,9 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     *out = nullptr;
     if (scene->width == 0 || scene->height == 0) return fail(PUPIL_ERR_INVALID, "empty film");
     if (scene->num_instances == 0) return fail(PUPIL_ERR_INVALID, "scene has no instances");
+    if (scene->env && scene->env->type == PUPIL_EMITTER_ENV_MAP &&
+        !env_map_size_ok(scene->env->radiance.width, scene->env->radiance.height))
+        return fail(PUPIL_ERR_INVALID, "env map smaller than 2 x 2 texels");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PUPIL_ERR_HIP, "no HIP device");
     if (device < 0 || device >= ndev) return fail(PUPIL_ERR_INVALID, "bad device index");
@@ -1175,6 +1189,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     }
     pt->d_insts = d_insts;
     pt->d_mats = d_mats;
+    pt->num_mats = (uint32_t)mats.size();
     pt->d_prim_inst = d_prim_inst;
     pt->leaf_size = 2u;  // with the 7-wave traversal: 2 beats 3 by 2 %, 1 and 4 are slower (config 4)
     if (const char *ls = std::getenv("PUPIL_LEAF_SIZE")) pt->leaf_size = (uint32_t)std::min(8, std::max(1, std::atoi(ls)));
@@ -1920,6 +1935,54 @@ int pupil_debug_select_emitter(pupil_pt *pt, uint32_t n, const float *p, int32_t
     if (dout) (void)hipFree(dout);
     HIP_TRY(err);
     return PUPIL_OK;
+}
+
+extern "C++" {
+namespace {
+// one probe launch: n inputs of `in_w` floats up, `out_w` floats per input back
+template <typename Launch>
+int debug_probe(pupil_pt *pt, uint32_t n, const float *in, uint32_t in_w, float *out, uint32_t out_w, Launch launch) {
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(order_after_renders(pt));
+    float *din = nullptr, *dout = nullptr;
+    HIP_TRY(hipMalloc((void **)&din, sizeof(float) * in_w * n));
+    hipError_t err = hipMalloc((void **)&dout, sizeof(float) * out_w * n);
+    if (err == hipSuccess) err = hipMemcpy(din, in, sizeof(float) * in_w * n, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+        launch(din, dout);
+        err = hipGetLastError();
+        if (err == hipSuccess) err = hipStreamSynchronize(pt->own_stream);
+    }
+    if (err == hipSuccess) err = hipMemcpy(out, dout, sizeof(float) * out_w * n, hipMemcpyDeviceToHost);
+    (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    HIP_TRY(err);
+    return PUPIL_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const float *pos_nrm, uint32_t mode, float *out) {
+    if (!pt || !xi_or_dir || !pos_nrm || !out) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (mode > 1u) return fail(PUPIL_ERR_INVALID, "unknown mode");
+    if (!pt->sc.has_env || !pt->d_env) return fail(PUPIL_ERR_INVALID, "the scene has no env emitter");
+    if (n == 0) return PUPIL_OK;
+    if (mode == 0u)  // the CDF searches take random numbers: anything else is not an input of SampleDirect
+        for (uint32_t i = 0; i < n; i++)
+            if (!(xi_or_dir[3 * i] >= 0.f && xi_or_dir[3 * i] <= 1.f && xi_or_dir[3 * i + 1] >= 0.f && xi_or_dir[3 * i + 1] <= 1.f))
+                return fail(PUPIL_ERR_INVALID, "xi outside [0, 1]");
+    return debug_probe(pt, n, xi_or_dir, 3, out, 8, [&](const float *din, float *dout) {
+        launch_debug_env(pt->sc, din, pos_nrm, mode, dout, n, pt->own_stream);
+    });
+}
+
+int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out) {
+    if (!pt || !uv || !out) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (material >= pt->num_mats || slot >= 4u) return fail(PUPIL_ERR_INVALID, "no such material texture");
+    if (n == 0) return PUPIL_OK;
+    return debug_probe(pt, n, uv, 2, out, 3, [&](const float *din, float *dout) {
+        launch_debug_tex(pt->sc, material, slot, din, dout, n, pt->own_stream);
+    });
 }
 
 int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value) {

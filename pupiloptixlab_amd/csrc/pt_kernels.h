@@ -229,6 +229,13 @@ void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);
+// the env emitter's emitter_sample_direct (mode 0, in = xi) or env_eval (mode 1, in = ray
+// direction) on n device inputs of 3 floats; pos_nrm: 6 host floats; out: 8 floats per input
+void launch_debug_env(const DeviceScene &sc, const float *in, const float *pos_nrm, uint32_t mode, float *out, uint32_t n,
+                      hipStream_t s);
+// tex_sample of materials[material].tex[slot] on n device uv pairs; out: 3 floats per input
+void launch_debug_tex(const DeviceScene &sc, uint32_t material, uint32_t slot, const float *uv, float *out, uint32_t n,
+                      hipStream_t s);
 
 // stable partition of path ids 0..n-1 by a key byte (queue_partition.hip)
 uint32_t partition_hist_entries(uint32_t n);

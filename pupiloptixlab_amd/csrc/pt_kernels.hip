@@ -213,6 +213,51 @@ __global__ void k_debug_select(DeviceScene sc, const float *p, int *out, uint32_
     out[i] = !e ? -2 : (e == sc.env && sc.has_env ? -1 : (int)(e - sc.areas));
 }
 
+// mode 0: emitter_sample_direct of the env emitter from (pos, nrm) with xi = in.xy;
+// mode 1: env_eval of a ray from pos along in.xyz.  One thread per input.
+__global__ void k_debug_env(DeviceScene sc, const float *in, vec3 pos, vec3 nrm, uint32_t mode, float *out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DevEmitter &e = *sc.env;
+    float *o = out + 8 * (size_t)i;
+    if (mode == 0u) {
+        LocalGeo g;
+        g.position = pos;
+        g.normal = nrm;
+        g.texcoord = v2(0.f, 0.f);
+        const EmitterSample r = emitter_sample_direct(e, g, v2(in[3 * i], in[3 * i + 1]));
+        o[0] = r.wi.x, o[1] = r.wi.y, o[2] = r.wi.z;
+        o[3] = r.pdf;
+        o[4] = r.distance;
+        o[5] = r.radiance.x, o[6] = r.radiance.y, o[7] = r.radiance.z;
+    } else {
+        vec3 radiance;
+        float pdf;
+        env_eval(e, pos, v3(in[3 * i], in[3 * i + 1], in[3 * i + 2]), radiance, pdf);
+        o[0] = radiance.x, o[1] = radiance.y, o[2] = radiance.z;
+        o[3] = pdf;
+        o[4] = o[5] = o[6] = o[7] = 0.f;
+    }
+}
+
+__global__ void k_debug_tex(const DevMaterial *mat, uint32_t slot, const float *uv, float *out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const vec3 c = tex_sample(mat->tex[slot], v2(uv[2 * i], uv[2 * i + 1]));
+    out[3 * i] = c.x, out[3 * i + 1] = c.y, out[3 * i + 2] = c.z;
+}
+
+void launch_debug_env(const DeviceScene &sc, const float *in, const float *pos_nrm, uint32_t mode, float *out, uint32_t n,
+                      hipStream_t s) {
+    hipLaunchKernelGGL(k_debug_env, dim3((n + 255) / 256), dim3(256), 0, s, sc, in, v3(pos_nrm[0], pos_nrm[1], pos_nrm[2]),
+                       v3(pos_nrm[3], pos_nrm[4], pos_nrm[5]), mode, out, n);
+}
+
+void launch_debug_tex(const DeviceScene &sc, uint32_t material, uint32_t slot, const float *uv, float *out, uint32_t n,
+                      hipStream_t s) {
+    hipLaunchKernelGGL(k_debug_tex, dim3((n + 255) / 256), dim3(256), 0, s, sc.materials + material, slot, uv, out, n);
+}
+
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_debug_select, dim3((n + 255) / 256), dim3(256), 0, s, sc, p, out, n);
 }

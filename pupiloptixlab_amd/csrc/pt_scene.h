@@ -60,9 +60,12 @@ struct DevEmitter {
     uint32_t map_w, map_h;
     float to_world[9];
     float to_local[9];
+    // one allocation col_cdf | row_cdf | row_weight | 0.0f (world/emitter.cpp:364-375 plus the
+    // trailing zero): SampleDirect's row map_h searches row_cdf for its column and reads the
+    // zero as its row weight
     const float *row_cdf;     // map_h + 1
     const float *col_cdf;     // (map_w + 1) * map_h
-    const float *row_weight;  // map_h
+    const float *row_weight;  // map_h (+ the zero)
 };
 
 struct DevInstance {

@@ -672,7 +672,8 @@ PT_D void env_map_eval(const DevEmitter &e, vec3 dir_world, vec3 &radiance, floa
                         dot(v3(e.to_local[3], e.to_local[4], e.to_local[5]), dir_world),
                         dot(v3(e.to_local[6], e.to_local[7], e.to_local[8]), dir_world));
     const float phi = kPi - dm_atan2(dir.x, dir.z);
-    const float theta = dm_acos(dir.y);
+    // a to_local row of norm 1 + ulp takes dir.y past 1 at the poles (acos -> NaN)
+    const float theta = dm_acos(fminf(fmaxf(dir.y, -1.f), 1.f));
     const vec2 tex = v2(phi * 0.5f * k1OverPi, theta * k1OverPi);
     uint32_t row = (uint32_t)(tex.y * e.map_h);
     if (row > e.map_h - 2u) row = e.map_h - 2u;

@@ -318,3 +318,101 @@ def test_example_render_thread_updates_match_oracle(instance, tmp_path):
     got = np.fromfile(accum, np.float32).reshape(-1, 4)
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), \
         f"{(got.view(np.uint32) != ref.view(np.uint32)).any(axis=1).sum()} pixels differ"
+
+
+# A stand-alone program over the CPU oracle (no GPU, no Python): a hand-filled scene of one
+# triangle under a 4 x 2 env map.  Built with the address and undefined-behaviour sanitizers, it
+# draws every row index -- xi.x = 1 - 2^-24 gives row index h, whose column walk and row weight
+# read past the three separate tables the oracle once kept (a heap overrun then) -- and
+# evaluates the poles.
+ENV_ORACLE_PROG = r"""
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include "pupil_pt.h"
+extern "C" {
+typedef struct oracle_scene oracle_scene;
+oracle_scene *oracle_scene_create(const pupil_scene_desc *d);
+void oracle_scene_destroy(oracle_scene *s);
+int oracle_emitter_sample(oracle_scene *s, uint32_t emitter, const float *pos, const float *nrm, float x0, float x1,
+                          float *out);
+int oracle_env_eval(oracle_scene *s, uint32_t n, const float *dirs, float *out);
+}
+int main() {
+    static const float positions[9] = {-1, 0, -1, 1, 0, -1, 0, 0, 1};
+    static const uint32_t indices[3] = {0, 1, 2};
+    static const float ident12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    static const float ident16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    float texels[4 * 2 * 4];
+    for (int i = 0; i < 8; i++) {
+        texels[4 * i] = 0.2f + 0.1f * i, texels[4 * i + 1] = 0.9f - 0.05f * i, texels[4 * i + 2] = 0.3f + 0.02f * i * i;
+        texels[4 * i + 3] = 1.f;
+    }
+    pupil_shape shape;
+    std::memset(&shape, 0, sizeof(shape));
+    shape.kind = PUPIL_SHAPE_MESH, shape.num_vertices = 3, shape.num_faces = 1;
+    shape.positions = positions, shape.indices = indices;
+    pupil_material mat;
+    std::memset(&mat, 0, sizeof(mat));
+    mat.type = PUPIL_MAT_DIFFUSE, mat.int_ior = mat.ext_ior = 1.f;
+    for (int k = 0; k < 4; k++) {
+        mat.tex[k].type = PUPIL_TEX_RGB;
+        mat.tex[k].c0[0] = mat.tex[k].c0[1] = mat.tex[k].c0[2] = 0.5f;
+        std::memcpy(mat.tex[k].transform, ident16, sizeof(ident16));
+    }
+    pupil_instance inst;
+    std::memset(&inst, 0, sizeof(inst));
+    std::memcpy(inst.to_world, ident12, sizeof(ident12));
+    std::memcpy(inst.to_object, ident12, sizeof(ident12));
+    inst.emitter_offset = -1;
+    pupil_emitter env;
+    std::memset(&env, 0, sizeof(env));
+    env.type = PUPIL_EMITTER_ENV_MAP, env.weight = 1.f, env.select_probability = 1.f, env.scale = 1.5f;
+    env.radiance.type = PUPIL_TEX_BITMAP, env.radiance.width = 4, env.radiance.height = 2, env.radiance.filter = 1;
+    env.radiance.rgba = texels;
+    std::memcpy(env.radiance.transform, ident16, sizeof(ident16));
+    for (int k = 0; k < 3; k++) env.to_world[4 * k] = env.to_local[4 * k] = 1.f;
+    pupil_scene_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.width = d.height = 4, d.max_depth = 2;
+    std::memcpy(d.sample_to_camera, ident16, sizeof(ident16));
+    std::memcpy(d.camera_to_world, ident16, sizeof(ident16));
+    d.num_shapes = d.num_materials = d.num_instances = 1;
+    d.shapes = &shape, d.materials = &mat, d.instances = &inst, d.env = &env;
+    oracle_scene *s = oracle_scene_create(&d);
+    if (!s) return 2;
+    int bad = 0;
+    const float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 1.f, 0.f};
+    const float xs[3] = {0.f, 0.5f, 1.f - 1.f / 16777216.f};
+    const float ys[6] = {0.f, 0.125f, 0.375f, 0.625f, 0.875f, 1.f - 1.f / 16777216.f};
+    for (float x : xs)
+        for (float y : ys) {
+            float out[8];
+            if (oracle_emitter_sample(s, 0, pos, nrm, x, y, out) != 0) return 3;
+            for (float v : out)
+                if (!std::isfinite(v)) bad++;
+            if (x > 0.9f ? out[3] != 0.f : !(out[3] > 0.f)) bad++;  // row index h: pdf exactly 0
+            std::printf("xi %.8f %.3f pdf %.6g\n", x, y, out[3]);
+        }
+    const float poles[6] = {0.f, 1.f, 0.f, 0.f, -1.f, 0.f};
+    float ev[8];
+    if (oracle_env_eval(s, 2, poles, ev) != 0) return 3;
+    for (float v : ev)
+        if (!std::isfinite(v)) bad++;
+    oracle_scene_destroy(s);
+    return bad ? 1 : 0;
+}
+"""
+
+
+def test_oracle_env_sampling_under_sanitizers(tmp_path):
+    src = tmp_path / "env_oracle.cpp"
+    src.write_text(ENV_ORACLE_PROG)
+    exe = tmp_path / "env_oracle"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "include"), str(src),
+                        os.path.join(ROOT, "oracle", "pt_oracle.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr

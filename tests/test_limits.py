@@ -1,6 +1,7 @@
 """Host-side checks of the BVH4 leaf-link limits (csrc/accel_limits.h): the
 two-level build must refuse or fall back before a 28-bit record slot wraps into the sign
-bit of a leaf link.  Compiled with g++ (no GPU)."""
+bit of a leaf link.  Compiled with g++ (no GPU).  And the smallest env map: EnvMap::Eval lerps
+two row weights (env.h:58-62), so a map with a one-texel side is refused at scene set-up."""
 import os
 import subprocess
 
@@ -49,3 +50,26 @@ def test_two_level_leaf_link_limits(tmp_path):
     assert r.returncode == 0, r.stderr
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
+
+
+@pytest.mark.parametrize("side", ["width", "height"])
+def test_env_map_with_a_one_texel_side_is_rejected(side):
+    """map_h - 2u wraps for a one-row map and row_weight[row + 1] leaves the table: the engine
+    returns PUPIL_ERR_INVALID before it touches a device (so also on a host without one), and
+    the oracle refuses the same desc."""
+    import ctypes as C
+
+    import oracle
+    import sampling_cases as sc
+    from pupiloptixlab_amd import abi
+
+    desc = sc.env_scene(16, 8)
+    h = C.c_void_p()
+    lib = abi.load_library()
+    setattr(desc.env.contents.radiance, side, 2)  # 2 x 8 and 16 x 2 are the smallest accepted
+    oracle.OracleScene(desc).close()
+    setattr(desc.env.contents.radiance, side, 1)
+    assert lib.pupil_pt_create(C.byref(desc), 0, C.byref(h)) == abi.ERR_INVALID
+    assert b"env map" in lib.pupil_last_error() and not h.value
+    with pytest.raises(ValueError):
+        oracle.OracleScene(desc)
