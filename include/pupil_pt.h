@@ -381,12 +381,34 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
  * the call fails after the argument checks (PUPIL_ERR_HIP / _OOM / _UNSUPPORTED from the refit or
  * the builders), the engine's vertex arrays already hold the new vertices while the acceleration
  * structure still bounds the old ones: do not render until a later call for this shape succeeds
- * (PUPIL_VERTS_REBUILD is the one that depends on nothing left behind).  pupil_pt_motion_vectors does not see vertex
- * motion (camera and rigid instance motion only).  No ABI bump: detect the symbol. */
+ * (PUPIL_VERTS_REBUILD is the one that depends on nothing left behind).  pupil_pt_motion_vectors
+ * sees the vertex motion of an update that pupil_pt_snapshot_shape_vertices preceded (below);
+ * without a snapshot it reports camera and rigid instance motion only.  No ABI bump: detect the
+ * symbol. */
 #define PUPIL_VERTS_DEVICE 1u
 #define PUPIL_VERTS_REBUILD 2u
 int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *positions, const float *normals,
                                    uint32_t flags, void *hip_stream);
+/* Flow for deforming meshes.  pupil_pt_snapshot_shape_vertices keeps the vertices mesh shape
+ * `shape` has NOW as its "previous" vertices, for the flow of the update that follows: call it
+ * before pupil_pt_update_shape_vertices.  While a shape holds a snapshot, pupil_pt_motion_vectors
+ * carries every hit on an instance of it back by the displacement of the hit point (barycentric
+ * blend of the three vertices' now-minus-snapshot displacements) before the previous instance
+ * transform and camera go on; hits on other shapes, and on triangles whose vertices did not move,
+ * get bit for bit the flow they get without a snapshot.  The copy is device to device from the
+ * engine's own array into a per-shape array allocated on first use, on the engine's stream after
+ * every render and flow pass enqueued so far; every later flow pass is ordered after it.  A second
+ * call for the shape overwrites the snapshot.  Works for emissive shapes, hidden instances and
+ * shapes no instance shows, and survives PUPIL_VERTS_REBUILD (vertex count, indices and global
+ * primitive ids never change).  Drops no frame in flight, is no refit (accel_refits and build_ms
+ * stay) and changes no pixel of any render.  PUPIL_ERR_INVALID: pt NULL, shape out of range or a
+ * PUPIL_SHAPE_SPHERE; PUPIL_ERR_OOM: the 12 B x num_vertices array could not be allocated (the
+ * shape then holds no snapshot).
+ * pupil_pt_clear_vertex_snapshots forgets every snapshot (the allocations are kept): flow is
+ * camera and rigid instance motion again, by the same kernel with the same arguments as before
+ * the first snapshot.  PUPIL_ERR_INVALID: pt NULL.  No ABI bump: detect the symbols. */
+int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape);
+int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
 /* replaces the area-emitter table, selection CDF and env emitter (after an emissive instance moved);
  * rewritten in place on the engine's stream when their shapes are unchanged */
 int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
@@ -406,7 +428,10 @@ void pupil_pt_destroy(pupil_pt *pt);
  * under the previous camera and the previous instance transforms.  An environment miss is the
  * point at infinity along the ray; a point at or behind the previous camera plane has no
  * previous pixel and gets (NaN, NaN).  Flow is that of the primary hit (nothing is followed
- * through reflections or refractions), and only rigid instance motion is covered.
+ * through reflections or refractions).  Rigid instance motion is covered through prev_to_world,
+ * vertex motion of the shapes that hold a snapshot (pupil_pt_snapshot_shape_vertices) through
+ * the snapshots: p' = prev_to_world (to_object p - d), d = the object-space displacement of the
+ * hit point since the snapshot.
  * prev_to_world: num_instances * 12 floats (row-major 3x4, host) or NULL = no instance moved.
  * Asynchronous on hip_stream, ordered after every render enqueued so far; the current camera
  * and instance transforms are the engine's (pupil_pt_set_camera / pupil_pt_update_instances).

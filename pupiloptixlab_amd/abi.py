@@ -130,6 +130,8 @@ SIGNATURES = {
     "pupil_pt_update_instances_masked": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p, u32p]),
     "pupil_pt_update_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                   C.c_void_p]),
+    "pupil_pt_snapshot_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "pupil_pt_clear_vertex_snapshots": (C.c_int, [C.c_void_p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_debug_fill_tlas_reserve": (C.c_int, [C.c_void_p, C.c_float]),
     "pupil_pt_render": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Launch), C.c_void_p]),

@@ -233,6 +233,10 @@ struct pupil_pt {
         uint32_t kind = PUPIL_SHAPE_MESH, num_vertices = 0, num_faces = 0;
         float *pos = nullptr, *nrm = nullptr, *tex = nullptr;
         uint32_t *idx = nullptr;
+        // pupil_pt_snapshot_shape_vertices: the vertices from before an update (allocated on the
+        // first snapshot and kept), and whether the flow pass uses them
+        float *prev = nullptr;
+        bool prev_valid = false;
     };
     std::vector<ShapeDev> shapes;
     std::vector<uint32_t> inst_shape;
@@ -245,6 +249,15 @@ struct pupil_pt {
     float *flow_prev = nullptr;
     std::vector<float> h_flow_prev;
     hipEvent_t ev_flow = nullptr;
+    // vertex snapshots (ShapeDev::prev) as the flow pass reads them: per instance the snapshot of
+    // its shape or null, uploaded by the first flow pass after the set of snapshots changed
+    // (flow_verts_stale; staged like flow_prev, under ev_flow); ev_snap: the last snapshot copy
+    // on the engine's stream, which every flow pass waits for while snapshots are held
+    const float **flow_verts = nullptr;
+    std::vector<const float *> h_flow_verts;
+    uint32_t snapshots = 0;
+    bool flow_verts_stale = false;
+    hipEvent_t ev_snap = nullptr;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -294,6 +307,7 @@ struct pupil_pt {
         if (ev_end) (void)hipEventDestroy(ev_end);
         if (ev_sync) (void)hipEventDestroy(ev_sync);
         if (ev_flow) (void)hipEventDestroy(ev_flow);
+        if (ev_snap) (void)hipEventDestroy(ev_snap);
         if (ev_verts) (void)hipEventDestroy(ev_verts);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -1514,6 +1528,41 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     return PUPIL_OK;
 }
 
+// The "previous" vertices of the flow pass (pt_flow.hip): a device-to-device copy of the shape's
+// own array on the engine's stream, after every render and flow pass enqueued so far (an earlier
+// flow pass may still read the snapshot this one overwrites) and before the vertex update that
+// follows on the same stream.  Nothing a render reads changes: no refit, no frames dropped.
+int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "shape index out of range");
+    pupil_pt::ShapeDev &sd = pt->shapes[shape];
+    if (sd.kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
+    HIP_TRY(hipSetDevice(pt->device));
+    if (!pt->ev_snap) HIP_TRY(hipEventCreateWithFlags(&pt->ev_snap, hipEventDisableTiming));
+    if (!sd.prev && pt->alloc(&sd.prev, 3 * (size_t)sd.num_vertices) != hipSuccess) {
+        (void)hipGetLastError();
+        sd.prev = nullptr;
+        return fail(PUPIL_ERR_OOM, "vertex snapshot allocation failed");
+    }
+    HIP_TRY(order_after_renders(pt));
+    HIP_TRY(hipMemcpyAsync(sd.prev, sd.pos, sizeof(float) * 3 * (size_t)sd.num_vertices, hipMemcpyDeviceToDevice,
+                           pt->own_stream));
+    HIP_TRY(hipEventRecord(pt->ev_snap, pt->own_stream));
+    if (!sd.prev_valid) {
+        sd.prev_valid = true;
+        pt->snapshots++;
+        pt->flow_verts_stale = true;
+    }
+    return PUPIL_OK;
+}
+
+int pupil_pt_clear_vertex_snapshots(pupil_pt *pt) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    for (pupil_pt::ShapeDev &sd : pt->shapes) sd.prev_valid = false;
+    pt->snapshots = 0;  // the flow pass reads no table; the next snapshot uploads a new one
+    return PUPIL_OK;
+}
+
 int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, const float *to_world,
                               const float *to_object) {
     if (!pt || (n && (!ids || !to_world || !to_object))) return fail(PUPIL_ERR_INVALID, "null argument");
@@ -1857,6 +1906,8 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
 // stream events after every render enqueued so far (the traversal's overflow stacks are shared
 // with them), and the renders after it order themselves behind it the same way.  Its traversal
 // has its own work-counter slot and adds to none of the ray totals pupil_pt_stats reports.
+// While shapes hold vertex snapshots the projection also takes the vertex motion off the hit
+// point (k_flow_project_deform); with none held the pass is launched as it always was.
 int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16], const float prev_camera_to_world[16],
                             const float *prev_to_world, void *out_flow, uint32_t compact, uint32_t tile_size,
                             uint32_t tile_rank, uint32_t tile_world, void *hip_stream) {
@@ -1891,16 +1942,34 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
         HIP_TRY(hipEventRecord(pt->ev_sync, pt->last_stream));
         HIP_TRY(hipStreamWaitEvent(s, pt->ev_sync, 0));
     }
+    // vertex snapshots held: after the last snapshot copy (the vertex update that followed it has
+    // synchronised the engine's stream), with the per-instance table of snapshot arrays
+    const bool table = pt->snapshots > 0 && pt->flow_verts_stale;
+    if (pt->snapshots > 0) HIP_TRY(hipStreamWaitEvent(s, pt->ev_snap, 0));
+    if (prev_to_world || table) {
+        if (!pt->ev_flow) HIP_TRY(hipEventCreateWithFlags(&pt->ev_flow, hipEventDisableTiming));
+        else HIP_TRY(hipEventSynchronize(pt->ev_flow));  // the previous upload has left the staging copies
+    }
     if (prev_to_world) {
         const size_t nf = 12 * pt->h_insts.size();
         if (!pt->flow_prev) HIP_TRY(pt->alloc(&pt->flow_prev, nf));
-        if (!pt->ev_flow) HIP_TRY(hipEventCreateWithFlags(&pt->ev_flow, hipEventDisableTiming));
-        else HIP_TRY(hipEventSynchronize(pt->ev_flow));  // the previous upload has left the staging copy
         pt->h_flow_prev.assign(prev_to_world, prev_to_world + nf);
         if (nf) HIP_TRY(hipMemcpyAsync(pt->flow_prev, pt->h_flow_prev.data(), sizeof(float) * nf, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(pt->ev_flow, s));
         job.prev_to_world = pt->flow_prev;
     }
+    if (table) {
+        const size_t ni = pt->h_insts.size();
+        if (!pt->flow_verts) HIP_TRY(pt->alloc(&pt->flow_verts, ni));
+        pt->h_flow_verts.assign(ni, nullptr);
+        for (size_t i = 0; i < ni; i++) {
+            const pupil_pt::ShapeDev &sd = pt->shapes[pt->inst_shape[i]];
+            if (sd.kind == PUPIL_SHAPE_MESH && sd.prev_valid) pt->h_flow_verts[i] = sd.prev;
+        }
+        HIP_TRY(hipMemcpyAsync(pt->flow_verts, pt->h_flow_verts.data(), sizeof(const float *) * ni, hipMemcpyHostToDevice, s));
+        pt->flow_verts_stale = false;
+    }
+    if (prev_to_world || table) HIP_TRY(hipEventRecord(pt->ev_flow, s));
+    const float *const *prev_verts = pt->snapshots > 0 ? pt->flow_verts : nullptr;
     job.width = pt->width;
     job.height = pt->height;
     job.n = num_local;
@@ -1909,7 +1978,7 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
     launch_flow_rays(pt->sc, pt->width, pt->height, job.pixel_map, num_local, pt->flow_rays, s);
     launch_trace_debug(pt->sc, (const float *)pt->flow_rays, (float *)pt->flow_hits, num_local, 0, pt->ovf,
                        pt->ovf_threads, pt->q.work + kWorkFlow, s);
-    launch_flow_project(pt->sc, job, pt->flow_rays, pt->flow_hits, (float2 *)out_flow, s);
+    launch_flow_project(pt->sc, job, pt->flow_rays, pt->flow_hits, (float2 *)out_flow, s, prev_verts);
     HIP_TRY(hipGetLastError());
     pt->last_stream = s;
     pt->rendered = true;

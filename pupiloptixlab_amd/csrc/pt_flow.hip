@@ -11,7 +11,10 @@
 // no previous pixel: (NaN, NaN), which the denoiser reads as "no history".
 //
 // Both kernels are one pixel per lane and stream: 32 B of ray record out (two 16-B stores), then
-// 48 B in and 8 B out (one float2 store); the instance tables stay in the L2.
+// 48 B in and 8 B out (one float2 store); the instance tables stay in the L2.  While a shape holds
+// a vertex snapshot (pupil_pt_snapshot_shape_vertices) the projection also undoes the vertex
+// motion: a pixel on such a shape gathers 12 B of indices and 2 x 36 B of vertices, which
+// neighbouring pixels share (they hit the same or neighbouring triangles).
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
@@ -52,8 +55,33 @@ __global__ __launch_bounds__(kFlowBlock) void k_flow_rays(Camera cam, uint32_t w
     rays[2 * (size_t)l + 1] = make_float4(d.y, d.z, 0.001f, kMaxDistance);
 }
 
-__global__ __launch_bounds__(kFlowBlock) void k_flow_project(DeviceScene sc, FlowJob job, const float4 *rays,
-                                                             const float4 *hits, float2 *flow) {
+__device__ __forceinline__ vec3 vertex3(const float *v, uint32_t i) {
+    return v3(v[3 * (size_t)i], v[3 * (size_t)i + 1], v[3 * (size_t)i + 2]);
+}
+
+// Object-space displacement (now minus before) of the point with barycentrics (b1, b2) on face
+// f of instance `in`, whose shape's vertices were prevv before the update: the weights are
+// reconstruct()'s (pt_shade.h), 1 - b1 - b2 on the face's first vertex.  Exactly 0 where the three
+// vertices did not move.  The 3 index loads go out together, then the 18 vertex loads.
+__device__ __forceinline__ vec3 vertex_displacement(const DevInstance &in, const float *prevv, uint32_t f, float b1,
+                                                    float b2) {
+    const uint32_t i0 = in.indices[3 * (size_t)f], i1 = in.indices[3 * (size_t)f + 1], i2 = in.indices[3 * (size_t)f + 2];
+    const vec3 c0 = vertex3(in.positions, i0), c1 = vertex3(in.positions, i1), c2 = vertex3(in.positions, i2);
+    const vec3 v0 = vertex3(prevv, i0), v1 = vertex3(prevv, i1), v2 = vertex3(prevv, i2);
+    const float w = 1.f - b1 - b2;
+    return w * (c0 - v0) + b1 * (c1 - v1) + b2 * (c2 - v2);
+}
+
+// DEFORM = false is the pass without vertex snapshots: prev_verts is not read.  DEFORM = true
+// (prev_verts: per instance the snapshot of its shape or null) runs the same arithmetic on the
+// pixels of instances without a snapshot, and takes the object-space displacement d of the hit
+// point off it on the others before the previous transform goes on:
+//     p' = prev_to_world (to_object p - d),   or   p' = p - L d   (L = the linear part of to_world)
+// when no instance moved.  The displacement form, not the re-interpolated previous position: where
+// d = 0 (the unmoved part of a mesh that deforms in part) p' is bit for bit the rigid pass's.
+template <bool DEFORM>
+__device__ __forceinline__ void flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays,
+                                             const float4 *hits, float2 *flow, const float *const *prev_verts) {
     const uint32_t l = blockIdx.x * kFlowBlock + threadIdx.x;
     if (l >= job.n) return;
     const uint32_t pixel = job.pixel_map ? job.pixel_map[l] : l;
@@ -66,8 +94,21 @@ __global__ __launch_bounds__(kFlowBlock) void k_flow_project(DeviceScene sc, Flo
     vec4 q = v4(d.x, d.y, d.z, 0.f);
     if (prim != kMissIndex) {
         vec3 p = v3(r0.x, r0.y, r0.z) + h.x * d;
-        if (job.prev_to_world) {  // the same object-space point under the instance's previous transform
-            const uint32_t inst = inst_of_prim(sc, prim);
+        const float *prevv = nullptr;
+        uint32_t inst = 0;
+        if (DEFORM) {
+            inst = inst_of_prim(sc, prim);
+            prevv = prev_verts[inst];
+        }
+        if (DEFORM && prevv) {  // a deformed mesh: the point the hit was on before the update
+            const DevInstance &in = sc.instances[inst];
+            const vec3 dv = vertex_displacement(in, prevv, prim - in.prim_offset, h.y, h.z);
+            if (job.prev_to_world)
+                p = xform_point(job.prev_to_world + 12 * (size_t)inst, xform_point(in.to_object, p) - dv);
+            else
+                p = p - xform_vector(in.to_world, dv);
+        } else if (job.prev_to_world) {  // the same object-space point under the instance's previous transform
+            if (!DEFORM) inst = inst_of_prim(sc, prim);
             p = xform_point(job.prev_to_world + 12 * (size_t)inst, xform_point(sc.instances[inst].to_object, p));
         }
         q = v4(p.x, p.y, p.z, 1.f);
@@ -83,6 +124,17 @@ __global__ __launch_bounds__(kFlowBlock) void k_flow_project(DeviceScene sc, Flo
     flow[job.compact ? l : pixel] = f;
 }
 
+__global__ __launch_bounds__(kFlowBlock) void k_flow_project(DeviceScene sc, FlowJob job, const float4 *rays,
+                                                             const float4 *hits, float2 *flow) {
+    flow_project<false>(sc, job, rays, hits, flow, nullptr);
+}
+
+__global__ __launch_bounds__(kFlowBlock) void k_flow_project_deform(DeviceScene sc, FlowJob job, const float4 *rays,
+                                                                    const float4 *hits, float2 *flow,
+                                                                    const float *const *prev_verts) {
+    flow_project<true>(sc, job, rays, hits, flow, prev_verts);
+}
+
 }  // namespace
 
 void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, const uint32_t *pixel_map, uint32_t n,
@@ -92,9 +144,12 @@ void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, co
 }
 
 void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays, const float4 *hits,
-                         float2 *flow, hipStream_t s) {
-    hipLaunchKernelGGL(k_flow_project, dim3((job.n + kFlowBlock - 1) / kFlowBlock), dim3(kFlowBlock), 0, s, sc, job,
-                       rays, hits, flow);
+                         float2 *flow, hipStream_t s, const float *const *prev_verts) {
+    const dim3 grid((job.n + kFlowBlock - 1) / kFlowBlock);
+    if (prev_verts)
+        hipLaunchKernelGGL(k_flow_project_deform, grid, dim3(kFlowBlock), 0, s, sc, job, rays, hits, flow, prev_verts);
+    else
+        hipLaunchKernelGGL(k_flow_project, grid, dim3(kFlowBlock), 0, s, sc, job, rays, hits, flow);
 }
 
 }  // namespace pupil

@@ -224,8 +224,11 @@ struct FlowJob {
 };
 void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, const uint32_t *pixel_map, uint32_t n,
                       float4 *rays, hipStream_t s);
+// prev_verts (deforming meshes, pupil_pt_snapshot_shape_vertices): device, per instance the
+// vertices its shape had before the update (3 floats per vertex) or null.  null = no shape holds
+// a snapshot: the kernel and its arguments are then those of the rigid-only pass.
 void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays, const float4 *hits,
-                         float2 *flow, hipStream_t s);
+                         float2 *flow, hipStream_t s, const float *const *prev_verts = nullptr);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

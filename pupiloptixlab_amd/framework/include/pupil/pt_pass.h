@@ -35,6 +35,10 @@ public:
     // restarts accumulation.  World::SetMeshVertices calls this through its event; several
     // updates of a shape before one OnRun cost one refit.
     void UpdateShape(uint32_t shape) noexcept;
+    // Flow for deforming meshes (default off): OnRun keeps a pending shape's vertices from before
+    // its update (pupil_pt_snapshot_shape_vertices), so ComputeMotionVectors covers the
+    // deformation, and forgets the snapshots on an OnRun that applies no shape update.
+    void SetKeepPreviousVertices(bool on) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in
@@ -67,6 +71,8 @@ private:
     bool m_have_cam = false;
     std::vector<float> m_to_world, m_prev_to_world;  // 12 floats per instance
     bool m_instances_moved = false;                 // by the last OnRun
+    std::atomic_bool m_keep_prev_verts = false;     // SetKeepPreviousVertices
+    bool m_snapshots = false;                       // the engine holds vertex snapshots
 };
 
 }  // namespace Pupil::pt

@@ -26,6 +26,10 @@ void PTPass::OnRun() noexcept {
     if (!m_engine) return;
     std::memcpy(m_cam[1], m_cam[0], sizeof(m_cam[0]));  // the previous OnRun's view, for ComputeMotionVectors
     m_instances_moved = false;
+    if (m_snapshots) {  // the vertex snapshots of the OnRun before are a frame old
+        pupil_pt_clear_vertex_snapshots(m_engine);
+        m_snapshots = false;
+    }
     if (m_dirty) {
         m_dirty = false;  // an event after this point marks the next frame dirty again
         std::vector<uint32_t> moved, deformed;
@@ -52,6 +56,10 @@ void PTPass::OnRun() noexcept {
             for (uint32_t shape : deformed) {
                 if (shape >= d.num_shapes) continue;
                 const pupil_shape &sh = d.shapes[shape];
+                if (m_keep_prev_verts && sh.kind == PUPIL_SHAPE_MESH) {  // the "before" of ComputeMotionVectors
+                    if (pupil_pt_snapshot_shape_vertices(m_engine, shape) == PUPIL_OK) m_snapshots = true;
+                    else Log("%s: vertex snapshot failed: %s", name.c_str(), pupil_last_error());
+                }
                 if (pupil_pt_update_shape_vertices(m_engine, shape, sh.positions, sh.normals, 0u, nullptr) != PUPIL_OK) {
                     Log("%s: shape update failed: %s", name.c_str(), pupil_last_error());
                     continue;  // the other shapes and their emitters still follow
@@ -125,6 +133,7 @@ void PTPass::SetScene(world::World *world) noexcept {
         pupil_pt_destroy(m_engine);
         m_engine = nullptr;
     }
+    m_snapshots = false;  // they went with the engine
     int w = world->scene->sensor.film.w, h = world->scene->sensor.film.h;
     m_max_depth = world->scene->integrator.max_depth;
     m_accumulated_flag = true;
@@ -238,6 +247,8 @@ void PTPass::UpdateShape(uint32_t shape) noexcept {
     }
     m_dirty = true;
 }
+
+void PTPass::SetKeepPreviousVertices(bool on) noexcept { m_keep_prev_verts = on; }
 
 bool PTPass::Stats(pupil_pt_counters &out) noexcept { return m_engine && pupil_pt_stats(m_engine, &out) == PUPIL_OK; }
 

@@ -112,6 +112,10 @@ class PTPass(Pass):
         self._cam = self._last_cam = self._prev_cam = None
         self._to_world = self._prev_to_world = None
         self._moved = False  # update_instances ran since the last render
+        # flow of deforming meshes: the shapes updated with keep_previous since the last render
+        # (their snapshot, the first "before", stays), and whether the engine holds snapshots
+        self._kept = set()
+        self._snapshots = False
         self.events = events or Events()
         self.events.bind(Events.CAMERA_CHANGE, lambda _: self.mark_dirty())
         self.events.bind(Events.RENDER_INSTANCE_UPDATE, self._on_instance_update)
@@ -162,13 +166,32 @@ class PTPass(Pass):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
 
-    def update_shape(self, world, shape: int, rebuild: bool = False):
+    def _keep_previous(self, shape: int):
+        """The vertices `shape` has now become its "previous" vertices for motion_vectors()
+        (pupil_pt_snapshot_shape_vertices), unless an update since the last render already kept
+        them: like _prev_to_world, the first "before" stays.  The first kept update after a render
+        forgets the snapshots of the frame before, so only the shapes deformed since that render
+        carry vertex flow."""
+        if shape in self._kept:
+            return
+        if not self._kept and self._snapshots:
+            check(self._lib.pupil_pt_clear_vertex_snapshots(self._pt))
+            self._snapshots = False
+        check(self._lib.pupil_pt_snapshot_shape_vertices(self._pt, shape))
+        self._kept.add(shape)
+        self._snapshots = True
+
+    def update_shape(self, world, shape: int, rebuild: bool = False, keep_previous: bool = False):
         """Deformed mesh applied now: the vertices `world` holds for `shape` (World.set_mesh_vertices)
         go into the engine with ONE refit over every instance of the shape
         (pupil_pt_update_shape_vertices; rebuild: PUPIL_VERTS_REBUILD), then the emitter table if
-        an instance of the shape emits; restarts accumulation."""
+        an instance of the shape emits; restarts accumulation.  keep_previous: the engine keeps
+        the vertices from before, and motion_vectors() after the next render covers the
+        deformation."""
         desc = world.desc()
         sh = desc.shapes[int(shape)] if 0 <= int(shape) < desc.num_shapes else None
+        if keep_previous:
+            self._keep_previous(int(shape))
         check(self._lib.pupil_pt_update_shape_vertices(
             self._pt, int(shape), C.cast(sh.positions, C.c_void_p) if sh is not None else None,
             C.cast(sh.normals, C.c_void_p) if sh is not None and sh.normals else None,
@@ -178,11 +201,13 @@ class PTPass(Pass):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
 
-    def update_shape_device(self, shape: int, positions, normals=None, rebuild: bool = False, stream=None):
+    def update_shape_device(self, shape: int, positions, normals=None, rebuild: bool = False, stream=None,
+                            keep_previous: bool = False):
         """The same from device tensors (float32, contiguous, 3 per vertex, on the pass's device):
         the copy into the engine's arrays is ordered after the work enqueued so far on `stream`
         (default: the current stream) and never passes through the host.  A shape with an
-        emissive instance raises PUPIL_ERR_UNSUPPORTED: use update_shape."""
+        emissive instance raises PUPIL_ERR_UNSUPPORTED: use update_shape.  keep_previous: as
+        update_shape's."""
         torch = self._torch
         if not self._pt:
             raise abi.PupilError(abi.ERR_INVALID, "no scene set")
@@ -201,6 +226,8 @@ class PTPass(Pass):
                 raise ValueError(f"update_shape_device needs tensors on {self.device}, got {t.device}")
         s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
         flags = abi.VERTS_DEVICE | (abi.VERTS_REBUILD if rebuild else 0)
+        if keep_previous:
+            self._keep_previous(int(shape))
         check(self._lib.pupil_pt_update_shape_vertices(
             self._pt, int(shape), C.c_void_p(positions.data_ptr()),
             C.c_void_p(normals.data_ptr()) if normals is not None else None, flags, C.c_void_p(s.cuda_stream)))
@@ -314,6 +341,9 @@ class PTPass(Pass):
         always do)."""
         if not self._moved:
             self._prev_to_world = None  # no instance moved between the last render and this one
+        if not self._kept and self._snapshots:  # nor did a mesh deform: its snapshot is a frame old
+            check(self._lib.pupil_pt_clear_vertex_snapshots(self._pt))
+            self._snapshots = False
         if self.dirty:  # pt_pass.cpp:40-49: camera re-uploaded, instances refitted, accumulation restarted
             pending, self._pending = self._pending, {}
             for world, ids in pending.values():
@@ -341,6 +371,7 @@ class PTPass(Pass):
         if self._accumulate:
             self.sample_cnt += spp
         self._moved = False
+        self._kept = set()
         self._prev_cam, self._last_cam = self._last_cam, self._cam  # the views of the last two renders
 
     def motion_vectors(self, prev_camera=None, prev_to_world=None, stream=None):
@@ -350,15 +381,20 @@ class PTPass(Pass):
         camera_to_world) of the previous frame, 16 floats each; prev_to_world: (num_instances, 12)
         previous instance transforms, or None = no instance moved.  With no arguments both mean
         "since my previous render": the camera of the render before the last one and, if
-        instances were moved between the two, the transforms they had before.  That needs the
-        engine to hold what the last render used: after update_instances, render first (or
-        pass prev_camera and prev_to_world)."""
+        instances were moved between the two, the transforms they had before; the vertices of the
+        meshes deformed between the two with keep_previous are covered too.  That needs the
+        engine to hold what the last render used: after update_instances or a keep_previous
+        update, render first (or pass prev_camera and prev_to_world; the vertex motion is then
+        that of whatever snapshots the engine holds)."""
         import numpy as np
 
         if prev_camera is None:
             if self._moved:
                 raise RuntimeError("instances were updated since the last render: render before motion_vectors(), "
                                    "or pass prev_camera / prev_to_world")
+            if self._kept:
+                raise RuntimeError("a mesh was deformed with keep_previous since the last render: render before "
+                                   "motion_vectors(), or pass prev_camera")
             prev_camera = self._prev_cam
             if prev_to_world is None:
                 prev_to_world = self._prev_to_world
@@ -418,6 +454,8 @@ class PTPass(Pass):
         if self._pt:
             self._lib.pupil_pt_destroy(self._pt)
             self._pt = C.c_void_p()
+        self._kept = set()  # the snapshots went with the engine
+        self._snapshots = False
 
     def __del__(self):  # pragma: no cover
         try:
