@@ -17,9 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pupil_pt.h"
-#include "accel_two_level.h"
-#include "pt_kernels.h"
+#include "pt_accel.h"
 
 namespace {
 
@@ -28,19 +26,6 @@ thread_local std::string g_last_error;
 // most event pairs pending at once: a PUPIL_STATS_TRACE_TIMING sequence that is never
 // read folds its pairs into sums at this count, a deep timed render stops recording
 constexpr uint32_t kMaxPairs = 4096;
-
-int fail(int code, const std::string &msg) {
-    g_last_error = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess)                                                                             \
-            return fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,                        \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                               \
-    } while (0)
 
 using namespace pupil;
 
@@ -87,23 +72,25 @@ namespace Pupil {
 void set_last_error(const std::string &m) { g_last_error = m; }
 }  // namespace Pupil
 
+int pupil::fail(int code, const std::string &msg) {
+    g_last_error = msg;
+    return code;
+}
+
 struct pupil_pt {
     int device = 0;
     hipStream_t own_stream = nullptr;
     DeviceScene sc{};
     std::vector<void *> allocs;
-    BvhBuildOutput bvh{};
-    bool two_level = false;  // TLAS + per-shape BLAS (accel_two_level.hip) instead of one flattened BVH
+    SceneAccel accel;
     bool primary_interleave = true;  // primary extend dequeues pixel-major (PUPIL_PRIMARY_ORDER)
     bool shade_list = false;  // shade walks the traced list instead of a material partition (PUPIL_SHADE_LIST)
     // list shading: a fresh batch's generate stores only its camera rays, and its bounce-0 shade
     // derives throughput, radiance and RNG (PUPIL_FRESH_SHADE=0: generate stores them all)
     bool fresh_shade = true;
     bool fresh() const { return fresh_shade && shade_list; }
-    TwoLevelAccel tl{};
     uint32_t width = 0, height = 0, max_depth = 1;
     uint32_t num_prims = 0;
-    uint32_t leaf_size = 2;  // primitives per BVH leaf (PUPIL_LEAF_SIZE)
     // Pipelined frames (render_pipelined, PUPIL_PIPE): the path state is a ring of K
     // slots of one batch each; consecutive renders that continue each other (OnRun
     // cadence, or PUPIL_HINT_CONTINUE) keep up to K frames in flight, each at its own
@@ -169,7 +156,6 @@ struct pupil_pt {
     size_t aov_cap = 0;
     hipStream_t last_stream = nullptr;  // of the last render (NULL = the default stream)
     bool rendered = false;
-    double build_ms = 0.0;
     // path state / queues (grown on demand)
     size_t cap = 0;
     PathState ps{};
@@ -187,7 +173,6 @@ struct pupil_pt {
     // render's own counts are [0..1] - [2..3] without a per-render clear (snap_taken)
     unsigned long long *ray_cum = nullptr;
     bool snap_taken = false;
-    uint32_t *node_bound = nullptr;                // launch_node_bound's result (3 floats as bits)
     uint64_t primary_cum = 0;                      // host running total of camera rays
     uint32_t last_paths = 0, last_iters = 0;
     uint64_t last_primary = 0;
@@ -203,7 +188,6 @@ struct pupil_pt {
     // pairs of a PUPIL_STATS_TRACE_TIMING sequence folded into sums once kMaxPairs are pending
     double kept_ms[4] = {0.0, 0.0, 0.0, 0.0};
     uint64_t kept_n[4] = {0, 0, 0, 0};
-    uint64_t refits = 0;  // acceleration structure refits / rebuilds after instance updates
     // PUPIL_TRACE_TAIL: per-wave start / drained / exit times of each traversal launch of a stats render
     unsigned long long *tail_buf = nullptr;
     uint32_t tail_waves = 0, tail_launches = 0;
@@ -222,25 +206,9 @@ struct pupil_pt {
     std::vector<DevEmitter> h_emit_areas;  // host sources of in-place emitter updates
     std::vector<float> h_emit_cdf;
     std::vector<uint32_t> h_emit_guide;
-    // flattened-BVH refits: per-instance moved flags and the node-box scratch
-    uint8_t *d_moved = nullptr;
-    std::vector<uint8_t> h_moved;
-    float *refit_box = nullptr;
     // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
-    // (those the instances point at), the shape of each instance, the two-level build's input
-    // (PUPIL_VERTS_REBUILD) and the event that orders a caller's stream before the copy
-    struct ShapeDev {
-        uint32_t kind = PUPIL_SHAPE_MESH, num_vertices = 0, num_faces = 0;
-        float *pos = nullptr, *nrm = nullptr, *tex = nullptr;
-        uint32_t *idx = nullptr;
-        // pupil_pt_snapshot_shape_vertices: the vertices from before an update (allocated on the
-        // first snapshot and kept), and whether the flow pass uses them
-        float *prev = nullptr;
-        bool prev_valid = false;
-    };
+    // and the event that orders a caller's stream before the copy
     std::vector<ShapeDev> shapes;
-    std::vector<uint32_t> inst_shape;
-    std::vector<TwoLevelShape> tl_shapes;
     hipEvent_t ev_verts = nullptr;
     // flow pass scratch (pupil_pt_motion_vectors), sized on first use: the ray list (2 float4
     // per pixel), the hit list, the previous instance transforms and their host staging copy;
@@ -299,8 +267,7 @@ struct pupil_pt {
         release_state();
         if (aov_scratch) (void)hipFree(aov_scratch);
         for (void *p : allocs) (void)hipFree(p);
-        free_lbvh(bvh);
-        free_two_level(tl);
+        accel.free();
         if (pixel_map) (void)hipFree(pixel_map);
         for (auto e : trace_events) (void)hipEventDestroy(e);
         if (ev_begin) (void)hipEventDestroy(ev_begin);
@@ -512,50 +479,12 @@ int ensure_state(pupil_pt *pt, size_t paths) {
     return PUPIL_OK;
 }
 
-// BVH4 node array the traversal walks (its size bounds the 32-bit node offsets, kMaxNodes4)
 // the engine's own stream waits for everything enqueued so far on the stream of the last
 // render (which itself waited for the renders before it on other streams)
 hipError_t order_after_renders(pupil_pt *pt) {
     if (!pt->rendered || pt->last_stream == pt->own_stream) return hipSuccess;
     hipError_t e = hipEventRecord(pt->ev_sync, pt->last_stream);
     return e == hipSuccess ? hipStreamWaitEvent(pt->own_stream, pt->ev_sync, 0) : e;
-}
-
-uint64_t nodes4_count(const pupil_pt *pt) {
-    return pt->two_level ? (pt->tl.world ? pt->tl.num_wnodes : pt->tl.num_nodes4) : pt->bvh.num_nodes4;
-}
-
-// DeviceScene::node_bound of the current BVH4 arrays (after every build and refit;
-// one 12-B read back, the traversal kernels take it by value).  Live nodes only: in the
-// two-level layouts the TLAS reserve [tlas_nodes, tlas_cap) is never written, and
-// whatever an earlier allocation left there must not loosen the bound of every ray.
-int refresh_node_bound(pupil_pt *pt) {
-    pt->sc.node_bound[0] = pt->sc.node_bound[1] = pt->sc.node_bound[2] = 0.f;
-    const uint64_t n = nodes4_count(pt);
-    {  // LDS-resident top of the tree (pt_scene.h top_nodes) for the world-mode two-level structure, whose
-       // braided TLAS every ray crosses first: -1.3 % per config-5 step; the flat trees of configs 3 / 4
-       // pay 1.1 % per launch for the per-visit branch and run the kernel without it
-       // (profiles/r05_top_nodes_bisect.txt; PUPIL_TOP_NODES=k forces k nodes, 0 off)
-        const char *e = std::getenv("PUPIL_TOP_NODES");
-        const uint32_t want = e ? (uint32_t)std::min<long>(kTopNodes, std::max(0L, std::atol(e)))
-                                : (pt->two_level && pt->tl.world ? kTopNodes : 0u);
-        uint64_t live = pt->sc.nodes4 ? n : 0;
-        if (pt->two_level) live = std::min<uint64_t>(live, pt->tl.tlas_nodes);
-        pt->sc.top_nodes = (uint32_t)std::min<uint64_t>(want, live);
-    }
-    if (!pt->sc.nodes4 || n == 0) return PUPIL_OK;
-    if (pt->two_level) {
-        const uint64_t tlas = std::min<uint64_t>(pt->tl.tlas_nodes, n), cap = std::min<uint64_t>(pt->tl.tlas_cap, n);
-        launch_node_bound(pt->sc.nodes4, tlas, pt->node_bound, pt->own_stream, true);
-        launch_node_bound(pt->sc.nodes4 + cap, n - cap, pt->node_bound, pt->own_stream, false);
-    } else {
-        launch_node_bound(pt->sc.nodes4, n, pt->node_bound, pt->own_stream, true);
-    }
-    uint32_t b[3];
-    HIP_TRY(hipMemcpyAsync(b, pt->node_bound, sizeof(b), hipMemcpyDeviceToHost, pt->own_stream));
-    HIP_TRY(hipStreamSynchronize(pt->own_stream));
-    for (int a = 0; a < 3; a++) std::memcpy(&pt->sc.node_bound[a], &b[a], 4);
-    return PUPIL_OK;
 }
 
 // Local pixel list of a rank: tiles t with t % world == rank, row-major tile
@@ -980,69 +909,191 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
     return PUPIL_OK;
 }
 
-// The flattened BVH after the instances in `changed` moved, were hidden or shown, or had their
-// shape's vertices replaced (attrs: their shading records are rewritten too): one refit in
-// place, or a rebuild with the masks applied after it (refit = false, PUPIL_FLAT_UPDATE=rebuild,
-// a tree without a level order).  The instance table on the device is already up to date.
-int flat_update(pupil_pt *pt, const std::vector<uint32_t> &changed, bool refit, bool attrs) {
-    BvhBuildInput bin{pt->num_prims, pt->d_prim_inst, pt->d_insts, pt->d_mats};
-    // the flags of the instances whose records are rewritten, and the node-box scratch
-    const auto refit_flags = [&](bool hidden_ones) -> int {
-        if (!pt->d_moved) HIP_TRY(pt->alloc(&pt->d_moved, pt->h_insts.size()));
-        if (!pt->refit_box) HIP_TRY(pt->alloc(&pt->refit_box, 6 * (size_t)std::max(1u, pt->bvh.num_nodes4)));
-        pt->h_moved.assign(pt->h_insts.size(), 0);
-        if (hidden_ones) {
-            for (size_t i = 0; i < pt->h_insts.size(); i++) pt->h_moved[i] = pt->h_insts[i].hidden ? 1 : 0;
-        } else {
-            for (uint32_t id : changed) pt->h_moved[id] = 1;
-        }
-        HIP_TRY(hipMemcpyAsync(pt->d_moved, pt->h_moved.data(), pt->h_moved.size(), hipMemcpyHostToDevice, pt->own_stream));
-        return PUPIL_OK;
-    };
-    // refit in place (PUPIL_FLAT_UPDATE=rebuild: full rebuild)
-    const char *fu = std::getenv("PUPIL_FLAT_UPDATE");
-    if (refit && !(fu && std::strcmp(fu, "rebuild") == 0)) {
-        if (const int rc = refit_flags(false)) return rc;
-        double rms = 0.0;
-        if (refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &rms) == 0) {
-            // deformed meshes: the shading records follow (refresh_node_bound synchronises the stream)
-            if (attrs) launch_refresh_attrs(bin, pt->bvh, pt->d_moved, pt->own_stream);
-            pt->totals.build_ms = rms;
-            return refresh_node_bound(pt);
+// ------------------------------------------------------------------ pupil_pt_create, step by step
+// (each returns an ABI code; create frees the engine when one fails)
+
+// shapes: validated, their arrays copied to engine-owned HBM
+int upload_shapes(pupil_pt *pt, const pupil_scene_desc *scene) {
+    std::vector<ShapeDev> &shapes = pt->shapes;
+    shapes.assign(scene->num_shapes, ShapeDev{});
+    for (uint32_t s = 0; s < scene->num_shapes; s++) {
+        const pupil_shape &sh = scene->shapes[s];
+        shapes[s].kind = sh.kind;
+        shapes[s].num_vertices = sh.num_vertices;
+        shapes[s].num_faces = sh.num_faces;
+        if (sh.kind == PUPIL_SHAPE_MESH) {
+            if (!sh.positions || !sh.indices || sh.num_faces == 0)
+                return fail(PUPIL_ERR_INVALID, "mesh without positions/indices");
+            for (size_t i = 0; i < 3 * (size_t)sh.num_faces; i++)
+                if (sh.indices[i] >= sh.num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
+            if (pt->upload(&shapes[s].pos, sh.positions, 3 * (size_t)sh.num_vertices) ||
+                (sh.normals && pt->upload(&shapes[s].nrm, sh.normals, 3 * (size_t)sh.num_vertices)) ||
+                (sh.texcoords && pt->upload(&shapes[s].tex, sh.texcoords, 2 * (size_t)sh.num_vertices)) ||
+                pt->upload(&shapes[s].idx, sh.indices, 3 * (size_t)sh.num_faces))
+                return fail(PUPIL_ERR_OOM, "mesh upload failed");
+        } else if (sh.kind != PUPIL_SHAPE_SPHERE) {
+            return fail(PUPIL_ERR_INVALID, "unknown shape kind");
         }
     }
-    BvhBuildOutput nb{};
-    double ms = 0.0;
-    const int brc = build_bvh_bounded(bin, nb, pt->leaf_size, pt->own_stream, &ms, 0);
-    if (brc != 0) {
-        free_lbvh(nb);
-        return fail(brc == -3 ? PUPIL_ERR_UNSUPPORTED : PUPIL_ERR_HIP,
-                    brc == -3 ? "BVH deeper than the traversal stacks hold" : "LBVH rebuild failed");
+    return PUPIL_OK;
+}
+
+// materials (optix_material.cpp:39-132 host precompute); their bitmap textures are uploaded here
+int convert_materials(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<DevMaterial> &mats) {
+    mats.resize(scene->num_materials);
+    for (uint32_t m = 0; m < scene->num_materials; m++) {
+        const pupil_material &src = scene->materials[m];
+        DevMaterial &d = mats[m];
+        std::memset(&d, 0, sizeof(d));
+        d.type = src.type <= 7u ? src.type : 0u;
+        d.twosided = src.twosided;
+        d.nonlinear = src.nonlinear;
+        if (d.type == PUPIL_MAT_DIELECTRIC || d.type == PUPIL_MAT_ROUGH_DIELECTRIC || d.type == PUPIL_MAT_PLASTIC ||
+            d.type == PUPIL_MAT_ROUGH_PLASTIC)
+            d.eta = src.int_ior / src.ext_ior;
+        if (d.type == PUPIL_MAT_PLASTIC || d.type == PUPIL_MAT_ROUGH_PLASTIC) {
+            const pupil_texture &dt = d.type == PUPIL_MAT_PLASTIC ? src.tex[0] : src.tex[1];
+            const pupil_texture &stx = d.type == PUPIL_MAT_PLASTIC ? src.tex[1] : src.tex[2];
+            const float diffuse_luminance = luminance(pixel_average(dt));
+            const float specular_luminance = luminance(pixel_average(stx));
+            d.specular_sampling_weight = specular_luminance / (specular_luminance + diffuse_luminance);
+            d.int_fdr = diffuse_reflectance(1.f / d.eta);
+        }
+        for (int k = 0; k < 4; k++)
+            if (const int rc = upload_texture(pt, src.tex[k], d.tex[k])) return rc;
     }
-    free_lbvh(pt->bvh);
-    pt->bvh = nb;
-    if (pt->refit_box) {  // sized for the old tree
-        pt->release(pt->refit_box);
-        pt->refit_box = nullptr;
+    if (mats.empty()) {  // keep a valid pointer for instances without material
+        DevMaterial d;
+        std::memset(&d, 0, sizeof(d));
+        mats.push_back(d);
     }
-    pt->sc.prims = nb.prims;
-    pt->sc.attrs = nb.attrs;
-    pt->sc.nodes4 = nb.nodes4;
-    pt->sc.root_link4 = nb.root_link4;
-    pt->totals.bvh_nodes = nb.num_nodes4;
-    pt->totals.bvh_depth = nb.depth4;
-    bool any_hidden = false;
-    for (const DevInstance &d : pt->h_insts) any_hidden = any_hidden || d.hidden != 0u;
-    if (any_hidden) {  // the build covered every instance: the masks go on like a refit's
-        if (const int rc = refit_flags(true)) return rc;
-        double hms = 0.0;
-        const int hrc = refit_bvh4(bin, pt->bvh, pt->d_moved, pt->refit_box, pt->own_stream, &hms, true);
-        if (hrc == -1) return fail(PUPIL_ERR_UNSUPPORTED, "hidden instances need the BVH4 level order");
-        if (hrc != 0) return fail(PUPIL_ERR_HIP, "applying the visibility masks failed");
-        ms += hms;
+    return PUPIL_OK;
+}
+
+// instances, the primitive -> instance table and the shading's lookup tables over it, uploaded
+// with the materials
+int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector<DevMaterial> &mats) {
+    std::vector<DevInstance> &insts = pt->h_insts;
+    insts.resize(scene->num_instances);
+    std::vector<uint32_t> prim_inst;
+    for (uint32_t i = 0; i < scene->num_instances; i++) {
+        const pupil_instance &src = scene->instances[i];
+        if (src.shape >= scene->num_shapes) return fail(PUPIL_ERR_INVALID, "instance shape out of range");
+        if (src.material >= mats.size()) return fail(PUPIL_ERR_INVALID, "instance material out of range");
+        const pupil_shape &sh = scene->shapes[src.shape];
+        DevInstance &d = insts[i];
+        std::memset(&d, 0, sizeof(d));
+        std::memcpy(d.to_world, src.to_world, sizeof(d.to_world));
+        std::memcpy(d.to_object, src.to_object, sizeof(d.to_object));
+        d.kind = sh.kind;
+        d.material = src.material;
+        d.prim_offset = (uint32_t)prim_inst.size();
+        d.emitter_offset = src.emitter_offset;
+        d.flip_normals = src.flip_normals;
+        d.flip_tex_coords = src.flip_tex_coords;
+        d.bin = (mats[src.material].type >= 1u && mats[src.material].type <= 7u) ? mats[src.material].type : 8u;
+        d.blas_root = kTraverseDone;
+        d.positions = pt->shapes[src.shape].pos;
+        d.normals = pt->shapes[src.shape].nrm;
+        d.texcoords = pt->shapes[src.shape].tex;
+        d.indices = pt->shapes[src.shape].idx;
+        const uint32_t nprim = sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
+        if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + nprim > scene->num_area_emitters)
+            return fail(PUPIL_ERR_INVALID, "emitter offset out of range");
+        prim_inst.insert(prim_inst.end(), nprim, i);
     }
-    pt->totals.build_ms = ms;
-    return refresh_node_bound(pt);
+    pt->num_prims = (uint32_t)prim_inst.size();
+    if (prim_inst.size() >= (1ull << 31)) return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives");
+    // the shading's prim -> instance lookup (pt_kernels.h inst_of_prim): instance starts and a
+    // guide table of at most ~8 K entries over the prim ids
+    std::vector<uint32_t> inst_first(insts.size() + 1);
+    for (size_t i = 0; i < insts.size(); i++) inst_first[i] = insts[i].prim_offset;
+    inst_first[insts.size()] = (uint32_t)prim_inst.size();
+    uint32_t guide_shift = 0;
+    while ((prim_inst.size() >> guide_shift) > 8192u) guide_shift++;
+    std::vector<uint32_t> inst_guide;
+    if (!prim_inst.empty()) {
+        const size_t nb = ((prim_inst.size() - 1) >> guide_shift) + 1;
+        inst_guide.resize(nb + 1);
+        for (size_t k = 0; k <= nb; k++)
+            inst_guide[k] = prim_inst[std::min(k << guide_shift, prim_inst.size() - 1)];
+    } else {
+        inst_guide.assign(2, 0u);
+    }
+    uint32_t *d_inst_first = nullptr, *d_inst_guide = nullptr;
+    if (pt->upload(&pt->d_insts, insts.data(), insts.size()) || pt->upload(&pt->d_mats, mats.data(), mats.size()) ||
+        pt->upload(&pt->d_prim_inst, prim_inst.data(), prim_inst.size()) ||
+        pt->upload(&d_inst_first, inst_first.data(), inst_first.size()) ||
+        pt->upload(&d_inst_guide, inst_guide.data(), inst_guide.size()))
+        return fail(PUPIL_ERR_OOM, "scene upload failed");
+    pt->num_mats = (uint32_t)mats.size();
+    DeviceScene &sc = pt->sc;
+    sc.num_prims = pt->num_prims;
+    sc.prim_inst = pt->d_prim_inst;
+    sc.inst_first = d_inst_first;
+    sc.inst_guide = d_inst_guide;
+    sc.inst_guide_shift = guide_shift;
+    sc.instances = pt->d_insts;
+    sc.materials = pt->d_mats;
+    return PUPIL_OK;
+}
+
+// the PUPIL_* knobs of the render schedule and their defaults; after the structure is built (the
+// ring budget is what is free then)
+void read_knobs(pupil_pt *pt) {
+    DeviceScene &sc = pt->sc;
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pt->device);
+    sc.num_cus = (uint32_t)std::max(1, cus);
+    // persistent BVH4 kernels: refill once 16 lanes are idle (r02 re-tune on the SAH tree:
+    // 16 / 12 beat 20 / 24 by ~0.7 % at N = 1 and the 8-way shard)
+    sc.trace_refill = 16;
+    if (const char *r = std::getenv("PUPIL_REFILL")) sc.trace_refill = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
+    if (const char *po = std::getenv("PUPIL_PRIMARY_ORDER")) pt->primary_interleave = std::strcmp(po, "path") != 0;
+    {  // one material bin in the whole scene: the material partition orders nothing (auto; =bins / =list force)
+        uint32_t bins = 0;
+        for (const DevInstance &d : pt->h_insts) bins |= 1u << d.bin;
+        pt->shade_list = (bins & (bins - 1u)) == 0u;
+        if (const char *sl = std::getenv("PUPIL_SHADE_LIST")) {
+            if (std::strcmp(sl, "bins") == 0) pt->shade_list = false;
+            if (std::strcmp(sl, "list") == 0) pt->shade_list = true;
+        }
+        sc.single_bin = pt->shade_list && bins && (bins & (bins - 1u)) == 0u ? (uint32_t)__builtin_ctz(bins) : 0u;
+        pt->bin_mask = bins | 1u;  // the material bins a traced path can land in, and the miss bin
+    }
+    if (const char *fr = std::getenv("PUPIL_FRESH_SHADE")) pt->fresh_shade = std::atoi(fr) != 0;
+    if (const char *a = std::getenv("PUPIL_AHEAD")) pt->ahead_mode = std::min(2, std::max(0, std::atoi(a)));
+    if (const char *k = std::getenv("PUPIL_PIPE")) pt->pipe_limit = (uint32_t)std::min(63, std::max(0, std::atoi(k)));
+    {  // ring budget: a quarter of the device memory free now (after the scene and its BVH)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        pt->pipe_budget = 0.25 * (double)free_b;
+    }
+    if (const char *g = std::getenv("PUPIL_PIPE_GB")) pt->pipe_budget = std::max(0.0, std::atof(g)) * 1e9;
+    if (const char *g = std::getenv("PUPIL_PIPE_PATHS")) pt->pipe_paths = std::max(1.0, std::atof(g));
+    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_PATHS")) pt->pipe_group_paths = std::max(1.0, std::atof(g));
+    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_MAX")) pt->pipe_group_max = (uint32_t)std::min(64, std::max(1, std::atoi(g)));
+    if (const char *g = std::getenv("PUPIL_PIPE_SPLIT")) pt->pipe_split = std::atoi(g) != 0;
+    if (const char *g = std::getenv("PUPIL_PIPE_RAMP")) pt->pipe_ramp = (uint32_t)std::max(0, std::atoi(g));
+    if (const char *g = std::getenv("PUPIL_FRAME_PATHS")) pt->frame_paths = std::max(0.0, std::atof(g));
+    sc.trace_node_min = 8;  // node phase ends below 8 active lanes (7 waves: 8 and 12 beat 4 by 1.5 %; 2 is slower)
+    if (const char *r = std::getenv("PUPIL_NODE_MIN")) sc.trace_node_min = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
+}
+
+// traversal overflow stacks, counters, events
+int alloc_workspace(pupil_pt *pt) {
+    pt->ovf_threads = trace_grid_blocks() * (uint32_t)kTraceBlock;
+    if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * kStackOvf) || pt->alloc(&pt->trace_counters, 32) ||
+        pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->q.counts, kCountSlots) || pt->alloc(&pt->q.work, kWorkSlots))
+        return fail(PUPIL_ERR_OOM, "workspace allocation failed");
+    if (hipMemset(pt->q.work, 0, kWorkSlots * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(pt->ray_cum, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
+        return fail(PUPIL_ERR_HIP, "workspace clear failed");
+    if (hipEventCreate(&pt->ev_begin) != hipSuccess || hipEventCreate(&pt->ev_end) != hipSuccess ||
+        hipEventCreateWithFlags(&pt->ev_sync, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&pt->ev_verts, hipEventDisableTiming) != hipSuccess)
+        return fail(PUPIL_ERR_HIP, "event creation failed");
+    return PUPIL_OK;
 }
 
 }  // namespace
@@ -1079,270 +1130,32 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     HIP_TRY(hipSetDevice(device));
     auto pt = new pupil_pt();
     pt->device = device;
-    auto cleanup = [&](int rc) {
-        delete pt;
-        return rc;
-    };
-    if (hipStreamCreateWithFlags(&pt->own_stream, hipStreamNonBlocking) != hipSuccess)
-        return cleanup(fail(PUPIL_ERR_HIP, "stream creation failed"));
     pt->width = scene->width;
     pt->height = scene->height;
     pt->max_depth = scene->max_depth ? scene->max_depth : 1;
-
-    // shapes
-    std::vector<pupil_pt::ShapeDev> &shapes = pt->shapes;
-    shapes.assign(scene->num_shapes, pupil_pt::ShapeDev{});
-    for (uint32_t s = 0; s < scene->num_shapes; s++) {
-        const pupil_shape &sh = scene->shapes[s];
-        shapes[s].kind = sh.kind;
-        shapes[s].num_vertices = sh.num_vertices;
-        shapes[s].num_faces = sh.num_faces;
-        if (sh.kind == PUPIL_SHAPE_MESH) {
-            if (!sh.positions || !sh.indices || sh.num_faces == 0)
-                return cleanup(fail(PUPIL_ERR_INVALID, "mesh without positions/indices"));
-            for (size_t i = 0; i < 3 * (size_t)sh.num_faces; i++)
-                if (sh.indices[i] >= sh.num_vertices) return cleanup(fail(PUPIL_ERR_INVALID, "index out of range"));
-            if (pt->upload(&shapes[s].pos, sh.positions, 3 * (size_t)sh.num_vertices) ||
-                (sh.normals && pt->upload(&shapes[s].nrm, sh.normals, 3 * (size_t)sh.num_vertices)) ||
-                (sh.texcoords && pt->upload(&shapes[s].tex, sh.texcoords, 2 * (size_t)sh.num_vertices)) ||
-                pt->upload(&shapes[s].idx, sh.indices, 3 * (size_t)sh.num_faces))
-                return cleanup(fail(PUPIL_ERR_OOM, "mesh upload failed"));
-        } else if (sh.kind != PUPIL_SHAPE_SPHERE) {
-            return cleanup(fail(PUPIL_ERR_INVALID, "unknown shape kind"));
-        }
+    std::memcpy(pt->sc.camera.s2c, scene->sample_to_camera, sizeof(pt->sc.camera.s2c));
+    std::memcpy(pt->sc.camera.c2w, scene->camera_to_world, sizeof(pt->sc.camera.c2w));
+    std::vector<DevMaterial> mats;
+    int rc = hipStreamCreateWithFlags(&pt->own_stream, hipStreamNonBlocking) == hipSuccess
+                 ? PUPIL_OK
+                 : fail(PUPIL_ERR_HIP, "stream creation failed");
+    if (!rc) rc = upload_shapes(pt, scene);
+    if (!rc) rc = convert_materials(pt, scene, mats);
+    if (!rc) rc = upload_tables(pt, scene, mats);
+    if (!rc) rc = upload_emitters(pt, scene);
+    if (!rc)
+        rc = pt->accel.build({pt->own_stream, pt->num_prims, pt->d_prim_inst, pt->d_insts, pt->d_mats, &pt->h_insts,
+                              &pt->sc, &pt->totals},
+                             scene, pt->shapes);
+    if (!rc) read_knobs(pt);
+    if (!rc) rc = alloc_workspace(pt);
+    if (!rc) rc = pt->accel.publish();
+    if (rc) {
+        delete pt;
+        return rc;
     }
-    // materials (optix_material.cpp:39-132 host precompute)
-    std::vector<DevMaterial> mats(scene->num_materials);
-    for (uint32_t m = 0; m < scene->num_materials; m++) {
-        const pupil_material &src = scene->materials[m];
-        DevMaterial &d = mats[m];
-        std::memset(&d, 0, sizeof(d));
-        d.type = src.type <= 7u ? src.type : 0u;
-        d.twosided = src.twosided;
-        d.nonlinear = src.nonlinear;
-        if (d.type == PUPIL_MAT_DIELECTRIC || d.type == PUPIL_MAT_ROUGH_DIELECTRIC || d.type == PUPIL_MAT_PLASTIC ||
-            d.type == PUPIL_MAT_ROUGH_PLASTIC)
-            d.eta = src.int_ior / src.ext_ior;
-        if (d.type == PUPIL_MAT_PLASTIC || d.type == PUPIL_MAT_ROUGH_PLASTIC) {
-            const pupil_texture &dt = d.type == PUPIL_MAT_PLASTIC ? src.tex[0] : src.tex[1];
-            const pupil_texture &stx = d.type == PUPIL_MAT_PLASTIC ? src.tex[1] : src.tex[2];
-            const float diffuse_luminance = luminance(pixel_average(dt));
-            const float specular_luminance = luminance(pixel_average(stx));
-            d.specular_sampling_weight = specular_luminance / (specular_luminance + diffuse_luminance);
-            d.int_fdr = diffuse_reflectance(1.f / d.eta);
-        }
-        for (int k = 0; k < 4; k++) {
-            int rc = upload_texture(pt, src.tex[k], d.tex[k]);
-            if (rc) return cleanup(rc);
-        }
-    }
-    if (mats.empty()) {  // keep a valid pointer for instances without material
-        DevMaterial d;
-        std::memset(&d, 0, sizeof(d));
-        mats.push_back(d);
-    }
-    // instances + primitive -> instance table
-    std::vector<DevInstance> insts(scene->num_instances);
-    std::vector<uint32_t> prim_inst;
-    for (uint32_t i = 0; i < scene->num_instances; i++) {
-        const pupil_instance &src = scene->instances[i];
-        if (src.shape >= scene->num_shapes) return cleanup(fail(PUPIL_ERR_INVALID, "instance shape out of range"));
-        if (src.material >= mats.size()) return cleanup(fail(PUPIL_ERR_INVALID, "instance material out of range"));
-        const pupil_shape &sh = scene->shapes[src.shape];
-        DevInstance &d = insts[i];
-        std::memset(&d, 0, sizeof(d));
-        std::memcpy(d.to_world, src.to_world, sizeof(d.to_world));
-        std::memcpy(d.to_object, src.to_object, sizeof(d.to_object));
-        d.kind = sh.kind;
-        d.material = src.material;
-        d.prim_offset = (uint32_t)prim_inst.size();
-        d.emitter_offset = src.emitter_offset;
-        d.flip_normals = src.flip_normals;
-        d.flip_tex_coords = src.flip_tex_coords;
-        d.bin = (mats[src.material].type >= 1u && mats[src.material].type <= 7u) ? mats[src.material].type : 8u;
-        d.blas_root = kTraverseDone;
-        d.positions = shapes[src.shape].pos;
-        d.normals = shapes[src.shape].nrm;
-        d.texcoords = shapes[src.shape].tex;
-        d.indices = shapes[src.shape].idx;
-        const uint32_t nprim = sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
-        if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + nprim > scene->num_area_emitters)
-            return cleanup(fail(PUPIL_ERR_INVALID, "emitter offset out of range"));
-        prim_inst.insert(prim_inst.end(), nprim, i);
-    }
-    pt->num_prims = (uint32_t)prim_inst.size();
-    if (prim_inst.size() >= (1ull << 31)) return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives"));
-    DevInstance *d_insts = nullptr;
-    DevMaterial *d_mats = nullptr;
-    uint32_t *d_prim_inst = nullptr;
-    // the shading's prim -> instance lookup (pt_kernels.h inst_of_prim): instance starts and a
-    // guide table of at most ~8 K entries over the prim ids
-    std::vector<uint32_t> inst_first(insts.size() + 1);
-    for (size_t i = 0; i < insts.size(); i++) inst_first[i] = insts[i].prim_offset;
-    inst_first[insts.size()] = (uint32_t)prim_inst.size();
-    uint32_t guide_shift = 0;
-    while ((prim_inst.size() >> guide_shift) > 8192u) guide_shift++;
-    std::vector<uint32_t> inst_guide;
-    if (!prim_inst.empty()) {
-        const size_t nb = ((prim_inst.size() - 1) >> guide_shift) + 1;
-        inst_guide.resize(nb + 1);
-        for (size_t k = 0; k <= nb; k++)
-            inst_guide[k] = prim_inst[std::min(k << guide_shift, prim_inst.size() - 1)];
-    } else {
-        inst_guide.assign(2, 0u);
-    }
-    uint32_t *d_inst_first = nullptr, *d_inst_guide = nullptr;
-    if (pt->upload(&d_insts, insts.data(), insts.size()) || pt->upload(&d_mats, mats.data(), mats.size()) ||
-        pt->upload(&d_prim_inst, prim_inst.data(), prim_inst.size()) ||
-        pt->upload(&d_inst_first, inst_first.data(), inst_first.size()) ||
-        pt->upload(&d_inst_guide, inst_guide.data(), inst_guide.size()))
-        return cleanup(fail(PUPIL_ERR_OOM, "scene upload failed"));
-    {
-        int rc = upload_emitters(pt, scene);
-        if (rc) return cleanup(rc);
-    }
-    pt->d_insts = d_insts;
-    pt->d_mats = d_mats;
-    pt->num_mats = (uint32_t)mats.size();
-    pt->d_prim_inst = d_prim_inst;
-    pt->leaf_size = 2u;  // with the 7-wave traversal: 2 beats 3 by 2 %, 1 and 4 are slower (config 4)
-    if (const char *ls = std::getenv("PUPIL_LEAF_SIZE")) pt->leaf_size = (uint32_t)std::min(8, std::max(1, std::atoi(ls)));
-    // Acceleration structure (replaces the GAS + IAS builds): one flattened BVH over
-    // world-space primitives (default: on config 5 it traces 1.08x faster than the
-    // two-level world mode), or a TLAS over per-instance BLASes (PUPIL_ACCEL=two_level,
-    // which bench.py selects for config 5: cheaper instance updates; automatic when
-    // the flattened primitive count would pass the flat build's 2^27 limit).  Both
-    // give bit-identical hits.
-    {
-        std::vector<uint32_t> uses(scene->num_shapes, 0), inst_shape(scene->num_instances);
-        uint64_t flat_prims = 0;
-        for (uint32_t i = 0; i < scene->num_instances; i++) {
-            inst_shape[i] = scene->instances[i].shape;
-            uses[inst_shape[i]]++;
-            const pupil_shape &sh = scene->shapes[inst_shape[i]];
-            flat_prims += sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
-        }
-        pt->inst_shape = inst_shape;
-        // leaf links hold 28-bit record slots, up to two per primitive (pt_scene.h kRecF4)
-        pt->two_level = flat_prims >= (1ull << 27);
-        if (const char *a = std::getenv("PUPIL_ACCEL")) {
-            if (std::strcmp(a, "flat") == 0) pt->two_level = false;
-            if (std::strcmp(a, "two_level") == 0) pt->two_level = true;
-        }
-        if (!pt->two_level && flat_prims >= (1ull << 27))
-            return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "flattened BVH limited to 2^27 primitives"));
-        if (pt->two_level) {
-            std::vector<TwoLevelShape> tls(scene->num_shapes);
-            for (uint32_t k = 0; k < scene->num_shapes; k++) {
-                const pupil_shape &sh = scene->shapes[k];
-                TwoLevelShape &t = tls[k];
-                t = TwoLevelShape{};
-                if (sh.kind != PUPIL_SHAPE_MESH || !uses[k]) continue;
-                t.num_faces = sh.num_faces;
-                t.num_vertices = sh.num_vertices;
-                t.positions = shapes[k].pos;
-                t.normals = shapes[k].nrm;
-                t.texcoords = shapes[k].tex;
-                t.indices = shapes[k].idx;
-                float vmax = 0.f;
-                for (size_t v = 0; v < 3 * (size_t)sh.num_vertices; v++) vmax = std::max(vmax, std::fabs(sh.positions[v]));
-                t.vmax = vmax;
-            }
-            pt->tl_shapes = tls;
-            const int trc = build_two_level(tls, inst_shape, insts, d_insts, d_mats, pt->leaf_size, pt->own_stream, pt->tl);
-            if (trc == -3) return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold"));
-            if (trc == -4) return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "two-level record slots beyond the 28-bit leaf links"));
-            if (trc != 0) return cleanup(fail(PUPIL_ERR_HIP, "two-level acceleration build failed"));
-            pt->build_ms = pt->tl.build_ms;
-        } else {
-            BvhBuildInput bin{pt->num_prims, d_prim_inst, d_insts, d_mats};
-            const int brc = build_bvh_bounded(bin, pt->bvh, pt->leaf_size, pt->own_stream, &pt->build_ms, 0);
-            if (brc == -3) return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "BVH deeper than the traversal stacks hold"));
-            if (brc != 0) return cleanup(fail(PUPIL_ERR_HIP, "LBVH build failed"));
-        }
-    }
-    pt->h_insts = insts;
-    DeviceScene &sc = pt->sc;
-    sc.num_prims = pt->num_prims;
-    if (pt->two_level) {
-        sc.two_level = 1;
-        sc.tl_world = pt->tl.world ? 1u : 0u;
-        sc.nodes4 = pt->tl.world ? pt->tl.wnodes : pt->tl.nodes4;
-        sc.prims = pt->tl.world ? pt->tl.wprims : pt->tl.prims;
-        sc.wprims = pt->tl.wprims;
-        sc.attrs = pt->tl.attrs;
-        sc.root_link4 = pt->tl.root_link4;
-    } else {
-        sc.prims = pt->bvh.prims;
-        sc.attrs = pt->bvh.attrs;
-        sc.nodes4 = pt->bvh.nodes4;
-        sc.root_link4 = pt->bvh.root_link4;
-    }
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pt->device);
-    sc.num_cus = (uint32_t)std::max(1, cus);
-    // persistent BVH4 kernels: refill once 16 lanes are idle (r02 re-tune on the SAH tree:
-    // 16 / 12 beat 20 / 24 by ~0.7 % at N = 1 and the 8-way shard)
-    sc.trace_refill = 16;
-    if (const char *r = std::getenv("PUPIL_REFILL")) sc.trace_refill = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
-    if (const char *po = std::getenv("PUPIL_PRIMARY_ORDER")) pt->primary_interleave = std::strcmp(po, "path") != 0;
-    {  // one material bin in the whole scene: the material partition orders nothing (auto; =bins / =list force)
-        uint32_t bins = 0;
-        for (const DevInstance &d : insts) bins |= 1u << d.bin;
-        pt->shade_list = (bins & (bins - 1u)) == 0u;
-        if (const char *sl = std::getenv("PUPIL_SHADE_LIST")) {
-            if (std::strcmp(sl, "bins") == 0) pt->shade_list = false;
-            if (std::strcmp(sl, "list") == 0) pt->shade_list = true;
-        }
-        sc.single_bin = pt->shade_list && bins && (bins & (bins - 1u)) == 0u ? (uint32_t)__builtin_ctz(bins) : 0u;
-        pt->bin_mask = bins | 1u;  // the material bins a traced path can land in, and the miss bin
-    }
-    if (const char *fr = std::getenv("PUPIL_FRESH_SHADE")) pt->fresh_shade = std::atoi(fr) != 0;
-    if (const char *a = std::getenv("PUPIL_AHEAD")) pt->ahead_mode = std::min(2, std::max(0, std::atoi(a)));
-    if (const char *k = std::getenv("PUPIL_PIPE")) pt->pipe_limit = (uint32_t)std::min(63, std::max(0, std::atoi(k)));
-    {  // ring budget: a quarter of the device memory free now (after the scene and its BVH)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        pt->pipe_budget = 0.25 * (double)free_b;
-    }
-    if (const char *g = std::getenv("PUPIL_PIPE_GB")) pt->pipe_budget = std::max(0.0, std::atof(g)) * 1e9;
-    if (const char *g = std::getenv("PUPIL_PIPE_PATHS")) pt->pipe_paths = std::max(1.0, std::atof(g));
-    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_PATHS")) pt->pipe_group_paths = std::max(1.0, std::atof(g));
-    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_MAX")) pt->pipe_group_max = (uint32_t)std::min(64, std::max(1, std::atoi(g)));
-    if (const char *g = std::getenv("PUPIL_PIPE_SPLIT")) pt->pipe_split = std::atoi(g) != 0;
-    if (const char *g = std::getenv("PUPIL_PIPE_RAMP")) pt->pipe_ramp = (uint32_t)std::max(0, std::atoi(g));
-    if (const char *g = std::getenv("PUPIL_FRAME_PATHS")) pt->frame_paths = std::max(0.0, std::atof(g));
-    sc.trace_node_min = 8;  // node phase ends below 8 active lanes (7 waves: 8 and 12 beat 4 by 1.5 %; 2 is slower)
-    if (const char *r = std::getenv("PUPIL_NODE_MIN")) sc.trace_node_min = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
-    if (nodes4_count(pt) > kMaxNodes4)
-        return cleanup(fail(PUPIL_ERR_UNSUPPORTED, "BVH4 larger than 2^26 nodes (32-bit node offsets)"));
-    sc.prim_inst = d_prim_inst;
-    sc.inst_first = d_inst_first;
-    sc.inst_guide = d_inst_guide;
-    sc.inst_guide_shift = guide_shift;
-    sc.instances = d_insts;
-    sc.materials = d_mats;
-    std::memcpy(sc.camera.s2c, scene->sample_to_camera, sizeof(sc.camera.s2c));
-    std::memcpy(sc.camera.c2w, scene->camera_to_world, sizeof(sc.camera.c2w));
-    // traversal overflow stacks, counters, events
-    pt->ovf_threads = trace_grid_blocks() * (uint32_t)kTraceBlock;
-    if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * kStackOvf) || pt->alloc(&pt->trace_counters, 32) ||
-        pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->node_bound, 3) || pt->alloc(&pt->q.counts, kCountSlots) ||
-        pt->alloc(&pt->q.work, kWorkSlots))
-        return cleanup(fail(PUPIL_ERR_OOM, "workspace allocation failed"));
-    if (hipMemset(pt->q.work, 0, kWorkSlots * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(pt->ray_cum, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
-        return cleanup(fail(PUPIL_ERR_HIP, "workspace clear failed"));
-    if (hipEventCreate(&pt->ev_begin) != hipSuccess || hipEventCreate(&pt->ev_end) != hipSuccess ||
-        hipEventCreateWithFlags(&pt->ev_sync, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&pt->ev_verts, hipEventDisableTiming) != hipSuccess)
-        return cleanup(fail(PUPIL_ERR_HIP, "event creation failed"));
-    if (refresh_node_bound(pt) != PUPIL_OK) return cleanup(PUPIL_ERR_HIP);
-    pt->totals.bvh_nodes = pt->two_level ? two_level_nodes(pt->tl) : pt->bvh.num_nodes4;
-    pt->totals.two_level = pt->two_level ? 1u : 0u;
-    pt->totals.bvh_depth = pt->two_level ? pt->tl.tlas_depth + pt->tl.blas_depth : pt->bvh.depth4;
     pt->totals.bvh_prims = pt->num_prims;
-    pt->totals.build_ms = pt->build_ms;
+    pt->totals.build_ms = pt->accel.ms;
     *out = pt;
     return PUPIL_OK;
 }
@@ -1393,13 +1206,13 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
         if (to_world) {
             std::memcpy(d.to_world, to_world + 12 * (size_t)k, sizeof(d.to_world));
             std::memcpy(d.to_object, to_object + 12 * (size_t)k, sizeof(d.to_object));
-            if (pt->two_level) refresh_instance_margins(d);  // they depend on the transform
+            if (pt->accel.two_level) refresh_instance_margins(d);  // they depend on the transform
         }
         if (visibility_mask) d.hidden = (visibility_mask[k] & 0xFFu) == 0u ? 1u : 0u;
         if (std::find(changed.begin(), changed.end(), id) == changed.end()) changed.push_back(id);
     }
     // the device copies (pt_scene.h device_instance: a hidden sphere's to_object is NaN there);
-    // `staged` outlives the copies (the stream is synchronised below)
+    // `staged` outlives the copies (the structure update synchronises the stream)
     std::vector<DevInstance> staged;
     staged.reserve(changed.size());
     for (uint32_t id : changed) {
@@ -1407,47 +1220,28 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
         HIP_TRY(hipMemcpyAsync(pt->d_insts + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
                                pt->own_stream));
     }
-    pt->refits++;
-    if (pt->two_level) {
-        const auto t0 = std::chrono::steady_clock::now();
-        // world mode refits the TLAS like the reference's IAS update (PUPIL_TL_UPDATE=rebuild: full build)
-        const char *um = std::getenv("PUPIL_TL_UPDATE");
-        const bool refit = !(um && std::strcmp(um, "rebuild") == 0);
-        const int trc = rebuild_tlas(pt->tl, pt->h_insts, pt->d_insts, changed, pt->own_stream, refit);
-        if (trc == -3) return fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold");
-        if (trc != 0) return fail(PUPIL_ERR_HIP, "TLAS rebuild failed");
-        pt->sc.root_link4 = pt->tl.root_link4;
-        if (const int rc = refresh_node_bound(pt)) return rc;
-        pt->totals.bvh_nodes = two_level_nodes(pt->tl);
-        pt->totals.bvh_depth = pt->tl.tlas_depth + pt->tl.blas_depth;
-        pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return PUPIL_OK;
-    }
-    return flat_update(pt, changed, true, false);
+    pt->accel.refits++;  // once the tables have changed, before the structure follows: a failed update counts
+    if (const int rc = pt->accel.update_instances(changed)) return rc;
+    pt->totals.build_ms = pt->accel.ms;
+    return PUPIL_OK;
 }
 
 // Geometry-AS update (OPTIX_BUILD_OPERATION_UPDATE next to the instance-AS update above): the
 // vertices of one mesh shape are replaced and every structure derived from them follows in
-// place.  Flattened BVH: the shape's instances are flagged moved, refit_bvh4 rewrites their world
-// records (a hidden instance's stay NaN) and refits every node, launch_refresh_attrs rewrites
-// their shading records.  Two-level: update_shape_blas rewrites the object-space BLAS records,
-// refits the BLAS and refreshes its shading records, the instances get the new vmax and margins,
-// and rebuild_tlas regenerates their world boxes, world records and world BLAS copies and refits
-// (world mode) or rebuilds (object mode) the TLAS.  PUPIL_VERTS_REBUILD builds everything anew
-// with the create-time builders and puts the masks back on.
+// place (SceneAccel::update_shape), or, with PUPIL_VERTS_REBUILD, is built anew.
 int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *positions, const float *normals,
                                    uint32_t flags, void *hip_stream) {
     if (!pt || !positions) return fail(PUPIL_ERR_INVALID, "null argument");
     if (shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "shape index out of range");
-    const pupil_pt::ShapeDev &sd = pt->shapes[shape];
+    const ShapeDev &sd = pt->shapes[shape];
     if (sd.kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
     if (normals && !sd.nrm) return fail(PUPIL_ERR_INVALID, "the shape was created without normals");
     if (flags & ~(PUPIL_VERTS_DEVICE | PUPIL_VERTS_REBUILD)) return fail(PUPIL_ERR_INVALID, "unknown flags");
     const bool device = (flags & PUPIL_VERTS_DEVICE) != 0u, rebuild = (flags & PUPIL_VERTS_REBUILD) != 0u;
     std::vector<uint32_t> changed;
     bool emissive = false;
-    for (uint32_t i = 0; i < (uint32_t)pt->inst_shape.size(); i++)
-        if (pt->inst_shape[i] == shape && pt->h_insts[i].kind == PUPIL_SHAPE_MESH) {
+    for (uint32_t i = 0; i < (uint32_t)pt->h_insts.size(); i++)
+        if (pt->accel.inst_shape[i] == shape && pt->h_insts[i].kind == PUPIL_SHAPE_MESH) {
             changed.push_back(i);
             emissive = emissive || pt->h_insts[i].emitter_offset >= 0;
         }
@@ -1465,66 +1259,16 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     HIP_TRY(hipMemcpyAsync(sd.pos, positions, bytes, kind, pt->own_stream));
     if (normals) HIP_TRY(hipMemcpyAsync(sd.nrm, normals, bytes, kind, pt->own_stream));
-    // From here the shape's arrays hold the new vertices.  The refit counter ticks only once the
-    // structure has followed; after a failure below the structure still bounds the OLD vertices,
-    // and the engine must not render until an update of this shape succeeds (the header says so).
+    // From here the shape's arrays hold the new vertices.  After a failure below the structure
+    // still bounds the OLD vertices, and the engine must not render until an update of this shape
+    // succeeds (the header says so).
     if (changed.empty()) {  // no instance shows the shape: only its arrays change
         HIP_TRY(hipStreamSynchronize(pt->own_stream));
-        pt->refits++;
-        return PUPIL_OK;
-    }
-    if (!pt->two_level) {
-        const int rc = flat_update(pt, changed, !rebuild, true);
-        if (rc == PUPIL_OK) {
-            pt->refits++;
-            pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return rc;
-    }
-    TwoLevelShape &ts = pt->tl_shapes[shape];
-    if (rebuild) {
-        // vmax as at create, from the engine's own device copy by a device reduction (the same
-        // maximum the host loop at create finds): host and device vertices take one path, and
-        // device vertices never come back to the host
-        float vmax = 0.f;
-        if (shape_abs_max(pt->tl, ts, &vmax, pt->own_stream) != 0) return fail(PUPIL_ERR_HIP, "vertex reduction failed");
-        ts.vmax = vmax;
-        std::vector<DevInstance> insts = pt->h_insts;  // build_two_level refills the two-level fields
-        TwoLevelAccel ntl{};
-        const int trc = build_two_level(pt->tl_shapes, pt->inst_shape, insts, pt->d_insts, pt->d_mats, pt->leaf_size,
-                                        pt->own_stream, ntl);
-        if (trc == -3) return fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold");
-        if (trc != 0) return fail(PUPIL_ERR_HIP, "two-level acceleration rebuild failed");
-        free_two_level(pt->tl);
-        pt->tl = ntl;
-        pt->h_insts = insts;
-        DeviceScene &sc = pt->sc;
-        sc.tl_world = pt->tl.world ? 1u : 0u;
-        sc.nodes4 = pt->tl.world ? pt->tl.wnodes : pt->tl.nodes4;
-        sc.prims = pt->tl.world ? pt->tl.wprims : pt->tl.prims;
-        sc.wprims = pt->tl.wprims;
-        sc.attrs = pt->tl.attrs;
     } else {
-        float vmax = 0.f;
-        if (update_shape_blas(pt->tl, shape, ts, &vmax, pt->own_stream) != 0)
-            return fail(PUPIL_ERR_HIP, "BLAS refit failed");
-        ts.vmax = vmax;
-        for (uint32_t id : changed) {
-            pt->h_insts[id].vmax = vmax;
-            refresh_instance_margins(pt->h_insts[id]);
-        }
-        const char *um = std::getenv("PUPIL_TL_UPDATE");
-        const bool refit = !(um && std::strcmp(um, "rebuild") == 0);
-        const int trc = rebuild_tlas(pt->tl, pt->h_insts, pt->d_insts, changed, pt->own_stream, refit);
-        if (trc == -3) return fail(PUPIL_ERR_UNSUPPORTED, "TLAS + BLAS deeper than the traversal stacks hold");
-        if (trc != 0) return fail(PUPIL_ERR_HIP, "TLAS rebuild failed");
+        if (const int rc = pt->accel.update_shape(shape, changed, rebuild)) return rc;
+        pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    pt->sc.root_link4 = pt->tl.root_link4;
-    if (const int rc = refresh_node_bound(pt)) return rc;
-    pt->totals.bvh_nodes = two_level_nodes(pt->tl);
-    pt->totals.bvh_depth = pt->tl.tlas_depth + pt->tl.blas_depth;
-    pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    pt->refits++;
+    pt->accel.refits++;  // only once the structure has followed: a failed update does not count
     return PUPIL_OK;
 }
 
@@ -1535,7 +1279,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
 int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
     if (shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "shape index out of range");
-    pupil_pt::ShapeDev &sd = pt->shapes[shape];
+    ShapeDev &sd = pt->shapes[shape];
     if (sd.kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
     HIP_TRY(hipSetDevice(pt->device));
     if (!pt->ev_snap) HIP_TRY(hipEventCreateWithFlags(&pt->ev_snap, hipEventDisableTiming));
@@ -1558,7 +1302,7 @@ int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape) {
 
 int pupil_pt_clear_vertex_snapshots(pupil_pt *pt) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
-    for (pupil_pt::ShapeDev &sd : pt->shapes) sd.prev_valid = false;
+    for (ShapeDev &sd : pt->shapes) sd.prev_valid = false;
     pt->snapshots = 0;  // the flow pass reads no table; the next snapshot uploads a new one
     return PUPIL_OK;
 }
@@ -1733,10 +1477,10 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     c.frames_in_flight = 0;  // frames started ahead of the next render (in groups: not yet accumulated)
     for (const auto &g : pt->pipe) c.frames_in_flight += g.frames - g.consumed;
     c.pipeline_slots = pt->pipe_slots;
-    c.tlas_sah_splits = pt->two_level ? pt->tl.sah_splits : 0u;
+    c.tlas_sah_splits = pt->accel.two_level ? pt->accel.tl.sah_splits : 0u;
     c.ring_bytes = pt->ring_bytes + sizeof(float) * (uint64_t)pt->aov_cap;
     c.ring_budget_bytes = (uint64_t)pt->pipe_budget;
-    c.accel_refits = pt->refits;
+    c.accel_refits = pt->accel.refits;
     for (const DevInstance &d : pt->h_insts) c.hidden_instances += d.hidden ? 1u : 0u;
     c.frame_launches = pt->frame_launches;
     for (int a = 0; a < 3; a++) c.node_bound[a] = pt->sc.node_bound[a];
@@ -1840,22 +1584,23 @@ void pupil_pt_destroy(pupil_pt *pt) { delete pt; }
 int pupil_pt_export_bvh4(pupil_pt *pt, uint32_t *num_nodes, void *nodes, uint32_t *num_records, float *records,
                          int32_t *root_link) {
     if (!pt || !num_nodes || !num_records || !root_link) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (pt->two_level) return fail(PUPIL_ERR_UNSUPPORTED, "only the flattened BVH4 is exported");
+    if (pt->accel.two_level) return fail(PUPIL_ERR_UNSUPPORTED, "only the flattened BVH4 is exported");
     HIP_TRY(hipSetDevice(pt->device));
-    const uint32_t nn = pt->bvh.num_nodes4, nr = pt->bvh.num_records;
+    const BvhBuildOutput &bvh = pt->accel.bvh;
+    const uint32_t nn = bvh.num_nodes4, nr = bvh.num_records;
     if (nodes || records) {
         if (*num_nodes < nn || *num_records < nr) return fail(PUPIL_ERR_INVALID, "output too small");
         HIP_TRY(hipDeviceSynchronize());
-        if (nodes && nn) HIP_TRY(hipMemcpy(nodes, pt->bvh.nodes4, sizeof(Bvh4Node) * nn, hipMemcpyDeviceToHost));
+        if (nodes && nn) HIP_TRY(hipMemcpy(nodes, bvh.nodes4, sizeof(Bvh4Node) * nn, hipMemcpyDeviceToHost));
         if (records && nr) {  // record slots as 12 floats each (the 4th float4 of a slot is unused)
             std::vector<float4> h((size_t)kRecF4 * nr);
-            HIP_TRY(hipMemcpy(h.data(), pt->bvh.prims, sizeof(float4) * h.size(), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(h.data(), bvh.prims, sizeof(float4) * h.size(), hipMemcpyDeviceToHost));
             for (size_t r = 0; r < nr; r++) std::memcpy(records + 12 * r, &h[kRecF4 * r], 3 * sizeof(float4));
         }
     }
     *num_nodes = nn;
     *num_records = nr;
-    *root_link = (int32_t)pt->bvh.root_link4;
+    *root_link = (int32_t)bvh.root_link4;
     return PUPIL_OK;
 }
 
@@ -1962,7 +1707,7 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
         if (!pt->flow_verts) HIP_TRY(pt->alloc(&pt->flow_verts, ni));
         pt->h_flow_verts.assign(ni, nullptr);
         for (size_t i = 0; i < ni; i++) {
-            const pupil_pt::ShapeDev &sd = pt->shapes[pt->inst_shape[i]];
+            const ShapeDev &sd = pt->shapes[pt->accel.inst_shape[i]];
             if (sd.kind == PUPIL_SHAPE_MESH && sd.prev_valid) pt->h_flow_verts[i] = sd.prev;
         }
         HIP_TRY(hipMemcpyAsync(pt->flow_verts, pt->h_flow_verts.data(), sizeof(const float *) * ni, hipMemcpyHostToDevice, s));
@@ -2056,17 +1801,17 @@ int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint3
 
 int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (!pt->two_level) return fail(PUPIL_ERR_UNSUPPORTED, "the flattened BVH has no TLAS reserve");
+    if (!pt->accel.two_level) return fail(PUPIL_ERR_UNSUPPORTED, "the flattened BVH has no TLAS reserve");
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
-    const uint64_t lo = pt->tl.tlas_nodes, hi = std::min<uint64_t>(pt->tl.tlas_cap, nodes4_count(pt));
+    const uint64_t lo = pt->accel.tl.tlas_nodes, hi = std::min<uint64_t>(pt->accel.tl.tlas_cap, pt->accel.nodes4_count());
     if (hi > lo) {
         std::vector<float> junk((hi - lo) * (sizeof(Bvh4Node) / sizeof(float)), value);
         HIP_TRY(hipMemcpyAsync((void *)(pt->sc.nodes4 + lo), junk.data(), sizeof(float) * junk.size(),
                                hipMemcpyHostToDevice, pt->own_stream));
         HIP_TRY(hipStreamSynchronize(pt->own_stream));
     }
-    return refresh_node_bound(pt);
+    return pt->accel.publish();
 }
 
 int pupil_debug_math(int device, uint32_t n, const float *x, const float *y2, float *out) {

@@ -1,0 +1,92 @@
+// pt_accel.h — SceneAccel, the one owner of the engine's acceleration structure (pt_accel.hip),
+// and what the engine's host code shares with it.
+#pragma once
+
+#include <string>
+
+#include "../../include/pupil_pt.h"
+#include "accel_two_level.h"
+
+namespace pupil {
+
+// the ABI code, with msg left for pupil_last_error (engine.hip)
+int fail(int code, const std::string &msg);
+
+#define HIP_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess)                                                                             \
+            return fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,                        \
+                        std::string(#expr) + ": " + hipGetErrorString(_e));                               \
+    } while (0)
+
+// a shape's engine-owned device arrays (those the instances point at)
+struct ShapeDev {
+    uint32_t kind = PUPIL_SHAPE_MESH, num_vertices = 0, num_faces = 0;
+    float *pos = nullptr, *nrm = nullptr, *tex = nullptr;
+    uint32_t *idx = nullptr;
+    // pupil_pt_snapshot_shape_vertices: the vertices from before an update (allocated on the
+    // first snapshot and kept), and whether the flow pass uses them
+    float *prev = nullptr;
+    bool prev_valid = false;
+};
+
+// Acceleration structure (replaces the GAS + IAS builds): one flattened BVH over world-space
+// primitives, or a TLAS over per-shape BLASes (accel_two_level.hip).  Both give bit-identical
+// hits.  Everything that builds, refits, rebuilds or frees it is here; publish() is the only
+// writer of the structure's fields of DeviceScene and of totals.bvh_nodes / bvh_depth /
+// two_level, and every update ends in it.
+struct SceneAccel {
+    // The engine's tables the structure is built over and publishes to, valid for the engine's
+    // life.  Before an update, insts / d_insts already hold the new transforms and masks, and
+    // the shapes' device arrays the new vertices.
+    struct Tables {
+        hipStream_t stream;  // the engine's own
+        uint32_t num_prims;
+        const uint32_t *d_prim_inst;
+        DevInstance *d_insts;
+        const DevMaterial *d_mats;
+        std::vector<DevInstance> *insts;
+        DeviceScene *sc;
+        pupil_pt_counters *totals;
+    };
+    // Chooses flat or two-level and builds it.  publish() is left to the end of create: the
+    // ring budget is read between the two, before the engine's first kernel launch.
+    int build(const Tables &tables, const pupil_scene_desc *scene, const std::vector<ShapeDev> &shapes);
+    // the instances in `changed` moved, were hidden or shown
+    int update_instances(const std::vector<uint32_t> &changed);
+    // the vertices of mesh shape `shape`, shown by the instances in `changed`, were replaced;
+    // rebuild: PUPIL_VERTS_REBUILD
+    int update_shape(uint32_t shape, const std::vector<uint32_t> &changed, bool rebuild);
+    int publish();
+    // BVH4 node array the traversal walks (its size bounds the 32-bit node offsets, kMaxNodes4)
+    uint64_t nodes4_count() const;
+    void free();
+
+    bool two_level = false;  // TLAS + per-shape BLAS instead of one flattened BVH
+    BvhBuildOutput bvh{};
+    TwoLevelAccel tl{};
+    std::vector<TwoLevelShape> tl_shapes;  // the two-level build's input (PUPIL_VERTS_REBUILD)
+    std::vector<uint32_t> inst_shape;      // shape of each instance
+    uint32_t leaf_size = 2;                // primitives per BVH leaf (PUPIL_LEAF_SIZE)
+    // build_ms, one rule: the structure's own time is `ms` -- the builder's timer at create and
+    // the refit's or rebuild's after a flattened update; the two-level updates have no timer, so
+    // an instance update takes the host clock around the TLAS update and publish().  The entry
+    // points report `ms`, except pupil_pt_update_shape_vertices, which reports the host clock
+    // around its whole call (vertex copies included) in every mode.
+    double ms = 0.0;
+    uint64_t refits = 0;  // accel_refits; ticked by the entry points, not here
+
+private:
+    int update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs);
+    int update_tlas(const std::vector<uint32_t> &changed);
+    int flag_instances(const std::vector<uint32_t> *changed, uint32_t nodes);
+    Tables t{};
+    // flattened-BVH refits: per-instance moved flags and the node-box scratch
+    uint8_t *d_moved = nullptr;
+    std::vector<uint8_t> h_moved;
+    float *refit_box = nullptr;
+    uint32_t *node_bound = nullptr;  // launch_node_bound's result (3 floats as bits)
+};
+
+}  // namespace pupil

@@ -169,7 +169,7 @@ struct DeviceScene {
     uint32_t trace_node_min;  // BVH4 kernels: node phase ends when fewer lanes need a node
     // nodes [0, top_nodes) are copied into each traversal block's LDS at launch and read from
     // there (the collapse emits the BVH4 breadth first: the root and the levels below it,
-    // which every ray visits); <= kTopNodes, 0 = off (refresh_node_bound)
+    // which every ray visits); <= kTopNodes, 0 = off (SceneAccel::publish)
     uint32_t top_nodes;
     // per axis, max over every BVH4 node of |o| + 512 s (launch_node_bound after each build
     // and refit): the slab test's rounding bound is then one value per ray (pt_traverse.h
