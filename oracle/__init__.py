@@ -51,6 +51,7 @@ def lib():
         L.oracle_rng_sequence.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p]
         L.oracle_camera_ray.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
         L.oracle_closest.argtypes = [vp, C.c_uint32, f32p, f32p, C.c_int]
+        L.oracle_trace.argtypes = [vp, C.c_uint32, f32p, C.c_uint32, f32p, C.c_int, C.c_int]
         L.oracle_bsdf.argtypes = [vp, C.c_uint32, C.c_float, C.c_float, f32p, f32p, C.c_uint32, f32p]
         L.oracle_emitter_sample.argtypes = [vp, C.c_uint32, f32p, f32p, C.c_float, C.c_float, f32p]
         L.oracle_emitter_sample.restype = C.c_int
@@ -125,10 +126,18 @@ class OracleScene:
         if rc != 0:
             raise ValueError("engine BVH4 arrays do not match this scene")
 
-    def closest(self, rays, brute_force=False):
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    def closest(self, rays, brute_force=False, any_hit=False):
+        """Closest hits (t, b1, b2, primitive id bits; t = -1 and id 0xFFFFFFFF on a miss) of rays
+        (n, 6) = o, d with the path tracer's window [0.001, 1e16], or (n, 8) = o, d, tmin, tmax.
+        any_hit: 1 / -1 in column 0 as pupil_pt_trace_rays reports it.  brute_force tests every
+        primitive instead of traversing the BVH."""
+        rays = np.ascontiguousarray(rays, np.float32)
+        stride = rays.shape[-1] if rays.ndim == 2 else 6
+        if stride not in (6, 8):
+            raise ValueError("rays are (n, 6) or (n, 8)")
+        rays = rays.reshape(-1, stride)
         out = np.zeros((len(rays), 4), np.float32)
-        lib().oracle_closest(self._h, len(rays), _fp(rays), _fp(out), int(brute_force))
+        lib().oracle_trace(self._h, len(rays), _fp(rays), stride, _fp(out), int(brute_force), int(any_hit))
         return out
 
     def bsdf(self, material, wo, wi_eval, seed, uv=(0.5, 0.5)):

@@ -1270,10 +1270,18 @@ struct Scene {
         return idx;
     }
 
+    // A ray whose direction component is below MakeRay's 1e-30 clamp and whose origin lies in the
+    // closed slab [lo, hi] of that axis stays in the slab over any reachable distance: the axis
+    // is skipped.  Its slab product would be 0 * -+1e30 = -+0 for the face the origin lies on and
+    // -huge for the other one, i.e. t_far = -+0 < tmin: a ray running in a face plane of the box
+    // would be culled although the box's primitives in that plane are hit (pt_trace.h box_entry).
+    // Every other ray takes the same arithmetic as before.
     static bool BoxHit(const Box &b, const Ray &r, float tmin, float tmax) {
         float tn = tmin, tf = tmax;
         const float o[3] = {r.o.x, r.o.y, r.o.z}, id[3] = {r.idir.x, r.idir.y, r.idir.z};
+        const float d[3] = {r.d.x, r.d.y, r.d.z};
         for (int k = 0; k < 3; k++) {
+            if (absf(d[k]) < 1e-30f && o[k] >= b.lo[k] && o[k] <= b.hi[k]) continue;
             float t0 = (b.lo[k] - o[k]) * id[k], t1 = (b.hi[k] - o[k]) * id[k];
             if (t0 > t1) std::swap(t0, t1);
             tn = std::max(tn, t0);
@@ -1844,22 +1852,28 @@ void oracle_camera_ray(oracle_scene *s, uint32_t pixel, uint32_t seed, float *o6
     o6[3] = dir.x, o6[4] = dir.y, o6[5] = dir.z;
 }
 
-// closest hits for n rays (o,d packed 6 floats); out: t, b1, b2, prim id bits (0xFFFFFFFF miss)
-void oracle_closest(oracle_scene *s, uint32_t n, const float *rays, float *out, int brute_force) {
+// closest / any hits for n rays of `stride` floats: 6 = o, d with the window [0.001, 1e16] of the
+// path tracer's rays, 8 = o, d, tmin, tmax.  out: t, b1, b2, prim id bits (0xFFFFFFFF miss);
+// any_hit: 1 / -1, 0, 0, 0xFFFFFFFF (the engine's pupil_pt_trace_rays layout).  brute_force tests
+// every primitive in id order instead of traversing the BVH.
+void oracle_trace(oracle_scene *s, uint32_t n, const float *rays, uint32_t stride, float *out, int brute_force,
+                  int any_hit) {
     auto &sc = *reinterpret_cast<oracle::Scene *>(s);
     using namespace oracle;
     for (uint32_t i = 0; i < n; i++) {
-        const Ray r = MakeRay(make_float3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]),
-                              make_float3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]));
+        const float *ri = rays + (size_t)stride * i;
+        const Ray r = MakeRay(make_float3(ri[0], ri[1], ri[2]), make_float3(ri[3], ri[4], ri[5]));
+        const float tmin = stride >= 8 ? ri[6] : 0.001f;
+        const float tmax0 = stride >= 8 ? ri[7] : 1e16f;
         unsigned int prim = 0xFFFFFFFFu;
         float t = -1.f, b1 = 0.f, b2 = 0.f;
         bool hit = false;
         if (brute_force) {
-            float tmax = 1e16f;
+            float tmax = tmax0;
             for (const Prim &p : sc.prims) {
                 float tt, u = 0.f, v = 0.f;
-                const bool h = p.sphere ? HitSphere(sc.instances[p.inst], r, 0.001f, tmax, tt)
-                                        : HitTriangle(r, p, 0.001f, tmax, tt, u, v);
+                const bool h = p.sphere ? HitSphere(sc.instances[p.inst], r, tmin, tmax, tt)
+                                        : HitTriangle(r, p, tmin, tmax, tt, u, v);
                 if (h && (tt < tmax || p.id < prim)) {
                     tmax = tt;
                     prim = p.id;
@@ -1867,17 +1881,26 @@ void oracle_closest(oracle_scene *s, uint32_t n, const float *rays, float *out, 
                     b1 = u;
                     b2 = v;
                     hit = true;
+                    if (any_hit) break;
                 }
             }
+        } else if (any_hit) {
+            hit = sc.Occluded(r, tmin, tmax0);
         } else {
-            hit = sc.Closest(r, 0.001f, 1e16f, prim, t, b1, b2);
+            hit = sc.Closest(r, tmin, tmax0, prim, t, b1, b2);
         }
+        if (any_hit) t = 1.f, b1 = b2 = 0.f, prim = 0xFFFFFFFFu;
         uint32_t bits = hit ? prim : 0xFFFFFFFFu;
         out[4 * i] = hit ? t : -1.f;
         out[4 * i + 1] = b1;
         out[4 * i + 2] = b2;
         std::memcpy(&out[4 * i + 3], &bits, 4);
     }
+}
+
+// closest hits for n rays (o,d packed 6 floats); out: t, b1, b2, prim id bits (0xFFFFFFFF miss)
+void oracle_closest(oracle_scene *s, uint32_t n, const float *rays, float *out, int brute_force) {
+    oracle_trace(s, n, rays, 6, out, brute_force, 0);
 }
 
 // one BSDF Sample + Eval on a material of the scene: out = wi(3), f(3), pdf, type, eval f(3), eval pdf

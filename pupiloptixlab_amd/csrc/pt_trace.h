@@ -125,10 +125,21 @@ PT_HD bool intersect_unit_sphere(const float *inv, vec3 o, vec3 d, float tmin, f
 constexpr float kBoxConservative = 1.0000004f;  // 1 + 2*gamma(3)
 
 // Slab test of one box; returns entry distance or +inf when missed.
+// An axis whose direction component is below ray_pre's 1e-30 clamp is skipped while the origin
+// lies in the closed slab [lo, hi]: its products would be 0 * -+1e30 = -+0 for the face the
+// origin lies on and -huge for the other, t_far = -+0 < tmin, and a ray running in a face plane
+// of the box would be culled.  Rays with components above the clamp take the same arithmetic as
+// before.  (The BVH4 kernels do not use this exact test: visit4 widens both planes by a slab
+// error proportional to |idir|, which keeps such a ray inside.)
 PT_HD float box_entry(const RayPre &r, vec3 lo, vec3 hi, float tmin, float tmax) {
-    const float tx0 = (lo.x - r.o.x) * r.idir.x, tx1 = (hi.x - r.o.x) * r.idir.x;
-    const float ty0 = (lo.y - r.o.y) * r.idir.y, ty1 = (hi.y - r.o.y) * r.idir.y;
-    const float tz0 = (lo.z - r.o.z) * r.idir.z, tz1 = (hi.z - r.o.z) * r.idir.z;
+    constexpr float kInf = __builtin_huge_valf();
+    const float tiny = 1e-30f;
+    const bool sx = fabs_(r.d.x) < tiny && r.o.x >= lo.x && r.o.x <= hi.x;
+    const bool sy = fabs_(r.d.y) < tiny && r.o.y >= lo.y && r.o.y <= hi.y;
+    const bool sz = fabs_(r.d.z) < tiny && r.o.z >= lo.z && r.o.z <= hi.z;
+    const float tx0 = sx ? -kInf : (lo.x - r.o.x) * r.idir.x, tx1 = sx ? kInf : (hi.x - r.o.x) * r.idir.x;
+    const float ty0 = sy ? -kInf : (lo.y - r.o.y) * r.idir.y, ty1 = sy ? kInf : (hi.y - r.o.y) * r.idir.y;
+    const float tz0 = sz ? -kInf : (lo.z - r.o.z) * r.idir.z, tz1 = sz ? kInf : (hi.z - r.o.z) * r.idir.z;
     const float tn = fmaxf(fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fminf(tz0, tz1)), tmin);
     float tf = fminf(fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1)), tmax);
     tf = tf * kBoxConservative;
