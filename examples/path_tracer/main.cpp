@@ -309,6 +309,16 @@ static bool HideFromEnv(Pupil::System &system) {
     return true;
 }
 
+// PUPIL_DEVICE_EMITTERS=1: the engine owns the area-emitter table and rebuilds it on the device
+// after updates of emissive shapes and instances (PTPass::SetDeviceEmitters)
+static bool DeviceEmittersFromEnv(Pupil::pt::PTPass &pass) {
+    const char *on = std::getenv("PUPIL_DEVICE_EMITTERS");
+    if (!on || !std::atoi(on)) return true;
+    if (pass.SetDeviceEmitters(true)) return true;
+    std::fprintf(stderr, "PUPIL_DEVICE_EMITTERS: the engine refused the mode\n");
+    return false;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene.xml> [frames=16] [out.exr|.hdr|.pfm] [device=0]\n", argv[0]);
@@ -333,7 +343,7 @@ int main(int argc, char **argv) {
         system->AddPass(pt_pass.get());
         if (!system->SetScene(argv[1])) {
             rc = 1;
-        } else if (!HideFromEnv(*system)) {
+        } else if (!HideFromEnv(*system) || !DeviceEmittersFromEnv(*pt_pass)) {
             rc = 2;
         } else if (const char *bench = std::getenv("PUPIL_BENCH")) {
             rc = Bench(*system, *pt_pass, bench);

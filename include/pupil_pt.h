@@ -374,9 +374,11 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
  * PUPIL_ERR_INVALID: pt or positions NULL, shape out of range or a PUPIL_SHAPE_SPHERE, normals
  * for a shape created without them, unknown flags.  If an instance of the shape is emissive
  * (emitter_offset >= 0) its area emitters must follow through pupil_pt_update_emitters, as after
- * a transform (pupil_world_set_mesh_vertices + pupil_world_get_desc produce them); the engine
- * cannot derive that table from device vertices, so PUPIL_VERTS_DEVICE on such a shape returns
- * PUPIL_ERR_UNSUPPORTED.  Ordered after every render enqueued so far; frames in flight are
+ * a transform (pupil_world_set_mesh_vertices + pupil_world_get_desc produce them); without the
+ * device-side emitter table the engine cannot derive that table from device vertices, so
+ * PUPIL_VERTS_DEVICE on such a shape returns PUPIL_ERR_UNSUPPORTED.  That applies only while
+ * pupil_pt_enable_device_emitters (below) is off: with it on, this call rebuilds the table itself
+ * after the refit, from host or device vertices alike, and PUPIL_VERTS_DEVICE is accepted.  Ordered after every render enqueued so far; frames in flight are
  * dropped; returns once the structure is updated.  accel_refits counts successful calls only.  If
  * the call fails after the argument checks (PUPIL_ERR_HIP / _OOM / _UNSUPPORTED from the refit or
  * the builders), the engine's vertex arrays already hold the new vertices while the acceleration
@@ -412,6 +414,52 @@ int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
 /* replaces the area-emitter table, selection CDF and env emitter (after an emissive instance moved);
  * rewritten in place on the engine's stream when their shapes are unchanged */
 int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
+/* Engine-owned area-emitter table.  The engine holds everything the table is derived from
+ * (vertices, indices, normals, to_world / to_object, each instance's emitter_offset), so with
+ * this mode on it rebuilds the table on the device instead of taking it from the host.  Opt-in;
+ * with the mode off every call behaves as it did before the mode existed.  No ABI bump: detect
+ * the symbols.
+ *
+ * pupil_pt_enable_device_emitters: `scene` is the description the engine renders now (the one of
+ * pupil_pt_create, or the latest given to pupil_pt_update_emitters); NULL switches the mode off.
+ * From it the engine takes one value per emissive instance, the select weight of its radiance
+ * texture (the reference's GetWeight, world/emitter.cpp:73-101; a bitmap is summed on the host,
+ * now, from the scene's texel pointer), builds its bookkeeping (per emitter its instance, per
+ * instance the weight) and runs one rebuild.  After it the table equals the one `scene` describes
+ * bit for bit, provided `scene` was produced by pupil_world_get_desc: a caller who filled
+ * select_probability by another rule than the reference's (weight = select weight x area,
+ * normalised over the area emitters, then divided by the emitter count with the env) gets the
+ * reference's rule from then on.  PUPIL_ERR_INVALID, with the mode and the table unchanged: pt
+ * NULL; the scene's instance count, area-emitter count or any emitter_offset differs from the
+ * engine's; an emissive mesh instance's emitter range is not its face count (a sphere's: one).
+ *
+ * While the mode is on, pupil_pt_update_shape_vertices on a shape with an emissive instance (host
+ * vertices, PUPIL_VERTS_DEVICE, either with PUPIL_VERTS_REBUILD) and
+ * pupil_pt_update_instances[_masked] that give an emissive instance a transform rebuild the table
+ * before they return; a call that changes visibility masks only leaves it alone (a hidden
+ * emitter stays in the table, above).  pupil_pt_update_emitters still replaces everything, the
+ * env included; the mode stays on if the new scene still matches the engine's counts and offsets
+ * (its radiance weights are taken anew), otherwise it goes off and pupil_last_error() says so
+ * while the call returns PUPIL_OK.
+ *
+ * The rebuild rewrites, in place, pos / nrm / area / select_probability of every triangle
+ * emitter (center / radius / area / select_probability of a sphere), the selection CDF and its
+ * guide table, and nothing else: counts, guide_bits, radiance textures, texcoords and the env
+ * emitter (whose select probability depends on the emitter count only) cannot change.  Every
+ * stage restates the host's operations in the host's order (pt_emitters.hip), so the result is
+ * bit-identical to pupil_world_get_desc + pupil_pt_update_emitters for the same vertices and
+ * transforms; to_object must be the inverse the world computes.  Precondition, as for the host
+ * path's guide table: the weights are finite and >= 0, so the CDF is non-decreasing.
+ *
+ * pupil_pt_refresh_emitters runs the rebuild now, on the engine's stream after every render
+ * enqueued so far, drops frames in flight and returns when the table is written
+ * (PUPIL_ERR_INVALID with the mode off): for callers who write the engine's arrays by other
+ * means, and for timing.  pupil_pt_device_emitters_info: whether the mode is on, rebuilds since
+ * create, and the host's time around the last one (as build_ms is taken); any out pointer may be
+ * NULL. */
+int pupil_pt_enable_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
+int pupil_pt_refresh_emitters(pupil_pt *pt);
+int pupil_pt_device_emitters_info(pupil_pt *pt, uint32_t *enabled, uint64_t *refreshes, double *last_ms);
 /* Asynchronous on hip_stream (a hipStream_t; NULL = the default null stream): the
  * output buffers are complete once work later enqueued on that stream runs.  Exception:
  * with max_depth > 64 the call synchronises hip_stream every 16 bounces to read the list
@@ -461,6 +509,15 @@ int pupil_debug_math(int device, uint32_t n, const float *x, const float *y2, fl
 /* the device's emitter pick (EmitterGroup::SelectOneEmiiter, render/emitter.h:110-135)
  * for n random numbers p: out[i] = area emitter index, -1 = env, -2 = none */
 int pupil_debug_select_emitter(pupil_pt *pt, uint32_t n, const float *p, int32_t *out);
+/* the device's area-emitter table, emitters [first, first + n): 24 floats each --
+ * select_probability, area, cdf, the type word's bits, pos[3][3], nrm[3][3], 0, 0.
+ * PUPIL_ERR_INVALID when the range is out of bounds.  Works with the device-side emitter mode
+ * on or off. */
+int pupil_debug_read_emitters(pupil_pt *pt, uint32_t first, uint32_t n, float *out);
+/* the CDF's guide table: *bits = guide_bits, guide = its 2^bits + 1 entries.  Call with guide =
+ * NULL for the count; a count of 0 means the table has none (fewer than two emitters, or
+ * PUPIL_EMITTER_SELECT=binary). */
+int pupil_debug_read_emitter_guide(pupil_pt *pt, uint32_t *bits, uint32_t *guide, uint32_t *inout_count);
 /* the device's env emitter on n inputs of 3 floats, from the shading point pos_nrm =
  * (position xyz, normal xyz); out: 8 floats per input.
  * mode 0: Emitter::SampleDirect (render/emitter/env.h:23-49, 70-79) with xi = (in.x, in.y),

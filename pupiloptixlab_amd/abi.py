@@ -133,6 +133,11 @@ SIGNATURES = {
     "pupil_pt_snapshot_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pupil_pt_clear_vertex_snapshots": (C.c_int, [C.c_void_p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
+    "pupil_pt_enable_device_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
+    "pupil_pt_refresh_emitters": (C.c_int, [C.c_void_p]),
+    "pupil_pt_device_emitters_info": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_debug_read_emitters": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p]),
+    "pupil_debug_read_emitter_guide": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
     "pupil_debug_fill_tlas_reserve": (C.c_int, [C.c_void_p, C.c_float]),
     "pupil_pt_render": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Launch), C.c_void_p]),
     "pupil_pt_stats": (C.c_int, [C.c_void_p, C.POINTER(Counters)]),

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "host/emitter_weight.h"
 #include "pt_accel.h"
 
 namespace {
@@ -206,6 +207,16 @@ struct pupil_pt {
     std::vector<DevEmitter> h_emit_areas;  // host sources of in-place emitter updates
     std::vector<float> h_emit_cdf;
     std::vector<uint32_t> h_emit_guide;
+    // device-side emitter table (pupil_pt_enable_device_emitters): while dev_emit, vertex and
+    // transform updates of emissive instances rebuild the table from the engine's own arrays
+    // (pt_emitters.hip).  Per emitter its instance, per instance the select weight of its
+    // radiance, and the rebuild's scratch (weights, select probabilities, the weight sum)
+    bool dev_emit = false;
+    uint32_t dev_emit_count = 0;  // emitters the arrays below were sized for
+    uint32_t *d_emit_inst = nullptr;
+    float *d_inst_weight = nullptr, *d_emit_weight = nullptr, *d_emit_select = nullptr, *d_emit_sum = nullptr;
+    uint64_t emit_refreshes = 0;
+    double emit_ms = 0.0;  // host clock around the last rebuild
     // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
     // and the event that orders a caller's stream before the copy
     std::vector<ShapeDev> shapes;
@@ -1096,6 +1107,94 @@ int alloc_workspace(pupil_pt *pt) {
     return PUPIL_OK;
 }
 
+// ------------------------------------------------------------------ device-side emitter table
+// What pupil_pt_enable_device_emitters takes from a scene: it must describe the engine's
+// instances and emitter ranges, and gives each emissive instance's select weight.  Fills
+// emit_inst (per emitter) and inst_weight (per instance); changes nothing of the engine.
+int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std::vector<uint32_t> &emit_inst,
+                          std::vector<float> &inst_weight) {
+    const uint32_t ni = (uint32_t)pt->h_insts.size(), ne = pt->sc.num_areas;
+    if (scene->num_instances != ni) return fail(PUPIL_ERR_INVALID, "the scene's instance count is not the engine's");
+    if (scene->num_area_emitters != ne) return fail(PUPIL_ERR_INVALID, "the scene's area emitter count is not the engine's");
+    if ((ni && !scene->instances) || (ne && !scene->area_emitters)) return fail(PUPIL_ERR_INVALID, "missing scene array");
+    emit_inst.assign(ne, 0u);
+    inst_weight.assign(ni, 0.f);
+    uint32_t next = 0;  // emitter ranges follow each other in instance order (World::Build)
+    for (uint32_t i = 0; i < ni; i++) {
+        const DevInstance &d = pt->h_insts[i];
+        if (scene->instances[i].emitter_offset != d.emitter_offset)
+            return fail(PUPIL_ERR_INVALID, "an instance's emitter_offset is not the engine's");
+        if (d.emitter_offset < 0) continue;
+        const uint32_t range = d.kind == PUPIL_SHAPE_MESH ? pt->shapes[pt->accel.inst_shape[i]].num_faces : 1u;
+        if ((uint32_t)d.emitter_offset != next || range > ne - next)
+            return fail(PUPIL_ERR_INVALID, "an emissive instance's emitter range is not its face count");
+        inst_weight[i] = Pupil::world::GetWeight(scene->area_emitters[next].radiance);
+        for (uint32_t k = 0; k < range; k++) emit_inst[next + k] = i;
+        next += range;
+    }
+    if (next != ne) return fail(PUPIL_ERR_INVALID, "the emitter ranges do not cover the emitter table");
+    return PUPIL_OK;
+}
+
+// validates `scene` against the engine, then uploads the bookkeeping (the engine's stream is idle
+// or ordered by the caller; the copies are synchronous)
+int device_emitter_setup(pupil_pt *pt, const pupil_scene_desc *scene) {
+    std::vector<uint32_t> emit_inst;
+    std::vector<float> inst_weight;
+    if (const int rc = device_emitter_tables(pt, scene, emit_inst, inst_weight)) return rc;
+    const uint32_t ne = pt->sc.num_areas;
+    if (!pt->d_emit_inst || pt->dev_emit_count != ne) {
+        for (void *p : {(void *)pt->d_emit_inst, (void *)pt->d_emit_weight, (void *)pt->d_emit_select}) pt->release(p);
+        pt->d_emit_inst = nullptr;
+        pt->d_emit_weight = pt->d_emit_select = nullptr;
+        if (pt->alloc(&pt->d_emit_inst, ne) || pt->alloc(&pt->d_emit_weight, ne) || pt->alloc(&pt->d_emit_select, ne))
+            return fail(PUPIL_ERR_OOM, "emitter bookkeeping allocation failed");
+        pt->dev_emit_count = ne;
+    }
+    if (!pt->d_inst_weight && (pt->alloc(&pt->d_inst_weight, inst_weight.size()) || pt->alloc(&pt->d_emit_sum, 1)))
+        return fail(PUPIL_ERR_OOM, "emitter bookkeeping allocation failed");
+    if (ne) HIP_TRY(hipMemcpy(pt->d_emit_inst, emit_inst.data(), sizeof(uint32_t) * ne, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pt->d_inst_weight, inst_weight.data(), sizeof(float) * inst_weight.size(), hipMemcpyHostToDevice));
+    return PUPIL_OK;
+}
+
+// the rebuild (pt_emitters.hip) on the engine's stream, which the caller has ordered after the
+// renders; returns when the table is written
+int rebuild_emitters(pupil_pt *pt) {
+    const auto t0 = std::chrono::steady_clock::now();
+    EmitterJob job{};
+    job.areas = pt->d_areas;
+    job.cdf = pt->d_cdf;
+    job.guide = pt->d_guide;
+    job.guide_bits = pt->sc.guide_bits;
+    job.count = pt->sc.num_areas;
+    job.emitter_num = pt->sc.num_areas + (pt->sc.has_env ? 1u : 0u);
+    job.instances = pt->d_insts;
+    job.emit_inst = pt->d_emit_inst;
+    job.inst_weight = pt->d_inst_weight;
+    job.weight = pt->d_emit_weight;
+    job.select = pt->d_emit_select;
+    job.sum = pt->d_emit_sum;
+    launch_emitter_rebuild(job, pt->own_stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    pt->emit_refreshes++;
+    pt->emit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+// pupil_pt_update_emitters replaced the table: the device-side mode stays on when the new scene
+// still describes the engine's emitter ranges (its radiance weights are taken anew), else it goes
+// off and pupil_last_error says so; the update itself has succeeded either way
+int keep_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
+    if (!pt->dev_emit) return PUPIL_OK;
+    if (device_emitter_setup(pt, scene) != PUPIL_OK) {
+        pt->dev_emit = false;
+        g_last_error = "device-side emitter table switched off: " + g_last_error;
+    }
+    return PUPIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1200,10 +1299,12 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
     pt->pipe_valid = false;             // frames in flight were traced against the old geometry
     std::vector<uint32_t> changed;
+    bool emitters_moved = false;  // device-side emitter table: a transform of an emissive instance
     for (uint32_t k = 0; k < n; k++) {
         const uint32_t id = ids[k];
         DevInstance &d = pt->h_insts[id];
         if (to_world) {
+            emitters_moved = emitters_moved || d.emitter_offset >= 0;
             std::memcpy(d.to_world, to_world + 12 * (size_t)k, sizeof(d.to_world));
             std::memcpy(d.to_object, to_object + 12 * (size_t)k, sizeof(d.to_object));
             if (pt->accel.two_level) refresh_instance_margins(d);  // they depend on the transform
@@ -1223,6 +1324,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     pt->accel.refits++;  // once the tables have changed, before the structure follows: a failed update counts
     if (const int rc = pt->accel.update_instances(changed)) return rc;
     pt->totals.build_ms = pt->accel.ms;
+    if (pt->dev_emit && emitters_moved) return rebuild_emitters(pt);
     return PUPIL_OK;
 }
 
@@ -1245,7 +1347,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
             changed.push_back(i);
             emissive = emissive || pt->h_insts[i].emitter_offset >= 0;
         }
-    if (device && emissive)
+    if (device && emissive && !pt->dev_emit)
         return fail(PUPIL_ERR_UNSUPPORTED, "device vertices of an emissive shape: the emitter table needs the host path");
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
@@ -1269,6 +1371,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
         pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     pt->accel.refits++;  // only once the structure has followed: a failed update does not count
+    if (pt->dev_emit && emissive) return rebuild_emitters(pt);
     return PUPIL_OK;
 }
 
@@ -1351,11 +1454,51 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
                 HIP_TRY(hipMemcpyAsync(pt->d_guide, pt->h_emit_guide.data(), sizeof(uint32_t) * pt->h_emit_guide.size(),
                                        hipMemcpyHostToDevice, pt->own_stream));
             HIP_TRY(hipStreamSynchronize(pt->own_stream));
-            return PUPIL_OK;
+            return keep_device_emitters(pt, scene);
         }
     }
     HIP_TRY(hipStreamSynchronize(pt->own_stream));  // the old tables are freed below
-    return upload_emitters(pt, scene);
+    if (const int rc = upload_emitters(pt, scene)) return rc;
+    return keep_device_emitters(pt, scene);
+}
+
+int pupil_pt_enable_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (!scene) {
+        pt->dev_emit = false;
+        return PUPIL_OK;
+    }
+    HIP_TRY(hipSetDevice(pt->device));
+    // everything that can refuse the scene runs before anything of the engine changes
+    {
+        std::vector<uint32_t> emit_inst;
+        std::vector<float> inst_weight;
+        if (const int rc = device_emitter_tables(pt, scene, emit_inst, inst_weight)) return rc;
+    }
+    HIP_TRY(order_after_renders(pt));  // no render may still read the table
+    pt->pipe_valid = false;
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (const int rc = device_emitter_setup(pt, scene)) return rc;
+    if (const int rc = rebuild_emitters(pt)) return rc;
+    pt->dev_emit = true;
+    return PUPIL_OK;
+}
+
+int pupil_pt_refresh_emitters(pupil_pt *pt) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (!pt->dev_emit) return fail(PUPIL_ERR_INVALID, "the device-side emitter table is not enabled");
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(order_after_renders(pt));
+    pt->pipe_valid = false;  // frames in flight were shaded with the old table
+    return rebuild_emitters(pt);
+}
+
+int pupil_pt_device_emitters_info(pupil_pt *pt, uint32_t *enabled, uint64_t *refreshes, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (enabled) *enabled = pt->dev_emit ? 1u : 0u;
+    if (refreshes) *refreshes = pt->emit_refreshes;
+    if (last_ms) *last_ms = pt->emit_ms;
+    return PUPIL_OK;
 }
 
 int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_launch *launch, void *hip_stream) {
@@ -1748,6 +1891,48 @@ int pupil_debug_select_emitter(pupil_pt *pt, uint32_t n, const float *p, int32_t
     (void)hipFree(dp);
     if (dout) (void)hipFree(dout);
     HIP_TRY(err);
+    return PUPIL_OK;
+}
+
+int pupil_debug_read_emitters(pupil_pt *pt, uint32_t first, uint32_t n, float *out) {
+    if (!pt || (n && !out)) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (first > pt->sc.num_areas || n > pt->sc.num_areas - first) return fail(PUPIL_ERR_INVALID, "emitter range out of bounds");
+    if (n == 0) return PUPIL_OK;
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(order_after_renders(pt));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    std::vector<DevEmitter> areas(n);
+    std::vector<float> cdf(n);
+    HIP_TRY(hipMemcpy(areas.data(), pt->d_areas + first, sizeof(DevEmitter) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cdf.data(), pt->d_cdf + first, sizeof(float) * n, hipMemcpyDeviceToHost));
+    for (uint32_t e = 0; e < n; e++) {
+        const DevEmitter &d = areas[e];
+        float *o = out + 24 * (size_t)e;
+        o[0] = d.select_probability;
+        o[1] = d.area;
+        o[2] = cdf[e];
+        std::memcpy(o + 3, &d.type, sizeof(float));
+        for (int v = 0; v < 3; v++) {
+            o[4 + 3 * v] = d.pos[v].x, o[5 + 3 * v] = d.pos[v].y, o[6 + 3 * v] = d.pos[v].z;
+            o[13 + 3 * v] = d.nrm[v].x, o[14 + 3 * v] = d.nrm[v].y, o[15 + 3 * v] = d.nrm[v].z;
+        }
+        o[22] = o[23] = 0.f;
+    }
+    return PUPIL_OK;
+}
+
+int pupil_debug_read_emitter_guide(pupil_pt *pt, uint32_t *bits, uint32_t *guide, uint32_t *inout_count) {
+    if (!pt || !inout_count) return fail(PUPIL_ERR_INVALID, "null argument");
+    const uint32_t count = pt->d_guide ? (1u << pt->sc.guide_bits) + 1u : 0u;
+    if (bits) *bits = pt->sc.guide_bits;
+    if (guide && count) {
+        if (*inout_count < count) return fail(PUPIL_ERR_INVALID, "output too small");
+        HIP_TRY(hipSetDevice(pt->device));
+        HIP_TRY(order_after_renders(pt));
+        HIP_TRY(hipStreamSynchronize(pt->own_stream));
+        HIP_TRY(hipMemcpy(guide, pt->d_guide, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+    }
+    *inout_count = count;
     return PUPIL_OK;
 }
 

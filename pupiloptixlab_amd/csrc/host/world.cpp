@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../../include/pupil_pt.h"
+#include "emitter_weight.h"
 #include "hmath.h"
 #include "xml.h"
 
@@ -720,23 +721,7 @@ Texture FromDesc(const pupil_texture &d) {
     return t;
 }
 
-// emitter.cpp:73-101 GetWeight
-float GetWeight(const Texture &t) {
-    auto mx = [](float r, float g, float b) { return r > g ? (r > b ? r : b) : (g > b ? g : b); };
-    if (t.type == PUPIL_TEX_RGB) return mx(t.c0.x, t.c0.y, t.c0.z);
-    if (t.type == PUPIL_TEX_CHECKERBOARD) return (mx(t.c0.x, t.c0.y, t.c0.z) + mx(t.c1.x, t.c1.y, t.c1.z)) * 0.5f;
-    if (t.type == PUPIL_TEX_BITMAP && t.rgba) {
-        float w = 0.f;
-        const auto &d = *t.rgba;
-        for (size_t i = 0; i < t.width; i++)
-            for (size_t j = 0; j < t.height; j++) {
-                const size_t k = (i * t.width + j) * 4;
-                if (k + 2 < d.size()) w += mx(d[k], d[k + 1], d[k + 2]);
-            }
-        return w / (1.f * t.width * t.height);
-    }
-    return 0.f;
-}
+// GetWeight (emitter.cpp:73-101): emitter_weight.h, shared with the engine
 
 util::Float3 TransformPoint(util::Float3 p, const util::Mat4 &M) {  // transform.cpp:123-130
     const float *m = M.e;
@@ -865,7 +850,7 @@ public:
     // EmitterHelper::SetMeshAreaEmitter / SetSphereAreaEmitter (emitter.cpp:169-243)
     void AddAreaEmitter(const resource::ShapeInstance &ins, const resource::Shape &shape) {
         const pupil_texture radiance = ToDesc(ins.radiance);
-        const float select_weight = GetWeight(ins.radiance);
+        const float select_weight = GetWeight(radiance);
         if (shape.kind == PUPIL_SHAPE_SPHERE) {
             pupil_emitter e;
             std::memset(&e, 0, sizeof(e));

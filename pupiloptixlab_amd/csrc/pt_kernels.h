@@ -229,6 +229,23 @@ void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, co
 // a snapshot: the kernel and its arguments are then those of the rigid-only pass.
 void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays, const float4 *hits,
                          float2 *flow, hipStream_t s, const float *const *prev_verts = nullptr);
+// the area-emitter table rebuilt in place from the engine's own arrays (pt_emitters.hip): in every
+// DevEmitter pos, nrm, area and select_probability (a sphere: center, radius, area and
+// select_probability), the selection CDF and, unless null, its guide table
+struct EmitterJob {
+    DevEmitter *areas;
+    float *cdf;
+    uint32_t *guide;       // null = the table has none
+    uint32_t guide_bits;
+    uint32_t count;        // area emitters
+    uint32_t emitter_num;  // + 1 with an env emitter
+    const DevInstance *instances;
+    const uint32_t *emit_inst;  // per emitter: its instance
+    const float *inst_weight;   // per instance: GetWeight of its radiance (0 where not emissive)
+    float *weight, *select;     // scratch, one float per emitter
+    float *sum;                 // scratch, one float
+};
+void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

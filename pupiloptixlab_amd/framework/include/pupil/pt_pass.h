@@ -39,6 +39,11 @@ public:
     // its update (pupil_pt_snapshot_shape_vertices), so ComputeMotionVectors covers the
     // deformation, and forgets the snapshots on an OnRun that applies no shape update.
     void SetKeepPreviousVertices(bool on) noexcept;
+    // Engine-owned area-emitter table (pupil_pt_enable_device_emitters; default off): call after
+    // SetScene.  While on, the engine rebuilds the table on the device after every update of an
+    // emissive shape or instance, and OnRun's update handlers upload no host emitter table.
+    // SetScene switches it off (a new engine).  False: no scene, or the engine refused.
+    bool SetDeviceEmitters(bool on) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in
@@ -73,6 +78,7 @@ private:
     bool m_instances_moved = false;                 // by the last OnRun
     std::atomic_bool m_keep_prev_verts = false;     // SetKeepPreviousVertices
     bool m_snapshots = false;                       // the engine holds vertex snapshots
+    bool m_device_emitters = false;                 // SetDeviceEmitters
 };
 
 }  // namespace Pupil::pt

@@ -89,7 +89,8 @@ void PTPass::OnRun() noexcept {
                 else
                     emitters = emitters || emissive;
             }
-            if (emitters && pupil_pt_update_emitters(m_engine, &d) != PUPIL_OK)
+            // with the engine-owned emitter table on, the update calls above have rebuilt it
+            if (emitters && !m_device_emitters && pupil_pt_update_emitters(m_engine, &d) != PUPIL_OK)
                 Log("%s: emitter update failed: %s", name.c_str(), pupil_last_error());
         }
         m_frame_max_depth = (uint32_t)m_max_depth;
@@ -134,6 +135,7 @@ void PTPass::SetScene(world::World *world) noexcept {
         m_engine = nullptr;
     }
     m_snapshots = false;  // they went with the engine
+    m_device_emitters = false;  // and so did the engine-owned emitter table: a new engine
     int w = world->scene->sensor.film.w, h = world->scene->sensor.film.h;
     m_max_depth = world->scene->integrator.max_depth;
     m_accumulated_flag = true;
@@ -249,6 +251,18 @@ void PTPass::UpdateShape(uint32_t shape) noexcept {
 }
 
 void PTPass::SetKeepPreviousVertices(bool on) noexcept { m_keep_prev_verts = on; }
+
+bool PTPass::SetDeviceEmitters(bool on) noexcept {
+    if (!m_engine || !m_world) return false;
+    std::scoped_lock lock(m_world->Mutex());
+    if (pupil_pt_enable_device_emitters(m_engine, on ? &m_world->Desc() : nullptr) != PUPIL_OK) {
+        Log("%s: device emitters: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    m_device_emitters = on;
+    m_dirty = true;
+    return true;
+}
 
 bool PTPass::Stats(pupil_pt_counters &out) noexcept { return m_engine && pupil_pt_stats(m_engine, &out) == PUPIL_OK; }
 

@@ -140,7 +140,8 @@ class PTPass(Pass):
         """Several moved, hidden or shown instances with ONE refit of the acceleration
         structure: their transforms and visibility masks as the world holds them
         (pupil_pt_update_instances_masked, IASManager::UpdateInstance), then the emitter table
-        if any of them emits (a hidden emitter stays in it, as in the reference)."""
+        if any of them emits (a hidden emitter stays in it, as in the reference).  With
+        device_emitters on the engine has rebuilt the table itself and nothing is uploaded."""
         import numpy as np
 
         ids = sorted({int(i) for i in instances})
@@ -162,7 +163,7 @@ class PTPass(Pass):
                 self._prev_to_world = self._to_world.copy()
                 self._moved = True
             self._to_world[ids] = tw
-        if any(desc.instances[i].emitter_offset >= 0 for i in ids):
+        if not self.device_emitters and any(desc.instances[i].emitter_offset >= 0 for i in ids):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
 
@@ -185,7 +186,8 @@ class PTPass(Pass):
         """Deformed mesh applied now: the vertices `world` holds for `shape` (World.set_mesh_vertices)
         go into the engine with ONE refit over every instance of the shape
         (pupil_pt_update_shape_vertices; rebuild: PUPIL_VERTS_REBUILD), then the emitter table if
-        an instance of the shape emits; restarts accumulation.  keep_previous: the engine keeps
+        an instance of the shape emits (with device_emitters on the engine has rebuilt it itself
+        and nothing is uploaded); restarts accumulation.  keep_previous: the engine keeps
         the vertices from before, and motion_vectors() after the next render covers the
         deformation."""
         desc = world.desc()
@@ -196,8 +198,9 @@ class PTPass(Pass):
             self._pt, int(shape), C.cast(sh.positions, C.c_void_p) if sh is not None else None,
             C.cast(sh.normals, C.c_void_p) if sh is not None and sh.normals else None,
             abi.VERTS_REBUILD if rebuild else 0, None))
-        if any(desc.instances[i].shape == int(shape) and desc.instances[i].emitter_offset >= 0
-               for i in range(desc.num_instances)):
+        if not self.device_emitters and any(
+                desc.instances[i].shape == int(shape) and desc.instances[i].emitter_offset >= 0
+                for i in range(desc.num_instances)):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
 
@@ -206,8 +209,9 @@ class PTPass(Pass):
         """The same from device tensors (float32, contiguous, 3 per vertex, on the pass's device):
         the copy into the engine's arrays is ordered after the work enqueued so far on `stream`
         (default: the current stream) and never passes through the host.  A shape with an
-        emissive instance raises PUPIL_ERR_UNSUPPORTED: use update_shape.  keep_previous: as
-        update_shape's."""
+        emissive instance needs device_emitters on: the engine then rebuilds the emitter table from
+        the new vertices on the device; with it off such a shape raises PUPIL_ERR_UNSUPPORTED (use
+        update_shape).  keep_previous: as update_shape's."""
         torch = self._torch
         if not self._pt:
             raise abi.PupilError(abi.ERR_INVALID, "no scene set")
@@ -232,6 +236,71 @@ class PTPass(Pass):
             self._pt, int(shape), C.c_void_p(positions.data_ptr()),
             C.c_void_p(normals.data_ptr()) if normals is not None else None, flags, C.c_void_p(s.cuda_stream)))
         self.dirty = True
+
+    # ---- engine-owned emitter table (pupil_pt_enable_device_emitters)
+    @property
+    def device_emitters(self):
+        """Whether the engine owns the area-emitter table (asked of the engine: an emitter upload
+        whose counts no longer match switches the mode off)."""
+        return bool(self._pt) and self.device_emitters_info()["enabled"]
+
+    @device_emitters.setter
+    def device_emitters(self, v):
+        """True: the engine derives the area-emitter table from its own arrays after every
+        update of an emissive shape or instance (needs the World the scene came from, whose
+        current desc gives the radiance weights); False: the host uploads it, as without the
+        mode.  set_scene switches it off."""
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        if v:
+            if self._world is None:
+                raise abi.PupilError(abi.ERR_INVALID, "device_emitters needs a scene set from a World")
+            desc = self._world.desc()
+            check(self._lib.pupil_pt_enable_device_emitters(self._pt, C.byref(desc)))
+        else:
+            check(self._lib.pupil_pt_enable_device_emitters(self._pt, None))
+        self.dirty = True
+
+    def refresh_emitters(self):
+        """pupil_pt_refresh_emitters: the rebuild now (device_emitters on)."""
+        check(self._lib.pupil_pt_refresh_emitters(self._pt))
+        self.dirty = True
+
+    def device_emitters_info(self) -> dict:
+        en, n, ms = C.c_uint32(0), C.c_uint64(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_device_emitters_info(self._pt, C.byref(en), C.byref(n), C.byref(ms)))
+        return {"enabled": bool(en.value), "refreshes": n.value, "last_ms": ms.value}
+
+    def emitter_table(self):
+        """The engine's area-emitter table as numpy arrays (pupil_debug_read_emitters /
+        _read_emitter_guide): select_probability, area, cdf (n,), type (n,) uint32, pos and nrm
+        (n, 3, 3), guide_bits, and guide ((2^bits + 1,) uint32, or None when the table has none)."""
+        import numpy as np
+
+        cnt = C.c_uint32(0)
+        bits = C.c_uint32(0)
+        check(self._lib.pupil_debug_read_emitter_guide(self._pt, C.byref(bits), None, C.byref(cnt)))
+        guide = None
+        if cnt.value:
+            guide = np.zeros(cnt.value, np.uint32)
+            check(self._lib.pupil_debug_read_emitter_guide(self._pt, C.byref(bits),
+                                                           guide.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(cnt)))
+        # the count: an empty range is in bounds exactly up to it
+        in_bounds = lambda k: self._lib.pupil_debug_read_emitters(self._pt, k, 0, None) == abi.OK
+        lo, hi = 0, 1
+        while in_bounds(hi):
+            lo, hi = hi, 2 * hi
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if in_bounds(mid) else (lo, mid)
+        n = lo
+        raw = np.zeros((max(1, n), 24), np.float32)
+        if n:
+            check(self._lib.pupil_debug_read_emitters(self._pt, 0, n, raw.ctypes.data_as(C.POINTER(C.c_float))))
+        raw = raw[:n]
+        return {"select_probability": raw[:, 0].copy(), "area": raw[:, 1].copy(), "cdf": raw[:, 2].copy(),
+                "type": raw[:, 3].copy().view(np.uint32), "pos": raw[:, 4:13].reshape(n, 3, 3).copy(),
+                "nrm": raw[:, 13:22].reshape(n, 3, 3).copy(), "guide_bits": bits.value, "guide": guide}
 
     # ---- inspector knobs (pt_pass.cpp:225-237)
     @property
