@@ -460,6 +460,47 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
 int pupil_pt_enable_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
 int pupil_pt_refresh_emitters(pupil_pt *pt);
 int pupil_pt_device_emitters_info(pupil_pt *pt, uint32_t *enabled, uint64_t *refreshes, double *last_ms);
+/* Materials and textures updated in place.  The reference fixes them at SetScene
+ * (optix_material.cpp runs once per scene load, and its inspector edits no material): there is no
+ * reference event behind these entries.  No ABI bump: detect the symbols.
+ *
+ * pupil_pt_update_materials replaces materials ids[k] (indices into pupil_scene_desc.materials)
+ * by materials[k]; an id named twice takes its last entry.  Any field may change: type, twosided,
+ * the IORs, nonlinear and all four texture slots, a slot's kind and a bitmap's size included.  The
+ * host precompute is that of pupil_pt_create, so the next render equals, bit for bit, a render of
+ * an engine created with the new materials.  Everything is checked before anything changes
+ * (PUPIL_ERR_INVALID: pt NULL, ids / materials NULL with n > 0, an id out of range, an unknown
+ * texture type, a bitmap without texels or with a zero side; PUPIL_ERR_OOM: new texels could not
+ * be allocated): a refused call leaves the engine rendering exactly as before.  Ordered on the
+ * engine's stream after every render enqueued so far; frames in flight are dropped; returns once
+ * the copies have run.  Only the named DevMaterial entries are written.  A bitmap slot whose
+ * width * height is unchanged keeps its allocation; otherwise new texels are allocated and the
+ * old ones freed before the call returns, so repeated updates hold no more memory than the
+ * materials in use.  When a type changes, the material bin of every instance that uses the
+ * material follows (instance table and record slots), and with it the shading schedule
+ * (PUPIL_SHADE_LIST is honoured as at create).  No box or link of the acceleration structure
+ * depends on a material: it is not refitted and accel_refits stays.  Emitter radiance is not a
+ * material: pupil_pt_update_emitters changes it.
+ *
+ * pupil_pt_update_texture_device replaces the texels of bitmap slot `slot` (0..3) of `material`
+ * from device memory: width * height float4, row-major, the layout of pupil_texture::rgba.  The
+ * slot must already be a bitmap of exactly width x height (PUPIL_ERR_INVALID otherwise, the
+ * message says to set the size with pupil_pt_update_materials first; also for pt or rgba_device
+ * NULL, a material out of range, slot > 3).  As with PUPIL_VERTS_DEVICE the copy, device to
+ * device into the engine's own texels, is ordered after the work enqueued so far on hip_stream
+ * (a hipStream_t, NULL = the null stream) by an event: no device-wide sync, and the texels never
+ * pass through the host.  For a plastic or rough_plastic whose diffuse or specular reflectance
+ * slot is updated, specular_sampling_weight is recomputed on the device from the texels the two
+ * slots then hold, in the host's summation order, so it is bit for bit the weight
+ * pupil_pt_create would compute from them (pt_materials.hip); one serial pass over the bitmap.
+ * Frames in flight are dropped; returns once the engine's stream has passed the copy.
+ *
+ * pupil_pt_material_info: successful calls of either entry since create, and the host's time
+ * around the last one (as build_ms is taken); either out pointer may be NULL. */
+int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, const pupil_material *materials);
+int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slot, const void *rgba_device,
+                                   uint32_t width, uint32_t height, void *hip_stream);
+int pupil_pt_material_info(pupil_pt *pt, uint64_t *updates, double *last_ms);
 /* Asynchronous on hip_stream (a hipStream_t; NULL = the default null stream): the
  * output buffers are complete once work later enqueued on that stream runs.  Exception:
  * with max_depth > 64 the call synchronises hip_stream every 16 bounces to read the list
@@ -529,6 +570,9 @@ int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const floa
 /* the device's cuda::Texture::Sample (framework/cuda/texture.h:33-57) of texture `slot`
  * (0..3) of a material on n (u, v) pairs: out = rgb per input */
 int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out);
+/* the device's copy of a material, read back after everything enqueued so far: *type, and
+ * out = eta, int_fdr, specular_sampling_weight */
+int pupil_debug_read_material(pupil_pt *pt, uint32_t material, uint32_t *type, float out[3]);
 /* two-level structure: fills the never-written TLAS reserve [tlas_nodes, tlas_cap) of the
  * node array with nodes whose every float is `value`, then recomputes node_bound (test of
  * the bound's live-node ranges); PUPIL_ERR_UNSUPPORTED for the flattened BVH */
@@ -636,6 +680,15 @@ int pupil_world_get_instance_visibility(pupil_world *w, uint32_t instance, uint3
  * area emitters (world-space triangles, areas, select probabilities) that
  * pupil_pt_update_emitters takes after pupil_pt_update_shape_vertices. */
 int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *positions, const float *normals);
+/* A material replaced on the host side: `material` is an index into pupil_scene_desc.materials
+ * (the world flattens one material per instance, in instance order, so it is the material of
+ * desc instance `material`); the next pupil_world_get_desc carries *m there, and
+ * pupil_pt_update_materials takes it from that desc.  Bitmap texels are copied into the world, as
+ * by pupil_world_add_material: the caller's array is free once the call returns.  The table of
+ * pupil_world_add_material is not changed (instances added later take what they were given).
+ * PUPIL_ERR_INVALID, with the world unchanged: a null argument, a material out of range, an
+ * unknown texture type, a bitmap without texels or with a zero side. */
+int pupil_world_set_material(pupil_world *w, uint32_t material, const pupil_material *m);
 /* resolves emitters (EmitterHelper), camera matrices (CameraHelper) and fills desc;
  * pointers stay valid until the world is modified or destroyed */
 int pupil_world_get_desc(pupil_world *w, pupil_scene_desc *desc);

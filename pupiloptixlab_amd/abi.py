@@ -136,6 +136,11 @@ SIGNATURES = {
     "pupil_pt_enable_device_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_pt_refresh_emitters": (C.c_int, [C.c_void_p]),
     "pupil_pt_device_emitters_info": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_pt_update_materials": (C.c_int, [C.c_void_p, C.c_uint32, u32p, C.POINTER(Material)]),
+    "pupil_pt_update_texture_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                  C.c_uint32, C.c_void_p]),
+    "pupil_pt_material_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_debug_read_material": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p]),
     "pupil_debug_read_emitters": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p]),
     "pupil_debug_read_emitter_guide": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
     "pupil_debug_fill_tlas_reserve": (C.c_int, [C.c_void_p, C.c_float]),
@@ -168,6 +173,7 @@ SIGNATURES = {
     "pupil_world_set_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
     "pupil_world_set_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
+    "pupil_world_set_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
     "pupil_world_get_desc": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_world_destroy": (None, [C.c_void_p]),
     "pupil_denoiser_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]),

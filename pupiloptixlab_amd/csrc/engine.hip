@@ -45,14 +45,8 @@ float diffuse_reflectance(float eta) {
 }
 
 // GetPixelAverage (optix_material.cpp:15-42)
+// (the two halves, pt_kernels.h, are the ones the device restates after a texel update)
 vec3 pixel_average(const pupil_texture &t) {
-    if (t.type == PUPIL_TEX_RGB) return v3(t.c0[0], t.c0[1], t.c0[2]);
-    if (t.type == PUPIL_TEX_CHECKERBOARD) {
-        const float r = t.c0[0] + t.c1[0];
-        const float g = t.c0[1] + t.c1[1];
-        const float b = t.c0[2] + t.c1[2];
-        return v3(r, g, b) * 0.5f;
-    }
     if (t.type == PUPIL_TEX_BITMAP && t.rgba && t.width && t.height) {
         float r = 0.f, g = 0.f, b = 0.f;
         for (size_t i = 0, idx = 0; i < t.height; ++i)
@@ -62,10 +56,13 @@ vec3 pixel_average(const pupil_texture &t) {
                 b += t.rgba[idx++];
                 idx++;
             }
-        return v3(r, g, b) / (1.f * (float)t.height * (float)t.width);
+        return bitmap_average(v3(r, g, b), t.width, t.height);
     }
-    return v3(0.f);
+    return texture_const_average(t.type, t.c0, t.c1);
 }
+
+// material bin of a material type (0 is the miss bin, 8 holds every unknown type)
+uint32_t material_bin(uint32_t type) { return type >= 1u && type <= 7u ? type : 8u; }
 
 }  // namespace
 
@@ -198,6 +195,13 @@ struct pupil_pt {
     DevInstance *d_insts = nullptr;
     DevMaterial *d_mats = nullptr;
     uint32_t num_mats = 0;
+    // material updates (pupil_pt_update_materials / _update_texture_device): the host mirror of
+    // d_mats -- descriptors and texel pointers; after a device texel update of a plastic its
+    // specular_sampling_weight is stale here, and an entry is written to the device only when its
+    // own material is replaced -- the successful calls and the host clock around the last one
+    std::vector<DevMaterial> h_mats;
+    uint64_t mat_updates = 0;
+    double mat_ms = 0.0;
     uint32_t *d_prim_inst = nullptr;
     DevEmitter *d_areas = nullptr, *d_env = nullptr;
     float *d_cdf = nullptr;
@@ -218,7 +222,7 @@ struct pupil_pt {
     uint64_t emit_refreshes = 0;
     double emit_ms = 0.0;  // host clock around the last rebuild
     // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
-    // and the event that orders a caller's stream before the copy
+    // and the event that orders a caller's stream before a device-to-device copy (vertices, texels)
     std::vector<ShapeDev> shapes;
     hipEvent_t ev_verts = nullptr;
     // flow pass scratch (pupil_pt_motion_vectors), sized on first use: the ray list (2 float4
@@ -293,7 +297,8 @@ struct pupil_pt {
 
 namespace {
 
-int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
+// everything of a texture but its texels (data stays null); refuses what no engine can sample
+int texture_desc(const pupil_texture &t, DevTexture &d) {
     std::memset(&d, 0, sizeof(d));
     d.type = t.type;
     d.width = t.width;
@@ -309,11 +314,18 @@ int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
     }
     if (t.type == PUPIL_TEX_BITMAP) {
         if (!t.rgba || !t.width || !t.height) return fail(PUPIL_ERR_INVALID, "bitmap texture without texels");
+    } else if (t.type > PUPIL_TEX_CHECKERBOARD) {
+        return fail(PUPIL_ERR_INVALID, "unknown texture type");
+    }
+    return PUPIL_OK;
+}
+
+int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
+    if (const int rc = texture_desc(t, d)) return rc;
+    if (t.type == PUPIL_TEX_BITMAP) {
         float4 *texels = nullptr;
         HIP_TRY(pt->upload(&texels, reinterpret_cast<const float4 *>(t.rgba), (size_t)t.width * t.height));
         d.data = texels;
-    } else if (t.type > PUPIL_TEX_CHECKERBOARD) {
-        return fail(PUPIL_ERR_INVALID, "unknown texture type");
     }
     return PUPIL_OK;
 }
@@ -949,29 +961,42 @@ int upload_shapes(pupil_pt *pt, const pupil_scene_desc *scene) {
     return PUPIL_OK;
 }
 
-// materials (optix_material.cpp:39-132 host precompute); their bitmap textures are uploaded here
+// one material (optix_material.cpp:39-132 host precompute) with its texture descriptors; the
+// texels are placed by the caller (create: convert_materials; pupil_pt_update_materials).
+// Touches nothing of an engine: it is also the validation of an update
+int convert_material(const pupil_material &src, DevMaterial &d) {
+    std::memset(&d, 0, sizeof(d));
+    d.type = src.type <= 7u ? src.type : 0u;
+    d.twosided = src.twosided;
+    d.nonlinear = src.nonlinear;
+    if (d.type == PUPIL_MAT_DIELECTRIC || d.type == PUPIL_MAT_ROUGH_DIELECTRIC || d.type == PUPIL_MAT_PLASTIC ||
+        d.type == PUPIL_MAT_ROUGH_PLASTIC)
+        d.eta = src.int_ior / src.ext_ior;
+    for (int k = 0; k < 4; k++)
+        if (const int rc = texture_desc(src.tex[k], d.tex[k])) return rc;
+    if (d.type == PUPIL_MAT_PLASTIC || d.type == PUPIL_MAT_ROUGH_PLASTIC) {
+        const pupil_texture &dt = d.type == PUPIL_MAT_PLASTIC ? src.tex[0] : src.tex[1];
+        const pupil_texture &stx = d.type == PUPIL_MAT_PLASTIC ? src.tex[1] : src.tex[2];
+        d.specular_sampling_weight = specular_sampling_weight(pixel_average(dt), pixel_average(stx));
+        d.int_fdr = diffuse_reflectance(1.f / d.eta);
+    }
+    return PUPIL_OK;
+}
+
+// the scene's materials; their bitmap textures are uploaded here
 int convert_materials(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<DevMaterial> &mats) {
     mats.resize(scene->num_materials);
     for (uint32_t m = 0; m < scene->num_materials; m++) {
         const pupil_material &src = scene->materials[m];
         DevMaterial &d = mats[m];
-        std::memset(&d, 0, sizeof(d));
-        d.type = src.type <= 7u ? src.type : 0u;
-        d.twosided = src.twosided;
-        d.nonlinear = src.nonlinear;
-        if (d.type == PUPIL_MAT_DIELECTRIC || d.type == PUPIL_MAT_ROUGH_DIELECTRIC || d.type == PUPIL_MAT_PLASTIC ||
-            d.type == PUPIL_MAT_ROUGH_PLASTIC)
-            d.eta = src.int_ior / src.ext_ior;
-        if (d.type == PUPIL_MAT_PLASTIC || d.type == PUPIL_MAT_ROUGH_PLASTIC) {
-            const pupil_texture &dt = d.type == PUPIL_MAT_PLASTIC ? src.tex[0] : src.tex[1];
-            const pupil_texture &stx = d.type == PUPIL_MAT_PLASTIC ? src.tex[1] : src.tex[2];
-            const float diffuse_luminance = luminance(pixel_average(dt));
-            const float specular_luminance = luminance(pixel_average(stx));
-            d.specular_sampling_weight = specular_luminance / (specular_luminance + diffuse_luminance);
-            d.int_fdr = diffuse_reflectance(1.f / d.eta);
-        }
+        if (const int rc = convert_material(src, d)) return rc;
         for (int k = 0; k < 4; k++)
-            if (const int rc = upload_texture(pt, src.tex[k], d.tex[k])) return rc;
+            if (src.tex[k].type == PUPIL_TEX_BITMAP) {
+                float4 *texels = nullptr;
+                HIP_TRY(pt->upload(&texels, reinterpret_cast<const float4 *>(src.tex[k].rgba),
+                                   (size_t)src.tex[k].width * src.tex[k].height));
+                d.tex[k].data = texels;
+            }
     }
     if (mats.empty()) {  // keep a valid pointer for instances without material
         DevMaterial d;
@@ -1002,7 +1027,7 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
         d.emitter_offset = src.emitter_offset;
         d.flip_normals = src.flip_normals;
         d.flip_tex_coords = src.flip_tex_coords;
-        d.bin = (mats[src.material].type >= 1u && mats[src.material].type <= 7u) ? mats[src.material].type : 8u;
+        d.bin = material_bin(mats[src.material].type);
         d.blas_root = kTraverseDone;
         d.positions = pt->shapes[src.shape].pos;
         d.normals = pt->shapes[src.shape].nrm;
@@ -1038,6 +1063,7 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
         pt->upload(&d_inst_guide, inst_guide.data(), inst_guide.size()))
         return fail(PUPIL_ERR_OOM, "scene upload failed");
     pt->num_mats = (uint32_t)mats.size();
+    pt->h_mats = mats;
     DeviceScene &sc = pt->sc;
     sc.num_prims = pt->num_prims;
     sc.prim_inst = pt->d_prim_inst;
@@ -1047,6 +1073,28 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
     sc.instances = pt->d_insts;
     sc.materials = pt->d_mats;
     return PUPIL_OK;
+}
+
+// What the shading schedule takes from the instances' material bins: one bin in the whole scene
+// and the material partition orders nothing (shade_list: auto; PUPIL_SHADE_LIST=bins / =list
+// force), single_bin names it, bin_mask the bins a path can land in.  At create, and again when
+// pupil_pt_update_materials moved an instance to another bin
+void derive_bins(pupil_pt *pt) {
+    DeviceScene &sc = pt->sc;
+    const bool was_list = pt->shade_list;
+    const uint32_t was_single = sc.single_bin;
+    uint32_t bins = 0;
+    for (const DevInstance &d : pt->h_insts) bins |= 1u << d.bin;
+    pt->shade_list = (bins & (bins - 1u)) == 0u;
+    if (const char *sl = std::getenv("PUPIL_SHADE_LIST")) {
+        if (std::strcmp(sl, "bins") == 0) pt->shade_list = false;
+        if (std::strcmp(sl, "list") == 0) pt->shade_list = true;
+    }
+    sc.single_bin = pt->shade_list && bins && (bins & (bins - 1u)) == 0u ? (uint32_t)__builtin_ctz(bins) : 0u;
+    pt->bin_mask = bins | 1u;  // the material bins a traced path can land in, and the miss bin
+    // the ring's bin bytes are 0xFF for untraced paths only while the bins schedule keeps them so:
+    // after a change the next render clears the whole ring, as after an allocation
+    if (pt->shade_list != was_list || sc.single_bin != was_single) pt->ring_fresh = true;
 }
 
 // the PUPIL_* knobs of the render schedule and their defaults; after the structure is built (the
@@ -1061,17 +1109,7 @@ void read_knobs(pupil_pt *pt) {
     sc.trace_refill = 16;
     if (const char *r = std::getenv("PUPIL_REFILL")) sc.trace_refill = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
     if (const char *po = std::getenv("PUPIL_PRIMARY_ORDER")) pt->primary_interleave = std::strcmp(po, "path") != 0;
-    {  // one material bin in the whole scene: the material partition orders nothing (auto; =bins / =list force)
-        uint32_t bins = 0;
-        for (const DevInstance &d : pt->h_insts) bins |= 1u << d.bin;
-        pt->shade_list = (bins & (bins - 1u)) == 0u;
-        if (const char *sl = std::getenv("PUPIL_SHADE_LIST")) {
-            if (std::strcmp(sl, "bins") == 0) pt->shade_list = false;
-            if (std::strcmp(sl, "list") == 0) pt->shade_list = true;
-        }
-        sc.single_bin = pt->shade_list && bins && (bins & (bins - 1u)) == 0u ? (uint32_t)__builtin_ctz(bins) : 0u;
-        pt->bin_mask = bins | 1u;  // the material bins a traced path can land in, and the miss bin
-    }
+    derive_bins(pt);
     if (const char *fr = std::getenv("PUPIL_FRESH_SHADE")) pt->fresh_shade = std::atoi(fr) != 0;
     if (const char *a = std::getenv("PUPIL_AHEAD")) pt->ahead_mode = std::min(2, std::max(0, std::atoi(a)));
     if (const char *k = std::getenv("PUPIL_PIPE")) pt->pipe_limit = (uint32_t)std::min(63, std::max(0, std::atoi(k)));
@@ -1498,6 +1536,133 @@ int pupil_pt_device_emitters_info(pupil_pt *pt, uint32_t *enabled, uint64_t *ref
     if (enabled) *enabled = pt->dev_emit ? 1u : 0u;
     if (refreshes) *refreshes = pt->emit_refreshes;
     if (last_ms) *last_ms = pt->emit_ms;
+    return PUPIL_OK;
+}
+
+// Materials replaced in place: convert_material is the host precompute of create, so d_mats[ids[k]]
+// becomes what a fresh engine would hold.  Everything that can refuse the call runs first; then,
+// on the engine's stream after the renders enqueued so far, the texels (a bitmap slot of an
+// unchanged texel count keeps its allocation), the changed DevMaterial entries and -- when a type
+// changed -- the bins of the instances that use it, the records' bin words and the shading
+// schedule derived from the bins.  No box or link of the acceleration structure depends on a
+// material: accel_refits stays.  Returns once the stream has passed the copies, and frees the
+// replaced texels then.
+int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, const pupil_material *materials) {
+    if (!pt || (n && (!ids || !materials))) return fail(PUPIL_ERR_INVALID, "null argument");
+    std::vector<DevMaterial> conv(n);
+    for (uint32_t k = 0; k < n; k++) {
+        if (ids[k] >= pt->num_mats) return fail(PUPIL_ERR_INVALID, "material index out of range");
+        if (const int rc = convert_material(materials[k], conv[k])) return rc;
+    }
+    if (n == 0) return PUPIL_OK;
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> last(n, 1);  // an id named twice: its last material is the one that counts
+    for (uint32_t k = 0; k < n; k++)
+        for (uint32_t j = k + 1; j < n && last[k]; j++) last[k] = ids[j] != ids[k];
+    std::vector<void *> fresh, stale;
+    for (uint32_t k = 0; k < n; k++) {
+        if (!last[k]) continue;
+        for (int s = 0; s < 4; s++) {
+            DevTexture &nt = conv[k].tex[s];
+            const DevTexture &ot = pt->h_mats[ids[k]].tex[s];
+            const bool had = ot.type == PUPIL_TEX_BITMAP && ot.data;
+            const size_t count = (size_t)nt.width * nt.height;
+            if (nt.type == PUPIL_TEX_BITMAP && had && (size_t)ot.width * ot.height == count) {
+                nt.data = ot.data;
+                continue;
+            }
+            if (had) stale.push_back((void *)ot.data);
+            if (nt.type != PUPIL_TEX_BITMAP) continue;
+            float4 *texels = nullptr;
+            if (pt->alloc(&texels, count) != hipSuccess) {  // nothing of the engine has changed yet
+                (void)hipGetLastError();
+                for (void *p : fresh) pt->release(p);
+                return fail(PUPIL_ERR_OOM, "texel allocation failed");
+            }
+            fresh.push_back(texels);
+            nt.data = texels;
+        }
+    }
+    HIP_TRY(order_after_renders(pt));  // no render may still read the old materials
+    pt->pipe_valid = false;             // frames in flight were shaded with them
+    bool type_changed = false;
+    for (uint32_t k = 0; k < n; k++) {
+        if (!last[k]) continue;
+        for (int s = 0; s < 4; s++)
+            if (conv[k].tex[s].type == PUPIL_TEX_BITMAP)
+                HIP_TRY(hipMemcpyAsync((void *)conv[k].tex[s].data, materials[k].tex[s].rgba,
+                                       sizeof(float4) * (size_t)conv[k].tex[s].width * conv[k].tex[s].height,
+                                       hipMemcpyHostToDevice, pt->own_stream));
+        DevMaterial &h = pt->h_mats[ids[k]];
+        type_changed = type_changed || h.type != conv[k].type;
+        h = conv[k];
+        HIP_TRY(hipMemcpyAsync(pt->d_mats + ids[k], &h, sizeof(DevMaterial), hipMemcpyHostToDevice, pt->own_stream));
+    }
+    std::vector<DevInstance> staged;  // outlives the copies (synchronised below)
+    if (type_changed) {
+        staged.reserve(pt->h_insts.size());
+        for (size_t i = 0; i < pt->h_insts.size(); i++) {
+            DevInstance &d = pt->h_insts[i];
+            const uint32_t bin = material_bin(pt->h_mats[d.material].type);
+            if (bin == d.bin) continue;
+            d.bin = bin;
+            staged.push_back(device_instance(d));
+            HIP_TRY(hipMemcpyAsync(pt->d_insts + i, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
+                                   pt->own_stream));
+        }
+        if (!staged.empty()) {
+            pt->accel.update_bins();
+            HIP_TRY(hipGetLastError());
+            derive_bins(pt);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    for (void *p : stale) pt->release(p);  // the stream has passed them
+    pt->mat_updates++;
+    pt->mat_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+// The texels of one bitmap slot from device memory, ordered like PUPIL_VERTS_DEVICE: an event on
+// the caller's stream, the engine's stream waits for it, then the copy device to device.  A
+// plastic's specular_sampling_weight follows on the device (pt_materials.hip) when the slot is
+// one of the two it is derived from.
+int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slot, const void *rgba_device,
+                                   uint32_t width, uint32_t height, void *hip_stream) {
+    if (!pt || !rgba_device) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (material >= pt->num_mats || slot >= 4u) return fail(PUPIL_ERR_INVALID, "no such material texture");
+    const DevMaterial &m = pt->h_mats[material];
+    const DevTexture &t = m.tex[slot];
+    if (t.type != PUPIL_TEX_BITMAP || !t.data)
+        return fail(PUPIL_ERR_INVALID, "the slot holds no bitmap: make it one with pupil_pt_update_materials first");
+    if (t.width != width || t.height != height)
+        return fail(PUPIL_ERR_INVALID, "the slot's bitmap is " + std::to_string(t.width) + " x " + std::to_string(t.height) +
+                                           ": set the size with pupil_pt_update_materials first");
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(order_after_renders(pt));  // no render may still read the old texels
+    pt->pipe_valid = false;
+    HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));  // after the caller's work; no device-wide sync
+    HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    HIP_TRY(hipMemcpyAsync((void *)t.data, rgba_device, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice,
+                           pt->own_stream));
+    const uint32_t diffuse_slot = m.type == PUPIL_MAT_PLASTIC ? 0u : 1u;
+    if ((m.type == PUPIL_MAT_PLASTIC || m.type == PUPIL_MAT_ROUGH_PLASTIC) &&
+        (slot == diffuse_slot || slot == diffuse_slot + 1u)) {
+        launch_specular_weight(pt->d_mats + material, pt->own_stream);  // h_mats keeps the stale weight
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    pt->mat_updates++;
+    pt->mat_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+int pupil_pt_material_info(pupil_pt *pt, uint64_t *updates, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (updates) *updates = pt->mat_updates;
+    if (last_ms) *last_ms = pt->mat_ms;
     return PUPIL_OK;
 }
 
@@ -1982,6 +2147,21 @@ int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint3
     return debug_probe(pt, n, uv, 2, out, 3, [&](const float *din, float *dout) {
         launch_debug_tex(pt->sc, material, slot, din, dout, n, pt->own_stream);
     });
+}
+
+int pupil_debug_read_material(pupil_pt *pt, uint32_t material, uint32_t *type, float out[3]) {
+    if (!pt || !type || !out) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (material >= pt->num_mats) return fail(PUPIL_ERR_INVALID, "material index out of range");
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(order_after_renders(pt));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    DevMaterial d;
+    HIP_TRY(hipMemcpy(&d, pt->d_mats + material, sizeof(d), hipMemcpyDeviceToHost));
+    *type = d.type;
+    out[0] = d.eta;
+    out[1] = d.int_fdr;
+    out[2] = d.specular_sampling_weight;
+    return PUPIL_OK;
 }
 
 int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value) {

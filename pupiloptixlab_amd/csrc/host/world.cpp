@@ -1083,6 +1083,29 @@ int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *p
     return PUPIL_OK;
 }
 
+int pupil_world_set_material(pupil_world *w, uint32_t material, const pupil_material *m) {
+    if (!w || !m) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    if (material >= desc_instance_count(w)) return Pupil::werr(PUPIL_ERR_INVALID, "material out of range");
+    for (const pupil_texture &t : m->tex) {
+        if (t.type > PUPIL_TEX_CHECKERBOARD) return Pupil::werr(PUPIL_ERR_INVALID, "unknown texture type");
+        if (t.type == PUPIL_TEX_BITMAP && (!t.rgba || !t.width || !t.height))
+            return Pupil::werr(PUPIL_ERR_INVALID, "bitmap texture without texels");
+    }
+    // desc material k = the material of the k-th scene instance with a shape (World::Build)
+    uint32_t k = 0;
+    for (auto &ins : w->w.scene.instances) {
+        if (ins.shape < 0 || k++ != material) continue;
+        ins.mat.type = m->type;
+        ins.mat.twosided = m->twosided != 0;
+        ins.mat.int_ior = m->int_ior;
+        ins.mat.ext_ior = m->ext_ior;
+        ins.mat.nonlinear = m->nonlinear != 0;
+        for (int s = 0; s < 4; s++) ins.mat.tex[s] = Pupil::world::FromDesc(m->tex[s]);
+        return PUPIL_OK;
+    }
+    return Pupil::werr(PUPIL_ERR_INVALID, "material out of range");
+}
+
 int pupil_world_add_const_env(pupil_world *w, const float radiance[3]) {
     if (!w || !radiance) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
     Pupil::resource::SceneEmitter e;

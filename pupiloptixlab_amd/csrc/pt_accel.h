@@ -58,6 +58,9 @@ struct SceneAccel {
     // the vertices of mesh shape `shape`, shown by the instances in `changed`, were replaced;
     // rebuild: PUPIL_VERTS_REBUILD
     int update_shape(uint32_t shape, const std::vector<uint32_t> &changed, bool rebuild);
+    // the material bins of instances changed (insts / d_insts hold the new ones): the bin words of
+    // the record slots follow, enqueued on the stream.  No box or link changes: not a refit
+    void update_bins();
     int publish();
     // BVH4 node array the traversal walks (its size bounds the 32-bit node offsets, kMaxNodes4)
     uint64_t nodes4_count() const;

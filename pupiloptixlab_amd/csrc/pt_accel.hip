@@ -213,6 +213,17 @@ int SceneAccel::update_instances(const std::vector<uint32_t> &changed) {
     return PUPIL_OK;
 }
 
+// The records that carry a bin word: the flattened BVH's, or the two-level world records (world
+// mode: with one two-slot leaf per sphere appended; object mode traverses with the instances'
+// own bins, its world records are kept consistent all the same).
+void SceneAccel::update_bins() {
+    const std::vector<DevInstance> &insts = *t.insts;
+    uint64_t slots = two_level ? tl.num_wprims : bvh.num_records;
+    if (two_level && tl.world)
+        for (const DevInstance &d : insts) slots += d.kind == PUPIL_SHAPE_SPHERE ? 2u : 0u;
+    launch_record_bins(two_level ? tl.wprims : bvh.prims, (uint32_t)slots, t.d_insts, (uint32_t)insts.size(), t.stream);
+}
+
 // Flattened BVH: the shape's instances are flagged moved, refit_bvh4 rewrites their world records
 // (a hidden instance's stay NaN) and refits every node, launch_refresh_attrs rewrites their
 // shading records.  Two-level: update_shape_blas rewrites the object-space BLAS records, refits

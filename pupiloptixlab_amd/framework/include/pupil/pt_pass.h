@@ -44,6 +44,16 @@ public:
     // emissive shape or instance, and OnRun's update handlers upload no host emitter table.
     // SetScene switches it off (a new engine).  False: no scene, or the engine refused.
     bool SetDeviceEmitters(bool on) noexcept;
+    // Materials and textures in place (pupil_pt_update_materials / _update_texture_device), applied
+    // now: call them from the thread that runs OnRun, between OnRuns, like SetDeviceEmitters.
+    // UpdateMaterials: Desc().materials[i] of the scene's world for every i in ids
+    // (World::SetMaterial), in one engine call.  UpdateTextureDevice: width x height float4 texels
+    // in device memory for bitmap slot `slot` of `material`, copied after the work enqueued so far
+    // on `stream`.  Both restart accumulation at the next OnRun, as an instance update does.
+    // False: no scene, or the engine refused (the log has pupil_last_error).
+    bool UpdateMaterials(const std::vector<uint32_t> &ids) noexcept;
+    bool UpdateTextureDevice(uint32_t material, uint32_t slot, const void *rgba_device, uint32_t width, uint32_t height,
+                             hipStream_t stream) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in

@@ -80,6 +80,10 @@ public:
     // area emitters of emissive instances) and fires EWorldEvent::RenderInstanceUpdate with
     // InstanceUpdate::shape set; the pass refits once at the top of its next OnRun.
     bool SetMeshVertices(uint32_t shape, const float *positions, const float *normals = nullptr) noexcept;
+    // Replaces material `material` (index into Desc().materials: one per instance, in instance
+    // order) and refreshes Desc().  The reference has no event for a material edit and fires
+    // none: PTPass::UpdateMaterials hands the material to the engine.
+    bool SetMaterial(uint32_t material, const pupil_material &m) noexcept;
 
     pupil_world *handle() noexcept { return m_world; }
     // Flattened scene for pupil_pt_create (valid until the world changes); a thread

@@ -264,6 +264,39 @@ bool PTPass::SetDeviceEmitters(bool on) noexcept {
     return true;
 }
 
+bool PTPass::UpdateMaterials(const std::vector<uint32_t> &ids) noexcept {
+    if (!m_engine || !m_world) return false;
+    if (ids.empty()) return true;
+    std::scoped_lock lock(m_world->Mutex());
+    const pupil_scene_desc &d = m_world->Desc();
+    std::vector<pupil_material> mats;
+    mats.reserve(ids.size());
+    for (uint32_t id : ids) {
+        if (id >= d.num_materials) {
+            Log("%s: material update failed: material index out of range", name.c_str());
+            return false;
+        }
+        mats.push_back(d.materials[id]);
+    }
+    if (pupil_pt_update_materials(m_engine, (uint32_t)ids.size(), ids.data(), mats.data()) != PUPIL_OK) {
+        Log("%s: material update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    m_dirty = true;
+    return true;
+}
+
+bool PTPass::UpdateTextureDevice(uint32_t material, uint32_t slot, const void *rgba_device, uint32_t width,
+                                 uint32_t height, hipStream_t stream) noexcept {
+    if (!m_engine) return false;
+    if (pupil_pt_update_texture_device(m_engine, material, slot, rgba_device, width, height, stream) != PUPIL_OK) {
+        Log("%s: texture update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    m_dirty = true;
+    return true;
+}
+
 bool PTPass::Stats(pupil_pt_counters &out) noexcept { return m_engine && pupil_pt_stats(m_engine, &out) == PUPIL_OK; }
 
 void PTPass::BindingEventCallback() noexcept {

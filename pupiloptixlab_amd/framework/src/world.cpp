@@ -109,6 +109,19 @@ bool World::SetMeshVertices(uint32_t shape, const float *positions, const float 
     return true;
 }
 
+bool World::SetMaterial(uint32_t material, const pupil_material &m) noexcept {
+    std::scoped_lock lock(m_mutex);
+    if (!m_world || pupil_world_set_material(m_world, material, &m) != PUPIL_OK) {
+        Log("material update failed: %s", pupil_last_error());
+        return false;
+    }
+    if (pupil_world_get_desc(m_world, &m_desc) != PUPIL_OK) {
+        Log("scene description failed: %s", pupil_last_error());
+        return false;
+    }
+    return true;
+}
+
 // the caller holds Mutex() where another thread may edit the world
 uint32_t World::InstanceVisibility(uint32_t instance) noexcept {
     uint32_t mask = 1u;

@@ -237,6 +237,70 @@ class PTPass(Pass):
             C.c_void_p(normals.data_ptr()) if normals is not None else None, flags, C.c_void_p(s.cuda_stream)))
         self.dirty = True
 
+    # ---- materials and textures in place (pupil_pt_update_materials / _update_texture_device)
+    def update_material(self, world, material: int):
+        """Material `material` as `world` holds it now (World.set_material) goes into the engine;
+        restarts accumulation."""
+        self.update_materials(world, [material])
+
+    def update_materials(self, world, ids):
+        """Several materials in ONE call: desc().materials[i] of `world` for every i in ids.  Any
+        field may have changed, the type and the textures' kinds and sizes included; the
+        acceleration structure is not touched."""
+        import numpy as np
+
+        ids = sorted({int(i) for i in ids})
+        if not ids:
+            return
+        desc = world.desc()
+        for i in ids:
+            if not 0 <= i < desc.num_materials:
+                raise abi.PupilError(abi.ERR_INVALID, "material index out of range")
+        mats = (abi.Material * len(ids))()
+        for k, i in enumerate(ids):
+            C.memmove(C.byref(mats[k]), C.byref(desc.materials[i]), C.sizeof(abi.Material))
+        idv = np.array(ids, np.uint32)
+        check(self._lib.pupil_pt_update_materials(self._pt, len(ids), idv.ctypes.data_as(C.POINTER(C.c_uint32)), mats))
+        self.mark_dirty()
+
+    def update_texture_device(self, material: int, slot: int, tensor, stream=None):
+        """The texels of bitmap slot `slot` of `material` from a contiguous float32 tensor of shape
+        (h, w, 4) on the pass's device; the slot must already be an h x w bitmap
+        (update_material sets kinds and sizes).  The copy is ordered after the work enqueued so
+        far on `stream` (default: the current stream) and never passes through the host; a
+        plastic's sampling weight follows on the device.  Restarts accumulation."""
+        torch = self._torch
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        if not isinstance(tensor, torch.Tensor):
+            raise ValueError("update_texture_device needs a torch tensor")
+        if tensor.dim() != 3 or tensor.shape[2] != 4 or tensor.shape[0] == 0 or tensor.shape[1] == 0:
+            raise ValueError(f"update_texture_device needs an (h, w, 4) tensor, got {tuple(tensor.shape)}")
+        if not (tensor.is_cuda and tensor.dtype == torch.float32 and tensor.is_contiguous()):
+            raise ValueError("update_texture_device needs a contiguous float32 device tensor")
+        if tensor.device.index != self.device_index:  # the copy runs device to device on the engine's GPU
+            raise ValueError(f"update_texture_device needs a tensor on {self.device}, got {tensor.device}")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        check(self._lib.pupil_pt_update_texture_device(self._pt, int(material), int(slot), C.c_void_p(tensor.data_ptr()),
+                                                       int(tensor.shape[1]), int(tensor.shape[0]),
+                                                       C.c_void_p(s.cuda_stream)))
+        self.mark_dirty()
+
+    def material_info(self) -> dict:
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_material_info(self._pt, C.byref(n), C.byref(ms)))
+        return {"updates": n.value, "last_ms": ms.value}
+
+    def read_material(self, material: int) -> dict:
+        """The device's copy of a material (pupil_debug_read_material): type, eta, int_fdr and
+        specular_sampling_weight (float32)."""
+        import numpy as np
+
+        t = C.c_uint32(0)
+        out = np.zeros(3, np.float32)
+        check(self._lib.pupil_debug_read_material(self._pt, int(material), C.byref(t), out.ctypes.data_as(abi.f32p)))
+        return {"type": t.value, "eta": out[0], "int_fdr": out[1], "specular_sampling_weight": out[2]}
+
     # ---- engine-owned emitter table (pupil_pt_enable_device_emitters)
     @property
     def device_emitters(self):

@@ -55,6 +55,25 @@ def checkerboard(color0, color1, uv_scale=(1.0, 1.0)) -> abi.Texture:
     return t
 
 
+def bitmap(rgba, filter=1, uv_scale=(1.0, 1.0)) -> abi.Texture:
+    """Bitmap texture from an (h, w, 4) float32 array, row 0 first (util::BitmapTexture's order);
+    filter: 0 point, 1 bilinear.  The texture keeps the array alive: ctypes carries the reference
+    into every Material the texture is copied into, and the world copies the texels when it takes
+    the material (add_material / set_material)."""
+    a = np.ascontiguousarray(np.asarray(rgba, dtype=np.float32))
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError(f"bitmap needs an (h, w, 4) array, got {a.shape}")
+    t = abi.Texture()
+    t.type = abi.TEX_BITMAP
+    t.height, t.width = a.shape[0], a.shape[1]
+    t.filter = int(filter)
+    m = identity4()
+    m[0, 0], m[1, 1] = uv_scale
+    t.transform[:] = m.reshape(-1)
+    t.rgba = _ptr(a)  # the pointer object holds `a`, and t holds the pointer object
+    return t
+
+
 def _mat(mtype, textures, twosided=False, int_ior=1.0, ext_ior=1.0, nonlinear=False) -> abi.Material:
     m = abi.Material()
     m.type = mtype
@@ -62,6 +81,7 @@ def _mat(mtype, textures, twosided=False, int_ior=1.0, ext_ior=1.0, nonlinear=Fa
     m.int_ior = int_ior
     m.ext_ior = ext_ior
     m.nonlinear = int(nonlinear)
+    m._keep = list(textures)  # a bitmap's texel array lives as long as the material
     for k, t in enumerate(textures):
         m.tex[k] = t
     for k in range(len(textures), 4):
@@ -196,6 +216,13 @@ class World:
         carries the new matrices and area emitters (world/world.cpp:45-54)."""
         m = _f32(to_world, 16)
         check(self._lib.pupil_world_set_instance_transform(self._h, int(instance), _ptr(m)))
+        self._desc = None
+
+    def set_material(self, material: int, m: abi.Material):
+        """Replace material `material` (index into desc().materials: the world flattens one per
+        instance, in instance order); the next desc() carries it, and PTPass.update_material hands
+        it to the engine.  Bitmap texels are copied by the world."""
+        check(self._lib.pupil_world_set_material(self._h, int(material), C.byref(m)))
         self._desc = None
 
     def set_instance_visibility(self, instance: int, mask: int):
