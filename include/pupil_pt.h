@@ -577,6 +577,15 @@ int pupil_debug_read_material(pupil_pt *pt, uint32_t material, uint32_t *type, f
  * node array with nodes whose every float is `value`, then recomputes node_bound (test of
  * the bound's live-node ranges); PUPIL_ERR_UNSUPPORTED for the flattened BVH */
 int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value);
+/* the builder's binary tree over n >= 2 boxes (6 floats each: lo xyz, hi xyz) with `rounds`
+ * (<= 64) reinsertion rounds: cost[r] = the tree's surface-area cost (sum of the internal
+ * nodes' half areas) after r rounds, r = 0 .. rounds; a round the pass did not keep, or did
+ * not run because nothing was left to move, repeats the figure before it.  *kept = rounds that
+ * moved something and were committed, *rejected = rounds thrown away because they raised the
+ * cost (0 or 1: the pass ends at the first); kept + rejected < rounds means a round found
+ * nothing to move.  Either may be NULL. */
+int pupil_debug_bvh_reinsert(int device, uint32_t n, const float *boxes, uint32_t rounds, double *cost,
+                             uint32_t *kept, uint32_t *rejected);
 
 /* ---- image output (util::BitmapTexture::Save, framework/util/texture.cpp:12-85,152-160) ----
  * rgba: width*height float4, row 0 = image bottom (the "final result" order).

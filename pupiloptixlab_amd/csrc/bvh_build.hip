@@ -16,6 +16,7 @@
 //   9. k_attrs         per-primitive shading records in the same order
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <utility>
@@ -481,20 +482,6 @@ __global__ void k_ploc_compact(int m, const int *ref, const Aabb *box, const int
     }
 }
 
-// top-down: subtree [first, first + count) of the new primitive order
-__global__ void k_ploc_place(int lo, int hi, const int2 *node_child, const int *node_count, int *first,
-                             int *newpos) {
-    const int id = lo + blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= hi) return;
-    const int f = first[id];
-    const int2 c = node_child[id];
-    const int cl = c.x >= 0 ? node_count[c.x] : 1;
-    if (c.x >= 0) first[c.x] = f;
-    else newpos[~c.x] = f;
-    if (c.y >= 0) first[c.y] = f + cl;
-    else newpos[~c.y] = f + cl;
-}
-
 // creation id -> LBVH arrays (root 0), new primitive order
 __global__ void k_ploc_export(int n, const int2 *node_child, const Aabb *node_box, const int *node_count,
                               const int *first, const int *newpos, int2 *children, int2 *ranges, Aabb *node_boxes,
@@ -518,6 +505,227 @@ __global__ void k_ploc_permute(int n, const int *newpos, const uint32_t *vals_in
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     vals_out[newpos[i]] = vals_in[i];
+}
+
+// top-down: subtree [first, first + count) of the new primitive order.  The nodes of one
+// depth level place their children and queue the internal ones for the next level (any
+// binary tree; the queue's order does not matter, first/newpos depend on the topology alone)
+__global__ void k_ploc_place(int m, const int *items, const int2 *node_child, const int *node_count, int *first,
+                             int *newpos, int *next, int *next_count) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const int id = items[t];
+    const int f = first[id];
+    const int2 c = node_child[id];
+    const int cl = c.x >= 0 ? node_count[c.x] : 1;
+    if (c.x >= 0) first[c.x] = f;
+    else newpos[~c.x] = f;
+    if (c.y >= 0) first[c.y] = f + cl;
+    else newpos[~c.y] = f + cl;
+    const int k = (c.x >= 0 ? 1 : 0) + (c.y >= 0 ? 1 : 0);
+    if (k) {
+        int at = atomicAdd(next_count, k);
+        if (c.x >= 0) next[at++] = c.x;
+        if (c.y >= 0) next[at] = c.y;
+    }
+}
+
+// ---------------------------------------------------------------- parallel reinsertion
+// Meister & Bittner 2018, "Parallel Reinsertion for Bounding Volume Hierarchy
+// Optimization", over the PLOC binary tree (creation ids) before it is exported.  One round:
+// every node looks for the position where its subtree, removed and put back as the sibling
+// of another node, lowers the tree's surface-area cost the most (k_reins_search); the
+// candidates claim the five nodes whose links they rewrite with a 64-bit atomicMax of
+// (gain bits, node) and only those owning all five go on (k_reins_resolve); a move whose
+// target lies inside another mover's subtree is dropped, since two such moves could close a
+// cycle (k_reins_filter); the rest are applied (k_reins_apply) and the boxes and counts
+// refitted bottom up (k_reins_refit).  No locks and no waiting: the winners are a function
+// of the tree alone.  Nodes are named by one index u: internal creation id < n - 1, leaf at
+// Morton position p = n - 1 + p; box[] and parent[] are indexed by u.
+constexpr int kReinsStack = 32;    // search stack entries per thread
+constexpr int kReinsVisits = 256;  // search visit cap per node
+constexpr int kReinsDefault = 2;   // PUPIL_BVH_REINSERT
+
+__device__ __forceinline__ int ref_u(int r, int nm1) { return r >= 0 ? r : nm1 + ~r; }
+__device__ __forceinline__ int u_ref(int u, int nm1) { return u < nm1 ? u : ~(u - nm1); }
+
+__global__ void k_reins_init(int n, const uint32_t *sorted_vals, const Aabb *prim_boxes, const int2 *node_child,
+                             Aabb *box, int *parent) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nm1 = n - 1;
+    if (i < n) box[nm1 + i] = prim_boxes[sorted_vals[i]];
+    if (i < nm1) {
+        const int2 c = node_child[i];
+        parent[ref_u(c.x, nm1)] = i;
+        parent[ref_u(c.y, nm1)] = i;
+        if (i == n - 2) parent[i] = -1;  // root = last node created
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_reins_search(int n, const int2 *node_child, const Aabb *box,
+                                                         const int *parent, int *cand_x, int *cand_pivot,
+                                                         float *cand_gain, unsigned long long *claim) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nm1 = n - 1, total = 2 * n - 1;
+    if (u >= total) return;
+    cand_x[u] = -1;
+    const int P = parent[u];
+    if (P < 0 || parent[P] < 0) return;  // the root and its children stay: the root keeps its id
+    const Aabb bl = box[u];
+    const float al = half_area(bl);
+    int st_node[kReinsStack];
+    float st_ind[kReinsStack];
+    float best = 0.f;
+    int best_x = -1, best_pivot = -1;
+    int visits = 0;
+    int pivot = P, from = u;
+    float bound = half_area(box[P]);  // area saved so far by taking the subtree out
+    Aabb shr;                         // box of `from` once the subtree is out
+    bool have_shr = false;
+    while (visits < kReinsVisits) {
+        const int2 pc = node_child[pivot];
+        const int sib = ref_u(pc.x, nm1) == from ? ref_u(pc.y, nm1) : ref_u(pc.x, nm1);
+        if (have_shr && from != P) bound += half_area(box[from]) - half_area(shr);
+        int sp = 0;
+        st_node[sp] = sib;
+        st_ind[sp++] = 0.f;
+        while (sp > 0 && visits < kReinsVisits) {
+            sp--;
+            const int x = st_node[sp];
+            const float ind = st_ind[sp];
+            if (!(bound - ind - al > best)) continue;  // lower bound on the cost below x
+            visits++;
+            const Aabb bx = box[x];
+            const float m = half_area(merge(bx, bl));
+            const float g = bound - ind - m;
+            if (g > best) {
+                best = g;
+                best_x = x;
+                best_pivot = pivot;
+            }
+            if (x < nm1) {
+                const float cind = ind + (m - half_area(bx));
+                if (bound - cind - al > best && sp + 2 <= kReinsStack) {
+                    const int2 c = node_child[x];
+                    st_node[sp] = ref_u(c.y, nm1);
+                    st_ind[sp++] = cind;
+                    st_node[sp] = ref_u(c.x, nm1);
+                    st_ind[sp++] = cind;
+                }
+            }
+        }
+        const Aabb bs = box[sib];
+        shr = have_shr ? merge(shr, bs) : bs;
+        have_shr = true;
+        from = pivot;
+        pivot = parent[pivot];
+        visits++;
+        if (pivot < 0) break;
+    }
+    if (best_x < 0) return;
+    const int2 pc = node_child[P];
+    const int S = ref_u(pc.x, nm1) == u ? ref_u(pc.y, nm1) : ref_u(pc.x, nm1);
+    if (best_x == S) return;  // the place it has
+    cand_x[u] = best_x;
+    cand_pivot[u] = best_pivot;
+    cand_gain[u] = best;
+    // gains are positive floats: their bits order as integers; the node id makes keys unique
+    const unsigned long long key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)u;
+    atomicMax(&claim[u], key);
+    atomicMax(&claim[P], key);
+    atomicMax(&claim[S], key);
+    atomicMax(&claim[best_x], key);
+    atomicMax(&claim[parent[best_x]], key);
+}
+
+__global__ void k_reins_resolve(int n, const int2 *node_child, const int *parent, const int *cand_x,
+                                const float *cand_gain, const unsigned long long *claim, uint8_t *mover) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nm1 = n - 1;
+    if (u >= 2 * n - 1) return;
+    const int X = cand_x[u];
+    bool win = false;
+    if (X >= 0) {
+        const int P = parent[u];
+        const int2 pc = node_child[P];
+        const int S = ref_u(pc.x, nm1) == u ? ref_u(pc.y, nm1) : ref_u(pc.x, nm1);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(cand_gain[u]) << 32) | (unsigned)u;
+        win = claim[u] == key && claim[P] == key && claim[S] == key && claim[X] == key && claim[parent[X]] == key;
+    }
+    mover[u] = win ? 1 : 0;
+}
+
+// moves[k] = (L, slot of P in its parent, slot of X in its parent)
+__global__ void k_reins_filter(int n, const int2 *node_child, const int *parent, const int *cand_x,
+                               const int *cand_pivot, const uint8_t *mover, int3 *moves, int *num_moves) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nm1 = n - 1;
+    if (u >= 2 * n - 1 || !mover[u]) return;
+    const int X = cand_x[u], pivot = cand_pivot[u];
+    // between the target and the pivot no node may move itself: the pivot and everything
+    // above it hold the subtree before and after, so a mover there takes both along
+    int a = parent[X];
+    for (int k = 0; k < n && a >= 0 && a != pivot; k++) {
+        if (mover[a]) return;
+        a = parent[a];
+    }
+    const int P = parent[u], G = parent[P], XP = parent[X];
+    const int sg = ref_u(node_child[G].x, nm1) == P ? 0 : 1;
+    const int sx = ref_u(node_child[XP].x, nm1) == X ? 0 : 1;
+    moves[atomicAdd(num_moves, 1)] = make_int3(u, sg, sx);
+}
+
+__global__ void k_reins_apply(int n, int num_moves, const int3 *moves, const int *cand_x, int2 *node_child,
+                              int *parent) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nm1 = n - 1;
+    if (k >= num_moves) return;
+    const int3 mv = moves[k];
+    const int L = mv.x, X = cand_x[L];
+    // every link below belongs to a node this move owns (or to one slot of G / XP that no
+    // other surviving move rewrites), so the reads of parent[] see the old tree
+    const int P = parent[L], G = parent[P], XP = parent[X];
+    const int2 pc = node_child[P];
+    const int S = ref_u(pc.x, nm1) == L ? ref_u(pc.y, nm1) : ref_u(pc.x, nm1);
+    ((int *)&node_child[G])[mv.y] = u_ref(S, nm1);
+    ((int *)&node_child[XP])[mv.z] = u_ref(P, nm1);  // XP != P: the target is neither L nor S
+    node_child[P] = make_int2(u_ref(X, nm1), u_ref(L, nm1));
+    parent[S] = G;
+    parent[P] = XP;
+    parent[X] = P;
+}
+
+// bottom-up boxes and counts from the leaves; the second arrival at a node finishes it
+__global__ void k_reins_refit(int n, const int2 *node_child, const int *parent, Aabb *box, int *node_count,
+                              uint32_t *flags) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int nm1 = n - 1;
+    if (i >= n) return;
+    int node = parent[nm1 + i];
+    for (int k = 0; k < n && node >= 0; k++) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        const uint32_t prev = __hip_atomic_fetch_add(&flags[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (prev == 0u) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const int2 c = node_child[node];
+        box[node] = merge(box[ref_u(c.x, nm1)], box[ref_u(c.y, nm1)]);
+        node_count[node] = (c.x >= 0 ? node_count[c.x] : 1) + (c.y >= 0 ? node_count[c.y] : 1);
+        node = parent[node];
+    }
+}
+
+// surface-area cost of the binary tree: per-block sums of the internal nodes' half areas,
+// in a fixed order (the host adds the blocks in order), so the figure is reproducible
+__global__ __launch_bounds__(kBlock) void k_reins_cost(int m, const Aabb *box, double *partial) {
+    __shared__ double sh[kBlock];
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    sh[threadIdx.x] = i < m ? (double)half_area(box[i]) : 0.0;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
 }
 
 // ---------------------------------------------------------------- BVH4 collapse
@@ -984,9 +1192,129 @@ hipError_t collapse_bvh4(int n, const uint32_t *sorted_vals, const Aabb *prim_bo
     return err;
 }
 
-// PLOC topology (see the PLOC section) -> LBVH arrays and the new primitive order
+// PUPIL_BVH_REINSERT=<rounds>: reinsertion rounds over the PLOC tree (0: the PLOC tree as built)
+int reinsert_rounds() {
+    if (const char *e = std::getenv("PUPIL_BVH_REINSERT")) return std::min(64, std::max(0, std::atoi(e)));
+    return kReinsDefault;
+}
+
+// Up to `rounds` reinsertion rounds (see the section above) over the creation-id tree
+// node_child / node_box / node_count, in place.  A round works on copies and is committed
+// only if it did not raise the tree's cost: the gains of one round's moves are computed one
+// by one, and moves that refit the same ancestors can in rare cases add up to a loss; such a
+// round is thrown away and the pass ends there, as it does after a round without moves.
+// log (optional): the cost before the pass and after each committed round, and the rounds
+// kept and thrown away.  When the device is out of memory for the scratch arrays the tree
+// stays as it is; any other failure is an error.
+hipError_t reinsert_ploc(int n, int rounds, const uint32_t *vals_in, const Aabb *prim_boxes, int2 *node_child,
+                         Aabb *node_box, int *node_count, ReinsertLog *log, hipStream_t s) {
+    ReinsertLog env_log;  // PUPIL_BVH_REINSERT_LOG=1: one line per build on stderr
+    const bool print = !log && rounds > 0 && std::getenv("PUPIL_BVH_REINSERT_LOG");
+    if (print) log = &env_log;
+    if (log) *log = ReinsertLog{};
+    if (n < 2 || (rounds <= 0 && !log)) return hipSuccess;
+    const int nm1 = n - 1, total = 2 * n - 1;
+    const int nblk = (nm1 + kBlock - 1) / kBlock;
+    int2 *w_child = nullptr;
+    Aabb *w_box = nullptr;
+    int *w_count = nullptr, *parent = nullptr, *cand_x = nullptr, *cand_pivot = nullptr, *num_moves = nullptr;
+    float *cand_gain = nullptr;
+    unsigned long long *claim = nullptr;
+    uint8_t *mover = nullptr;
+    int3 *moves = nullptr;
+    uint32_t *flags = nullptr;
+    double *partial = nullptr;
+    hipError_t err = dmalloc(&w_child, n);
+    if (!err) err = dmalloc(&w_box, total);
+    if (!err) err = dmalloc(&w_count, n);
+    if (!err) err = dmalloc(&parent, total);
+    if (!err) err = dmalloc(&cand_x, total);
+    if (!err) err = dmalloc(&cand_pivot, total);
+    if (!err) err = dmalloc(&cand_gain, total);
+    if (!err) err = dmalloc(&claim, total);
+    if (!err) err = dmalloc(&mover, total);
+    if (!err) err = dmalloc(&moves, total);
+    if (!err) err = dmalloc(&num_moves, 1);
+    if (!err) err = dmalloc(&flags, n);
+    if (!err) err = dmalloc(&partial, nblk);
+    void *bufs[] = {w_child, w_box, w_count, parent, cand_x, cand_pivot, cand_gain, claim, mover, moves, num_moves,
+                    flags, partial};
+    const auto release = [&]() {
+        for (void *b : bufs)
+            if (b) (void)hipFree(b);
+    };
+    if (err) {  // out of memory for the pass: the unoptimised tree
+        (void)hipGetLastError();
+        release();
+        return err == hipErrorOutOfMemory ? hipSuccess : err;
+    }
+    const auto grid = [](int m) { return dim3((unsigned)((m + kBlock - 1) / kBlock)); };
+    std::vector<double> hp((size_t)nblk);
+    const auto cost_of = [&](const Aabb *box, double *out) {
+        hipLaunchKernelGGL(k_reins_cost, dim3(nblk), dim3(kBlock), 0, s, nm1, box, partial);
+        hipError_t e = hipMemcpyAsync(hp.data(), partial, sizeof(double) * nblk, hipMemcpyDeviceToHost, s);
+        if (!e) e = hipStreamSynchronize(s);
+        double c = 0.0;
+        for (double v : hp) c += v;
+        *out = c;
+        return e;
+    };
+    double cost = 0.0;
+    err = hipMemcpyAsync(w_child, node_child, sizeof(int2) * nm1, hipMemcpyDeviceToDevice, s);
+    if (!err) err = hipMemcpyAsync(w_box, node_box, sizeof(Aabb) * nm1, hipMemcpyDeviceToDevice, s);
+    if (!err) err = hipMemcpyAsync(w_count, node_count, sizeof(int) * nm1, hipMemcpyDeviceToDevice, s);
+    if (!err) {
+        hipLaunchKernelGGL(k_reins_init, grid(n), dim3(kBlock), 0, s, n, vals_in, prim_boxes, w_child, w_box, parent);
+        err = cost_of(w_box, &cost);
+    }
+    if (!err && log) log->costs.push_back(cost);
+    for (int r = 0; r < rounds && !err; r++) {
+        err = hipMemsetAsync(claim, 0, sizeof(unsigned long long) * total, s);
+        if (!err) err = hipMemsetAsync(num_moves, 0, sizeof(int), s);
+        if (err) break;
+        hipLaunchKernelGGL(k_reins_search, grid(total), dim3(kBlock), 0, s, n, w_child, w_box, parent, cand_x,
+                           cand_pivot, cand_gain, claim);
+        hipLaunchKernelGGL(k_reins_resolve, grid(total), dim3(kBlock), 0, s, n, w_child, parent, cand_x, cand_gain,
+                           claim, mover);
+        hipLaunchKernelGGL(k_reins_filter, grid(total), dim3(kBlock), 0, s, n, w_child, parent, cand_x, cand_pivot,
+                           mover, moves, num_moves);
+        int nmoves = 0;
+        err = hipMemcpyAsync(&nmoves, num_moves, sizeof(int), hipMemcpyDeviceToHost, s);
+        if (!err) err = hipStreamSynchronize(s);
+        if (err || nmoves <= 0) break;
+        hipLaunchKernelGGL(k_reins_apply, grid(nmoves), dim3(kBlock), 0, s, n, nmoves, moves, cand_x, w_child, parent);
+        err = hipMemsetAsync(flags, 0, sizeof(uint32_t) * n, s);
+        if (err) break;
+        hipLaunchKernelGGL(k_reins_refit, grid(n), dim3(kBlock), 0, s, n, w_child, parent, w_box, w_count, flags);
+        double after = 0.0;
+        err = cost_of(w_box, &after);
+        if (err) break;
+        if (after > cost) {  // a round that raised the cost is not committed
+            if (log) log->rejected++;
+            break;
+        }
+        err = hipMemcpyAsync(node_child, w_child, sizeof(int2) * nm1, hipMemcpyDeviceToDevice, s);
+        if (!err) err = hipMemcpyAsync(node_box, w_box, sizeof(Aabb) * nm1, hipMemcpyDeviceToDevice, s);
+        if (!err) err = hipMemcpyAsync(node_count, w_count, sizeof(int) * nm1, hipMemcpyDeviceToDevice, s);
+        cost = after;
+        if (!err && log) {
+            log->costs.push_back(cost);
+            log->kept++;
+        }
+    }
+    if (!err) err = hipStreamSynchronize(s);
+    release();
+    if (print && !log->costs.empty())
+        std::fprintf(stderr, "reinsert: %d leaves, %d rounds asked, %d kept, %d rejected, cost %.9g -> %.9g\n", n, rounds,
+                     log->kept, log->rejected, log->costs.front(), log->costs.back());
+    return err;
+}
+
+// PLOC topology (see the PLOC section) -> LBVH arrays and the new primitive order; `rounds`
+// reinsertion rounds in between
 hipError_t build_ploc(int n, const uint32_t *vals_in, uint32_t *vals_out, const Aabb *prim_boxes, int2 *children,
-                      int2 *ranges, Aabb *node_boxes, int *parent_internal, int *parent_leaf, hipStream_t s) {
+                      int2 *ranges, Aabb *node_boxes, int *parent_internal, int *parent_leaf, hipStream_t s,
+                      int rounds, ReinsertLog *log = nullptr) {
     int *ref_a = nullptr, *ref_b = nullptr, *nn = nullptr, *node_count = nullptr, *first = nullptr, *newpos = nullptr;
     Aabb *box_a = nullptr, *box_b = nullptr, *node_box = nullptr;
     int2 *node_child = nullptr;
@@ -1008,7 +1336,6 @@ hipError_t build_ploc(int n, const uint32_t *vals_in, uint32_t *vals_out, const 
     if (!err) err = dmalloc(&sums, nsum);
     if (!err) err = dmalloc(&total, 1);
     if (!err && nsum > per) err = hipErrorInvalidValue;  // > 16.7 G primitives
-    std::vector<int2> iters;
     if (!err) {
         const auto grid = [](int m) { return dim3((unsigned)((m + kBlock - 1) / kBlock)); };
         hipLaunchKernelGGL(k_ploc_init, grid(n), dim3(kBlock), 0, s, n, vals_in, prim_boxes, ref_a, box_a);
@@ -1029,19 +1356,30 @@ hipError_t build_ploc(int n, const uint32_t *vals_in, uint32_t *vals_out, const 
             if (err) break;
             hipLaunchKernelGGL(k_ploc_compact, grid(m), dim3(kBlock), 0, s, m, ref_a, box_a, nn, flg, pos, base,
                                ref_b, box_b, node_child, node_box, node_count);
-            iters.push_back(make_int2(base, merges));
             base += merges;
             std::swap(ref_a, ref_b);
             std::swap(box_a, box_b);
             m = m_new;
         }
+        if (!err) err = reinsert_ploc(n, rounds, vals_in, prim_boxes, node_child, node_box, node_count, log, s);
         if (!err) {
-            (void)hipMemsetAsync(first + (n - 2), 0, sizeof(int), s);  // root = last node created
-            for (size_t k = iters.size(); k-- > 0;) {
-                const int lo = iters[k].x, hi = iters[k].x + iters[k].y;
-                hipLaunchKernelGGL(k_ploc_place, grid(hi - lo), dim3(kBlock), 0, s, lo, hi, node_child, node_count,
-                                   first, newpos);
+            // top-down placement, one launch per depth level (after reinsertion the creation
+            // ids no longer order parents after children); ref_a / ref_b / nn are free now
+            const int root = n - 2;  // root = last node created
+            (void)hipMemsetAsync(first + root, 0, sizeof(int), s);
+            err = hipMemcpyAsync(ref_a, &root, sizeof(int), hipMemcpyHostToDevice, s);
+            int level = 1, levels = 0;
+            while (!err && level > 0) {
+                (void)hipMemsetAsync(nn, 0, sizeof(int), s);
+                hipLaunchKernelGGL(k_ploc_place, grid(level), dim3(kBlock), 0, s, level, ref_a, node_child,
+                                   node_count, first, newpos, ref_b, nn);
+                err = hipMemcpyAsync(&level, nn, sizeof(int), hipMemcpyDeviceToHost, s);
+                if (!err) err = hipStreamSynchronize(s);
+                std::swap(ref_a, ref_b);
+                if (!err && (level < 0 || level > n - 1 || ++levels > n)) err = hipErrorUnknown;  // cannot happen
             }
+        }
+        if (!err) {
             hipLaunchKernelGGL(k_ploc_export, grid(n - 1), dim3(kBlock), 0, s, n, node_child, node_box, node_count,
                                first, newpos, children, ranges, node_boxes, parent_internal, parent_leaf);
             hipLaunchKernelGGL(k_ploc_permute, grid(n), dim3(kBlock), 0, s, n, newpos, vals_in, vals_out);
@@ -1132,7 +1470,8 @@ int build_lbvh(const BvhBuildInput &in, BvhBuildOutput &out, uint32_t leaf_size,
             const char *builder = std::getenv("PUPIL_BVH_BUILDER");
             const bool ploc = !force_lbvh && !(builder && std::strcmp(builder, "lbvh") == 0);
             if (ploc) {
-                err = build_ploc(n, vi, vo, boxes, children, ranges, node_boxes, parent_internal, parent_leaf, s);
+                err = build_ploc(n, vi, vo, boxes, children, ranges, node_boxes, parent_internal, parent_leaf, s,
+                                 reinsert_rounds());
                 uint32_t *t = vi;  // vo holds the PLOC primitive order
                 vi = vo;
                 vo = t;
@@ -1279,7 +1618,7 @@ int build_lbvh(const BvhBuildInput &in, BvhBuildOutput &out, uint32_t leaf_size,
 // breadth first: parents before children) whose leaf links make_leaf(p, 1) name the
 // box order[p].  n >= 2.
 int build_bvh4_over_boxes(const float *h_boxes, uint32_t n, std::vector<Bvh4Node> &nodes, std::vector<uint32_t> &order,
-                          uint32_t *depth, hipStream_t s) {
+                          uint32_t *depth, hipStream_t s, int rounds, ReinsertLog *log) {
     if (n < 2) return -1;
     const int m = (int)n;
     Aabb *boxes = nullptr, *node_boxes = nullptr;
@@ -1320,7 +1659,8 @@ int build_bvh4_over_boxes(const float *h_boxes, uint32_t n, std::vector<Bvh4Node
             std::swap(vi, vo);
         }
         (void)hipMemsetAsync(parent_internal, 0xFF, sizeof(int) * n, s);
-        err = build_ploc(m, vi, vo, boxes, children, ranges, node_boxes, parent_internal, parent_leaf, s);
+        err = build_ploc(m, vi, vo, boxes, children, ranges, node_boxes, parent_internal, parent_leaf, s,
+                         rounds < 0 ? reinsert_rounds() : rounds, log);
         std::swap(vi, vo);  // vi: the PLOC box order
         std::vector<uint32_t> level_start;
         if (!err)

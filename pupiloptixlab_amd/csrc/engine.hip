@@ -2179,6 +2179,23 @@ int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value) {
     return pt->accel.publish();
 }
 
+int pupil_debug_bvh_reinsert(int device, uint32_t n, const float *boxes, uint32_t rounds, double *cost,
+                             uint32_t *kept, uint32_t *rejected) {
+    if (!boxes || !cost) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (n < 2 || rounds > 64u) return fail(PUPIL_ERR_INVALID, "needs n >= 2 boxes and at most 64 rounds");
+    HIP_TRY(hipSetDevice(device));
+    std::vector<Bvh4Node> nodes;
+    std::vector<uint32_t> order;
+    ReinsertLog log;
+    if (build_bvh4_over_boxes(boxes, n, nodes, order, nullptr, nullptr, (int)rounds, &log) != 0)
+        return fail(PUPIL_ERR_HIP, "the box BVH build failed");
+    if (log.costs.empty()) return fail(PUPIL_ERR_HIP, "out of device memory for the reinsertion pass");
+    for (uint32_t r = 0; r <= rounds; r++) cost[r] = log.costs[std::min<size_t>(r, log.costs.size() - 1)];
+    if (kept) *kept = (uint32_t)log.kept;
+    if (rejected) *rejected = (uint32_t)log.rejected;
+    return PUPIL_OK;
+}
+
 int pupil_debug_math(int device, uint32_t n, const float *x, const float *y2, float *out) {
     if (!x || !y2 || !out) return fail(PUPIL_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(device));

@@ -352,8 +352,16 @@ void launch_refresh_attrs_shape(float4 *attrs, uint32_t n, const float *position
                                 const uint32_t *indices, hipStream_t s);
 // BVH4 over n >= 2 boxes (6 floats each: lo xyz, hi xyz) with the flattened build's PLOC +
 // SAH collapse, one box per leaf: nodes (root 0, parents first) and, for leaf link
-// make_leaf(p, 1), the box order[p]; depth = 4-wide levels
+// make_leaf(p, 1), the box order[p]; depth = 4-wide levels.  rounds: reinsertion rounds over
+// the PLOC tree (< 0: PUPIL_BVH_REINSERT or its default); log (optional): what the pass did
+struct ReinsertLog {
+    std::vector<double> costs;  // the binary tree's surface-area cost (sum of the internal nodes' half
+                                // areas) before the pass and after each round it kept
+    int kept = 0;               // rounds committed
+    int rejected = 0;           // rounds thrown away because the cost rose (the pass ends there)
+};
 int build_bvh4_over_boxes(const float *h_boxes, uint32_t n, std::vector<Bvh4Node> &nodes,
-                          std::vector<uint32_t> &order, uint32_t *depth, hipStream_t s);
+                          std::vector<uint32_t> &order, uint32_t *depth, hipStream_t s, int rounds = -1,
+                          ReinsertLog *log = nullptr);
 
 }  // namespace pupil
