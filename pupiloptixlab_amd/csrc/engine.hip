@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "host/emitter_weight.h"
+#include "host/pipe_schedule.h"
 #include "pt_accel.h"
 
 namespace {
@@ -89,67 +90,15 @@ struct pupil_pt {
     bool fresh() const { return fresh_shade && shade_list; }
     uint32_t width = 0, height = 0, max_depth = 1;
     uint32_t num_prims = 0;
-    // Pipelined frames (render_pipelined, PUPIL_PIPE): the path state is a ring of K
-    // slots of one batch each; consecutive renders that continue each other (OnRun
-    // cadence, or PUPIL_HINT_CONTINUE) keep up to K frames in flight, each at its own
-    // bounce, and every iteration of a render advances all of them by one bounce in ONE
-    // persistent traversal launch and ONE shade launch.  A render returns with its own
-    // frame complete; the frames ahead of it depend only on (seed, camera, scene) and
-    // are dropped on any change.  ahead_mode: 1 = single-spp renders or the hint,
-    // 2 = every render, 0 = off (PUPIL_AHEAD).
-    int ahead_mode = 1;
-    // a group of `frames` consecutive frames (seeds seed, seed + spp, ...) in one ring slot
-    struct PipeFrame {
-        uint32_t slot, seed, phases;  // phases = bounces traced + shaded so far (complete at max_depth)
-        bool aov_scratch;             // AOVs wait in the slot's scratch until each frame's render
-        uint32_t frames, consumed;    // frames in the group; accumulated (rendered) so far
-    };
-    std::vector<PipeFrame> pipe;      // in flight, oldest first
-    // an iteration split over two renders (frame-group pacing, render_pipelined): the trace half
-    // ran, the shade half is due at the start of the next render
-    struct HalfIter {
-        bool had, inject;
-        PipeFrame nf;
-        uint32_t nfp;
-    };
-    HalfIter half{};
-    bool half_pending = false;
-    bool pipe_split = true;           // PUPIL_PIPE_SPLIT=0: whole iterations only (A/B)
-    // PUPIL_PIPE_GROUP_MAX: frames per group at most.  The latency bound is the group's paths
-    // (PUPIL_PIPE_GROUP_PATHS, 4 M: two 1080p frames), so the heaviest OnRun carries the same
-    // work at any tile share (profiles/r06_shard_probe_onrun.txt); 2 caps it at N = 1 sizes too
-    uint32_t pipe_group_max = 64;
-    uint32_t pipe_ramp = 1;           // PUPIL_PIPE_RAMP: groups one render may start ahead (0 = no limit)
-    uint32_t pipe_slots = 0;          // K of the ring in use
-    size_t pipe_np = 0;               // paths per slot
-    uint32_t pipe_key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // w, h, tile size, rank, world, spp, depth, local pixels, G
-    size_t pipe_cap = 0;              // paths per ring slot (G frames)
-    // PUPIL_PIPE_GROUP_PATHS: renders of fewer paths batch G = ceil(this / paths) frames per slot
-    double pipe_group_paths = 4e6;
-    // renders that start no frame ahead (a moving camera) with at most this many paths run as one
-    // persistent launch per frame (pt_frame.hip); PUPIL_FRAME_PATHS, 0 = never.  Moving-camera
-    // OnRuns at 1080p (r05 shard probe): one rank of 8 (260 k paths) 7.40 vs 8.47 ms per 8 OnRuns
-    // in one launch vs the stage pipeline, one of 4 (518 k) 12.86 vs 10.56, one GPU 39.7 vs 22.8
-    double frame_paths = 4e5;
+    // Pipelined frames (render_pipelined, PUPIL_PIPE): the path state is a ring of K slots of one
+    // batch each, and consecutive renders that continue each other keep up to K frames in
+    // flight.  The schedule, its knobs and its state: host/pipe_schedule.h
+    PipeKnobs knobs;
+    PipeState pipe;
     bool ring_fresh = true;           // the ring was (re)allocated: its flags bytes are not yet cleared
     uint32_t bin_mask = 0;            // material bins of the scene's instances + the miss bin (partition)
-    uint32_t pipe_run = 0;            // consecutive renders that continued the previous one
     uint64_t frame_launches = 0;      // renders run as one persistent launch (pt_frame.hip)
-    uint32_t pipe_next_seed = 0;      // random_seed of the render that would continue the last one
-    uint32_t pipe_gen = 0;            // iterations so far (flags tags)
-    uint32_t pipe_limit = 0;          // PUPIL_PIPE: most slots (0 = max_depth)
-    // PUPIL_PIPE_GB: most HBM bytes for the ring's path state; default a quarter of the
-    // device memory free when the engine was created (config 4 needs 9.5 GB, config 5 19 GB
-    // of a 288 GB MI355X), so a drop-in pass leaves the rest of a shared device to others
-    double pipe_budget = 0.0;
     uint64_t ring_bytes = 0;          // path state + queues + AOV scratch allocated now
-    // PUPIL_PIPE_PATHS: a ring needs no more slots than it takes to put this many paths in
-    // flight.  Frames ahead pay off by filling the launch tails of small launches; past
-    // ~64 M paths per launch the tail is amortised and a larger ring only spreads the
-    // traversal's path-state accesses (config 5, 133 M paths per frame: 2288 Mrays/s with
-    // one slot, 2208 / 2195 / 2155 / 2093 with 2 / 3 / 4 / 6, profiles/r03_pipe_sweep_config5.txt)
-    double pipe_paths = 64e6;
-    bool pipe_valid = false;          // cleared by camera / instance / emitter updates
     float *aov_scratch = nullptr;     // K slots x 7 floats per local pixel
     size_t aov_cap = 0;
     hipStream_t last_stream = nullptr;  // of the last render (NULL = the default stream)
@@ -273,9 +222,7 @@ struct pupil_pt {
         ps = PathState{};
         q.bins = q.nxsh = q.hist = nullptr;
         cap = 0;
-        pipe.clear();
-        half_pending = false;
-        pipe_valid = false;
+        pipe.ring_lost();
     }
     ~pupil_pt() {
         (void)hipSetDevice(device);
@@ -625,142 +572,50 @@ struct RenderCtx {
     }
 };
 
-// Pipelined frames.  The batch's path state is one slot of a ring of K slots.  A frame
-// runs max_depth phases -- phase b: trace (b = 0: the camera rays, else the shadow +
-// extension rays its bounce-(b-1) shade spawned) then the bounce-b shade -- and one
-// iteration of the loop below advances every frame in flight by one phase with one
-// flags partition over the ring, ONE persistent traversal launch (the listed shadow and
-// extension rays of all frames, plus the camera rays of a frame started in that
-// iteration) and ONE shade launch (each path at its own bounce).  A render runs the
-// iterations its own frame still needs and then accumulates it, so the frame is
-// complete when the call's work has run, as PTPass::OnRun requires
-// (pt_pass.cpp:51-56); the other frames in flight belong to the renders that continue
-// this one (random_seed + spp each, same camera, scene, tiling, spp and depth), and are
-// dropped when the next render does not continue it.  Frames are started in the last
-// run + 1 iterations of a render (run = renders in a row that continued the previous
-// one), so a continued sequence reaches one iteration per render after K renders, and
-// a render that is never continued (a moving camera) pays only for one frame's first
-// phase ahead.  Per path, every operation and its order are those of the reference's
-// per-pixel loop (main.cu:84-193): output is bit-identical to the oracle whatever the
-// schedule.  Renders that collect counters, depths above 63 (the 6-bit flags tags) and
-// PUPIL_AHEAD=0 run with K = 1: one frame at a time, D iterations.
+// Pipelined frames: the launches.  host/pipe_schedule.h decides what a render does -- the ring it
+// needs, whether it continues the last render, which frame group starts in which iteration --
+// and this function allocates, clears and launches what it is told.  Per path, every operation
+// and its order are those of the reference's per-pixel loop (main.cu:84-193): output is
+// bit-identical to the oracle whatever the schedule.
 int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch *launch) {
     pupil_pt *pt = cx.pt;
     hipStream_t s = cx.s;
-    const uint32_t D = fp.max_depth;
-    const size_t np = fp.num_paths;
-    const bool may_pipe = pt->ahead_mode != 0 &&
-                          (pt->ahead_mode == 2 || launch->spp == 1 || (launch->hints & PUPIL_HINT_CONTINUE)) && !cx.stats &&
-                          D >= 2 && D <= 63;  // the 6-bit flags tags of a slot stay unambiguous for 63 iterations
-    // frames ahead are started only once a continuation is likely: the caller said so
-    // (PUPIL_HINT_CONTINUE), or the last render was continued too.  A render after a change
-    // (a camera moving every OnRun) then traces nothing it may discard.
-    const bool cont_seed = pt->pipe_valid && pt->pipe_next_seed == launch->random_seed;
-    const bool speculate = (launch->hints & PUPIL_HINT_CONTINUE) || pt->ahead_mode == 2 ||
-                           (cont_seed && pt->pipe_run >= 1);
-    uint32_t K = 1, G = 1;
-    if (may_pipe) {
-        // frame groups: 1-spp renders (the OnRun cadence) smaller than PUPIL_PIPE_GROUP_PATHS
-        // (one rank's tiles, small films) batch G consecutive frames per ring slot, so each
-        // traversal launch carries enough rays to amortise its tail; the renders whose frame an
-        // earlier render already completed only accumulate it.  Batched renders (spp > 1, the
-        // bench's progressive steps) keep one frame per slot (PUPIL_PIPE_GROUP_ALL=1: group them too)
-        static const bool group_all = [] {
-            const char *e = std::getenv("PUPIL_PIPE_GROUP_ALL");
-            return e && std::atoi(e) != 0;
-        }();
-        if (launch->spp == 1 || group_all)
-            G = (uint32_t)std::min((double)pt->pipe_group_max,
-                                   std::max(1.0, std::ceil(pt->pipe_group_paths / (double)np)));
-        K = pt->pipe_limit ? std::min(pt->pipe_limit, D) : D;
-        constexpr double kPathBytes = 8 * 16 + 2 + 4 + 8 + 1;  // PathState + bins + nxsh + partition scratch
-        K = std::min<uint32_t>(K, (uint32_t)std::max(1.0, std::floor(pt->pipe_budget / ((double)G * np * kPathBytes))));
-        K = std::min<uint32_t>(K, (uint32_t)std::max(1.0, std::ceil(pt->pipe_paths / ((double)G * np))));
-        while (K * G > 1 && (uint64_t)K * G * np >= (1ull << 31)) {
-            if (G > 1) G--;
-            else K--;
-        }
-    }
-    uint32_t key[9] = {cx.key[0], cx.key[1], cx.key[2], cx.key[3], cx.key[4], fp.spp, D, fp.num_local, G};
-    // this render continues the last one (OnRun cadence: the next seed, nothing changed);
-    // frames in flight, if any, are then exactly the ones it and its successors need
-    bool reset = !(cont_seed && K == pt->pipe_slots && np == pt->pipe_np &&
-                   std::memcmp(key, pt->pipe_key, sizeof(key)) == 0 &&
-                   (pt->pipe.empty() ||
-                    pt->pipe.front().seed + pt->pipe.front().consumed * fp.spp == launch->random_seed));
+    PipeState &st = pt->pipe;
+    const PipeKnobs &kn = pt->knobs;
     const uint32_t nl = fp.num_local;
-    // a render that starts no frame ahead has none in flight either (speculation is off only
-    // right after a reset) and works on slot 0, frame 0: the ring is allocated for frames ahead
-    // only once a render speculates, so a camera moving every OnRun runs on the path-state
-    // footprint of PUPIL_AHEAD=0.  K and G stay as computed: the pipeline key does not change
-    // when speculation starts
-    const auto ring_need = [&]() { return speculate ? (size_t)K * G * np : (size_t)np; };
-    // a reset caused only by growing the ring (this render continues the last one) keeps the
-    // run count, so the render after the first speculating one speculates as well
-    const bool continued = !reset;
-    if (ring_need() > pt->cap) {  // growing the ring loses its contents
-        reset = true;
-        pt->pipe.clear();
-        int rc = ensure_state(pt, ring_need());
-        while (rc == PUPIL_ERR_OOM && speculate && K * G > 1) {  // a smaller ring, down to no frames ahead
-            if (K > 1) K = K > 2 ? K / 2 : 1;
-            else G = G > 2 ? G / 2 : 1;
-            rc = ensure_state(pt, ring_need());
-        }
+    const PipeRender r{fp.spp, launch->random_seed, fp.max_depth, (launch->hints & PUPIL_HINT_CONTINUE) != 0, cx.stats,
+                       fp.num_paths, nl, {cx.key[0], cx.key[1], cx.key[2], cx.key[3], cx.key[4]}};
+    PipePlan plan = st.plan(kn, r);
+    bool grew = false;
+    if (plan.ring_paths() > pt->cap) {  // growing the ring loses its contents
+        grew = true;
+        int rc = ensure_state(pt, plan.ring_paths());
+        while (rc == PUPIL_ERR_OOM && plan.shrink()) rc = ensure_state(pt, plan.ring_paths());
         if (rc) return rc;
-        key[8] = G;
     }
-    const size_t cap_paths = (size_t)G * np;  // paths per ring slot
-    // AOV scratch holds the AOVs of frames shaded ahead of their render: needed only once a
-    // render speculates (frames in flight imply an earlier speculating render allocated it), so a
-    // moving camera keeps the footprint of PUPIL_AHEAD=0 here too
-    if (speculate && K * G > 1 && (size_t)K * G * 7 * nl > pt->aov_cap) {
-        reset = true;
+    if (plan.aov_floats() > pt->aov_cap) {
+        grew = true;
         if (pt->aov_scratch) (void)hipFree(pt->aov_scratch);
         pt->aov_scratch = nullptr;
         pt->aov_cap = 0;
-        HIP_TRY(hipMalloc((void **)&pt->aov_scratch, sizeof(float) * (size_t)K * G * 7 * nl));
-        pt->aov_cap = (size_t)K * G * 7 * nl;
+        HIP_TRY(hipMalloc((void **)&pt->aov_scratch, sizeof(float) * plan.aov_floats()));
+        pt->aov_cap = plan.aov_floats();
     }
     const PathState ring = pt->ps;
-    if (reset) {
-        // the dropped frames' flags / bins bytes are cleared (every other byte of the ring is
-        // clear: a completed frame's accumulate clears its own)
-        for (const auto &g : pt->pipe) {
-            const size_t off = (size_t)g.slot * pt->pipe_cap, len = (size_t)g.frames * pt->pipe_np;
-            if (off + len > pt->cap) continue;
-            HIP_TRY(hipMemsetAsync(ring.sflags + off, 0, len, s));
-            if (!pt->shade_list) HIP_TRY(hipMemsetAsync(ring.mbin + off, 0xFF, len, s));
-        }
-        if (pt->ring_fresh) {  // a new allocation: everything
-            HIP_TRY(hipMemsetAsync(ring.sflags, 0, pt->cap, s));
-            if (!pt->shade_list) HIP_TRY(hipMemsetAsync(ring.mbin, 0xFF, pt->cap, s));
-            pt->ring_fresh = false;
-        }
-        pt->pipe.clear();
-        pt->half_pending = false;  // an iteration split over the last render and this one is dropped
-        pt->pipe_run = continued ? pt->pipe_run + 1 : 0;
-        pt->pipe_slots = K;
-        pt->pipe_np = np;
-        pt->pipe_cap = cap_paths;
-        std::memcpy(pt->pipe_key, key, sizeof(key));
-    } else {
-        pt->pipe_run++;
+    const PipeCommit commit = st.commit(plan, grew);
+    for (const PipeRange &d : commit.dropped) {
+        if (d.off + d.len > pt->cap) continue;
+        HIP_TRY(hipMemsetAsync(ring.sflags + d.off, 0, d.len, s));
+        if (!pt->shade_list) HIP_TRY(hipMemsetAsync(ring.mbin + d.off, 0xFF, d.len, s));
     }
-    pt->pipe_valid = true;
+    if (commit.reset && pt->ring_fresh) {  // a new allocation: everything
+        HIP_TRY(hipMemsetAsync(ring.sflags, 0, pt->cap, s));
+        if (!pt->shade_list) HIP_TRY(hipMemsetAsync(ring.mbin, 0xFF, pt->cap, s));
+        pt->ring_fresh = false;
+    }
     Queues &q = pt->q;
-    // the flags partition scans the slots in use: [0, end of the last frame group)
-    auto ring_end = [&]() {
-        size_t e = 0;
-        for (const auto &g : pt->pipe) e = std::max(e, (size_t)g.slot * cap_paths + (size_t)g.frames * np);
-        return (uint32_t)e;
-    };
     const uint32_t interleave0 = pt->primary_interleave;
-    // a render that starts nothing ahead and needs no frame in flight, small enough (one rank's
-    // tiles, small films): the whole frame in one persistent launch (pt_frame.hip), no
-    // per-bounce traversal drain, shade launch or partition
-    if (pt->frame_paths > 0.0 && !cx.stats && !speculate && pt->pipe.empty() && (double)np <= pt->frame_paths &&
-        frame_kernel_supported(pt->sc)) {
+    if (st.one_launch_frame(kn) && frame_kernel_supported(pt->sc)) {
         // this render's extension / shadow rays = the growth of the running totals from here
         HIP_TRY(hipMemcpyAsync(pt->ray_cum + 2, pt->ray_cum, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
         pt->snap_taken = true;
@@ -771,164 +626,98 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
                      interleave0 && fp.spp > 1 ? fp.spp : 0u, s);
         cx.ev1();
         launch_accumulate(fp, ring, nullptr, true, s);
-        pt->pipe_next_seed = launch->random_seed + fp.spp;
-        pt->last_iters = D;
-        pt->last_primary = np;
-        pt->primary_cum += np;
+        st.one_launch_frame_done();
+        pt->last_iters = fp.max_depth;
+        pt->last_primary = st.started;
+        pt->primary_cum += st.started;
         pt->frame_launches++;
         return PUPIL_OK;
     }
-    // AOV scratch of ring slot `slot`, frame `f` of its group: 7 floats per local pixel
-    auto scratch = [&](uint32_t slot, uint32_t f) { return pt->aov_scratch + ((size_t)slot * G + f) * 7 * nl; };
-    uint64_t started = 0;
-    // depths above 64: every 16 iterations the host reads the list lengths back and stops
-    // once no path is left (all of them missed, were absorbed or were terminated by RR)
-    const bool deep_exit = D > 64 && K == 1;
+    // AOV scratch of frame `index` of the ring (slot-major): 7 floats per local pixel
+    auto scratch = [&](uint32_t index) { return pt->aov_scratch + (size_t)index * 7 * nl; };
     pt->snap_taken = false;
-    // One iteration in two halves: (a) start a frame group if due, list the rays the previous
-    // shade spawned and trace them (with the new group's camera rays); (b) partition by
-    // material, shade.  Frame-group pacing runs (a) at the end of the render before the one
-    // that needs the iteration (below), (b) at that render's start.
-    using Half = pupil_pt::HalfIter;
-    // a render that starts on an empty pipeline (the first speculating render after a reset: it
-    // traces its own frame from the camera rays) starts at most PUPIL_PIPE_RAMP groups ahead;
-    // the renders after it fill the ring as before (one group more per iteration they run)
-    uint32_t ahead_started = 0;
-    bool fresh_start = false;
-    auto trace_half = [&](uint32_t it, uint32_t L_it, uint32_t run) -> int {
-        Half h{};
-        h.had = !pt->pipe.empty();
-        // start a frame group: this render's own on an empty pipeline (one frame unless
-        // speculating), else the next one ahead in the last run + 1 iterations while a slot is free
-        if (!h.had) fresh_start = true;
-        h.inject = !h.had || (speculate && pt->pipe.size() < K && it + run + 1 >= L_it &&
-                              (pt->pipe_ramp == 0 || !fresh_start || ahead_started < pt->pipe_ramp));
-        if (h.inject && h.had) ahead_started++;
-        // a group started on an empty pipeline (the render's own frame: after a reset, the first
-        // speculating render) holds one frame when the ramp is limited, so that render traces
-        // its own frame and at most PUPIL_PIPE_RAMP groups' first bounces, not G frames' worth
-        // (r06 pacing: the heaviest OnRun after the camera stops)
-        h.nf = pupil_pt::PipeFrame{0u, launch->random_seed, 0u, false,
-                                   speculate && (h.had || pt->pipe_ramp == 0) ? G : 1u, 0u};
-        if (h.inject && h.had) {
-            h.nf.slot = (pt->pipe.back().slot + 1) % K;
-            h.nf.seed = pt->pipe.back().seed + pt->pipe.back().frames * fp.spp;
-        }
-        h.nf.aov_scratch = h.had || h.nf.frames > 1;  // AOVs wait in the slot's scratch until the frame's render
-        h.nfp = (uint32_t)(h.nf.frames * np);          // paths of the new group
-        const uint32_t gspp = h.nf.frames * fp.spp;    // its samples per pixel
-        const uint32_t interleave = interleave0 && gspp > 1 ? gspp : 0u;
-        if (h.inject) {
+    // 1 = an early-exit check found nothing left to trace or shade: the frame is complete
+    auto trace = [&](const PipeTrace &t) -> int {
+        const uint32_t interleave = interleave0 && t.samples > 1 ? t.samples : 0u;
+        if (t.inject) {
             FrameParams fg = fp;
-            fg.seed0 = h.nf.seed;
-            fg.num_paths = h.nfp;
-            launch_generate(pt->sc, fg, cx.view(h.nf.slot, cap_paths), s, !pt->fresh());
-            started += h.nfp;
+            fg.seed0 = t.nf.seed;
+            fg.num_paths = t.nfp;
+            launch_generate(pt->sc, fg, cx.view(t.nf.slot, st.cap), s, !pt->fresh());
         }
-        if (h.had) {
+        if (t.had) {
             // the rays the previous iteration's shade spawned, over the slots in use, in
             // increasing path id: next (bit 0) and shadow (bit 1) lists -> q.nxsh
-            const uint32_t tag = pt->pipe_gen % 63u + 1u;
-            launch_partition(ring.sflags, ring_end(), 2, kPartFlags, tag, q.nxsh, q.hist, q.counts + kCntNext,
+            launch_partition(ring.sflags, t.ring_extent, 2, kPartFlags, t.read_tag, q.nxsh, q.hist, q.counts + kCntNext,
                              q.counts + kStartNext, nullptr, nullptr, s, pt->ray_cum,
                              pt->snap_taken ? nullptr : pt->ray_cum + 2);
             pt->snap_taken = true;
-            if (deep_exit && it % 16 == 0) {
+            if (t.check_exit) {
                 uint32_t c[2] = {1, 1};
                 HIP_TRY(hipMemcpyAsync(c, q.counts + kCntNext, sizeof(c), hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
-                if (c[0] == 0 && c[1] == 0) return 1;  // nothing left to trace or shade: the frame is complete
+                if (c[0] == 0 && c[1] == 0) return 1;
             }
             cx.ev0(1);
             cx.tail_slot();
-            if (h.inject)  // + the new group's camera rays, dequeued first in every chunk (pixel-major)
-                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, h.nfp, 0u,
-                                   (uint32_t)(h.nf.slot * cap_paths), interleave, nl);
+            if (t.inject)  // + the new group's camera rays, dequeued first in every chunk (pixel-major)
+                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, t.nfp, 0u, t.base, interleave, nl);
             else
                 launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s);
             cx.ev1();
         } else {
             cx.ev0(0);
             cx.tail_slot();
-            launch_extend(pt->sc, cx.view(h.nf.slot, cap_paths), q, nullptr, nullptr, h.nfp, pt->ovf, pt->ovf_threads,
+            launch_extend(pt->sc, cx.view(t.nf.slot, st.cap), q, nullptr, nullptr, t.nfp, pt->ovf, pt->ovf_threads,
                           cx.tsp(), s, interleave, nl);
             cx.ev1();
         }
-        if (h.inject) {  // the group is in flight from here (ring_end covers it)
-            h.nf.phases = 0;
-            pt->pipe.push_back(h.nf);
-        }
-        pt->half = h;
         return 0;
     };
-    auto shade_half = [&]() -> int {
-        const Half h = pt->half;
-        const uint32_t nring = ring_end();
+    auto shade = [&](const PipeShade &h) -> int {
         if (!pt->shade_list)  // material bins of every path traced in this iteration -> q.bins
-            launch_partition(ring.mbin, nring, kPartMaxBins, kPartExclusive, 0u, q.bins, q.hist, q.counts,
+            launch_partition(ring.mbin, h.ring_extent, kPartMaxBins, kPartExclusive, 0u, q.bins, q.hist, q.counts,
                              q.counts + kStartBins, q.counts + kScratch, nullptr, s, nullptr, nullptr, pt->bin_mask);
         FrameParams fs = fp;
-        fs.group = G;  // AOV frame of a sample: its group frame (samples per ring slot = G spp)
-        if (h.inject && h.nf.aov_scratch) {  // AOVs of frames ahead wait in their slot's scratch
-            fs.albedo = scratch(h.nf.slot, 0);
+        fs.group = st.G;  // AOV frame of a sample: its group frame (samples per ring slot = G spp)
+        if (h.aov_scratch) {
+            fs.albedo = scratch(h.aov_index);
             fs.normal = fs.albedo + 3 * (size_t)nl;
             fs.test = fs.albedo + 6 * (size_t)nl;
             fs.aov_local = 1;
             fs.aov_frame_stride = (uint32_t)(7 * nl);
         }
-        if (D > 63) HIP_TRY(hipMemsetAsync(ring.sflags, 0, nring, s));  // K = 1: tags would alias
-        const uint32_t wtag = (pt->pipe_gen + 1u) % 63u + 1u;
-        const ShadeList list =
-            !pt->shade_list ? kShadeBins : (h.had ? (h.inject ? kShadeNextRange : kShadeNext) : kShadeAll);
-        uint64_t live = 0;  // paths the launch may list
-        for (const auto &g : pt->pipe) live += (uint64_t)g.frames * np;
-        const uint32_t max_count = (uint32_t)std::min<uint64_t>(nring, live);
+        if (h.clear_flags) HIP_TRY(hipMemsetAsync(ring.sflags, 0, h.ring_extent, s));
+        constexpr ShadeList kLists[] = {kShadeAll, kShadeNext, kShadeNextRange};
+        const ShadeList list = pt->shade_list ? kLists[(int)h.list] : kShadeBins;
         cx.ev0(2);
-        launch_shade(pt->sc, fs, ring, q, wtag, s, list, (uint32_t)(h.nf.slot * cap_paths), h.inject ? h.nfp : 0u,
-                     max_count, pt->fresh(), h.nf.seed);
+        launch_shade(pt->sc, fs, ring, q, h.write_tag, s, list, h.range_base, h.range_n, h.max_count, pt->fresh(),
+                     h.range_seed);
         cx.ev1();
-        pt->pipe_gen++;
-        for (auto &f : pt->pipe) f.phases++;
         return 0;
     };
-    // the shade half of an iteration whose trace half the previous render ran (a reset above
-    // dropped it with the frames it belonged to)
-    if (pt->half_pending) {
-        pt->half_pending = false;
-        if (!reset)
-            if (const int rc = shade_half()) return rc;
-    }
-    // iterations this render needs: none when an earlier render completed its frame
-    const uint32_t L = pt->pipe.empty() ? D : D - pt->pipe.front().phases;
+    // the shade half of an iteration whose trace half the previous render ran (a reset dropped
+    // it with the frames it belonged to)
+    if (st.half_pending)
+        if (const int rc = shade(st.shade_half())) return rc;
+    const uint32_t L = st.iterations();
     for (uint32_t it = 0; it < L; it++) {
-        const int rc = trace_half(it, L, pt->pipe_run);
+        const int rc = trace(st.trace_half(kn, it, L));
         if (rc == 1) break;  // depth > 64: nothing left
         if (rc) return rc;
-        if (const int rs = shade_half()) return rs;
+        if (const int rs = shade(st.shade_half())) return rs;
     }
-    // this render's frame is complete: accumulate it; the group's slot is free once all
-    // its frames are accumulated
-    pupil_pt::PipeFrame &g = pt->pipe.front();
-    const uint32_t f = g.consumed;
     // (the accumulate clears the frame's flags bytes: no stale tag is ever listed again)
-    launch_accumulate(fp, cx.view(g.slot, cap_paths, (size_t)f * np), g.aov_scratch ? scratch(g.slot, f) : nullptr,
-                      true, s);
-    if (++g.consumed == g.frames) pt->pipe.erase(pt->pipe.begin());
-    // Frame-group pacing (r06): the render that displays a group's last frame, and would
-    // otherwise do no traversal, runs the trace half of the iteration the next render needs;
-    // that render starts with the shade half.  With G = 2 the traversal and the shade of every
-    // iteration land in different OnRuns (~0.8 / 0.2 of an iteration) instead of one OnRun
-    // doing all of it and the next none.  Speculative like the frames ahead: a reset drops it.
-    if (pt->pipe_split && speculate && G > 1 && L == 0 && !pt->pipe.empty() && pt->pipe.front().phases < D) {
-        const uint32_t L_next = D - pt->pipe.front().phases;
-        const int rc = trace_half(0, L_next, pt->pipe_run + 1);
+    const PipeFinish fin = st.finish(kn, L);
+    launch_accumulate(fp, cx.view(fin.slot, st.cap, fin.offset), fin.aov_scratch ? scratch(fin.aov_index) : nullptr, true, s);
+    if (fin.trace_ahead) {
+        const int rc = trace(st.trace_ahead(kn));
         if (rc < 0) return rc;
-        pt->half_pending = rc == 0;
+        st.half_ran(rc == 0);
     }
-    pt->pipe_next_seed = launch->random_seed + fp.spp;
     pt->last_iters = L;
-    pt->last_primary = started;
-    pt->primary_cum += started;
+    pt->last_primary = st.started;
+    pt->primary_cum += st.started;
     return PUPIL_OK;
 }
 
@@ -1111,20 +900,21 @@ void read_knobs(pupil_pt *pt) {
     if (const char *po = std::getenv("PUPIL_PRIMARY_ORDER")) pt->primary_interleave = std::strcmp(po, "path") != 0;
     derive_bins(pt);
     if (const char *fr = std::getenv("PUPIL_FRESH_SHADE")) pt->fresh_shade = std::atoi(fr) != 0;
-    if (const char *a = std::getenv("PUPIL_AHEAD")) pt->ahead_mode = std::min(2, std::max(0, std::atoi(a)));
-    if (const char *k = std::getenv("PUPIL_PIPE")) pt->pipe_limit = (uint32_t)std::min(63, std::max(0, std::atoi(k)));
+    if (const char *a = std::getenv("PUPIL_AHEAD")) pt->knobs.ahead_mode = std::min(2, std::max(0, std::atoi(a)));
+    if (const char *k = std::getenv("PUPIL_PIPE")) pt->knobs.limit = (uint32_t)std::min(63, std::max(0, std::atoi(k)));
     {  // ring budget: a quarter of the device memory free now (after the scene and its BVH)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        pt->pipe_budget = 0.25 * (double)free_b;
+        pt->knobs.budget = 0.25 * (double)free_b;
     }
-    if (const char *g = std::getenv("PUPIL_PIPE_GB")) pt->pipe_budget = std::max(0.0, std::atof(g)) * 1e9;
-    if (const char *g = std::getenv("PUPIL_PIPE_PATHS")) pt->pipe_paths = std::max(1.0, std::atof(g));
-    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_PATHS")) pt->pipe_group_paths = std::max(1.0, std::atof(g));
-    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_MAX")) pt->pipe_group_max = (uint32_t)std::min(64, std::max(1, std::atoi(g)));
-    if (const char *g = std::getenv("PUPIL_PIPE_SPLIT")) pt->pipe_split = std::atoi(g) != 0;
-    if (const char *g = std::getenv("PUPIL_PIPE_RAMP")) pt->pipe_ramp = (uint32_t)std::max(0, std::atoi(g));
-    if (const char *g = std::getenv("PUPIL_FRAME_PATHS")) pt->frame_paths = std::max(0.0, std::atof(g));
+    if (const char *g = std::getenv("PUPIL_PIPE_GB")) pt->knobs.budget = std::max(0.0, std::atof(g)) * 1e9;
+    if (const char *g = std::getenv("PUPIL_PIPE_PATHS")) pt->knobs.paths = std::max(1.0, std::atof(g));
+    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_PATHS")) pt->knobs.group_paths = std::max(1.0, std::atof(g));
+    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_MAX")) pt->knobs.group_max = (uint32_t)std::min(64, std::max(1, std::atoi(g)));
+    if (const char *g = std::getenv("PUPIL_PIPE_GROUP_ALL")) pt->knobs.group_all = std::atoi(g) != 0;
+    if (const char *g = std::getenv("PUPIL_PIPE_SPLIT")) pt->knobs.split = std::atoi(g) != 0;
+    if (const char *g = std::getenv("PUPIL_PIPE_RAMP")) pt->knobs.ramp = (uint32_t)std::max(0, std::atoi(g));
+    if (const char *g = std::getenv("PUPIL_FRAME_PATHS")) pt->knobs.frame_paths = std::max(0.0, std::atof(g));
     sc.trace_node_min = 8;  // node phase ends below 8 active lanes (7 waves: 8 and 12 beat 4 by 1.5 %; 2 is slower)
     if (const char *r = std::getenv("PUPIL_NODE_MIN")) sc.trace_node_min = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
 }
@@ -1301,7 +1091,7 @@ int pupil_pt_set_camera(pupil_pt *pt, const float sample_to_camera[16], const fl
     if (!pt || !sample_to_camera || !camera_to_world) return fail(PUPIL_ERR_INVALID, "null argument");
     if (std::memcmp(pt->sc.camera.s2c, sample_to_camera, sizeof(pt->sc.camera.s2c)) != 0 ||
         std::memcmp(pt->sc.camera.c2w, camera_to_world, sizeof(pt->sc.camera.c2w)) != 0)
-        pt->pipe_valid = false;  // frames in flight were started with the old view
+        pt->pipe.invalidate();  // frames in flight were started with the old view
     std::memcpy(pt->sc.camera.s2c, sample_to_camera, sizeof(pt->sc.camera.s2c));
     std::memcpy(pt->sc.camera.c2w, camera_to_world, sizeof(pt->sc.camera.c2w));
     return PUPIL_OK;
@@ -1335,7 +1125,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     if (n == 0) return PUPIL_OK;
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
-    pt->pipe_valid = false;             // frames in flight were traced against the old geometry
+    pt->pipe.invalidate();          // frames in flight were traced against the old geometry
     std::vector<uint32_t> changed;
     bool emitters_moved = false;  // device-side emitter table: a transform of an emissive instance
     for (uint32_t k = 0; k < n; k++) {
@@ -1390,7 +1180,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(order_after_renders(pt));  // no render may still read the old vertices
-    pt->pipe_valid = false;             // frames in flight were traced against the old geometry
+    pt->pipe.invalidate();          // frames in flight were traced against the old geometry
     const size_t bytes = sizeof(float) * 3 * (size_t)sd.num_vertices;
     if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
         HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
@@ -1469,7 +1259,7 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     if (scene->num_area_emitters && !scene->area_emitters) return fail(PUPIL_ERR_INVALID, "missing emitter array");
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
-    pt->pipe_valid = false;
+    pt->pipe.invalidate();
     bool in_place = pt->d_areas && scene->num_area_emitters == pt->sc.num_areas && same_env(pt, scene);
     for (uint32_t e = 0; in_place && e < scene->num_area_emitters; e++)
         in_place = scene->area_emitters[e].radiance.type != PUPIL_TEX_BITMAP;
@@ -1514,7 +1304,7 @@ int pupil_pt_enable_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene)
         if (const int rc = device_emitter_tables(pt, scene, emit_inst, inst_weight)) return rc;
     }
     HIP_TRY(order_after_renders(pt));  // no render may still read the table
-    pt->pipe_valid = false;
+    pt->pipe.invalidate();
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     if (const int rc = device_emitter_setup(pt, scene)) return rc;
     if (const int rc = rebuild_emitters(pt)) return rc;
@@ -1527,7 +1317,7 @@ int pupil_pt_refresh_emitters(pupil_pt *pt) {
     if (!pt->dev_emit) return fail(PUPIL_ERR_INVALID, "the device-side emitter table is not enabled");
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
-    pt->pipe_valid = false;  // frames in flight were shaded with the old table
+    pt->pipe.invalidate();  // frames in flight were shaded with the old table
     return rebuild_emitters(pt);
 }
 
@@ -1585,7 +1375,7 @@ int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
         }
     }
     HIP_TRY(order_after_renders(pt));  // no render may still read the old materials
-    pt->pipe_valid = false;             // frames in flight were shaded with them
+    pt->pipe.invalidate();          // frames in flight were shaded with them
     bool type_changed = false;
     for (uint32_t k = 0; k < n; k++) {
         if (!last[k]) continue;
@@ -1642,7 +1432,7 @@ int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slo
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(order_after_renders(pt));  // no render may still read the old texels
-    pt->pipe_valid = false;
+    pt->pipe.invalidate();
     HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));  // after the caller's work; no device-wide sync
     HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
     HIP_TRY(hipMemcpyAsync((void *)t.data, rgba_device, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice,
@@ -1782,12 +1572,11 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     unsigned long long cum[4] = {0, 0, 0, 0};  // running totals, then their values before the last render
     HIP_TRY(hipMemcpy(cum, pt->ray_cum, sizeof(cum), hipMemcpyDeviceToHost));
     c.rays_traced_total = pt->primary_cum + cum[0] + cum[1];
-    c.frames_in_flight = 0;  // frames started ahead of the next render (in groups: not yet accumulated)
-    for (const auto &g : pt->pipe) c.frames_in_flight += g.frames - g.consumed;
-    c.pipeline_slots = pt->pipe_slots;
+    c.frames_in_flight = pt->pipe.frames_in_flight();
+    c.pipeline_slots = pt->pipe.slots;
     c.tlas_sah_splits = pt->accel.two_level ? pt->accel.tl.sah_splits : 0u;
     c.ring_bytes = pt->ring_bytes + sizeof(float) * (uint64_t)pt->aov_cap;
-    c.ring_budget_bytes = (uint64_t)pt->pipe_budget;
+    c.ring_budget_bytes = (uint64_t)pt->knobs.budget;
     c.accel_refits = pt->accel.refits;
     for (const DevInstance &d : pt->h_insts) c.hidden_instances += d.hidden ? 1u : 0u;
     c.frame_launches = pt->frame_launches;

@@ -1,4 +1,6 @@
-"""Offline model of render_pipelined's frame schedule (engine.hip) for the OnRun cadence:
+"""Offline model of the frame schedule (csrc/host/pipe_schedule.h: PipeState::trace_half /
+shade_half / finish are the source it models; tests/test_pipe_schedule_host.py walks the real
+one) for the OnRun cadence:
 per render, the frame-bounces it traces (x0.8) and shades (x0.2), for injection rules of the
 pipeline fill (r06 pacing study).  Units: a lone 1-spp frame of depth D = D.
 The model's per-render shape matches the measured OnRun times of profiles/r06_pacing.txt
