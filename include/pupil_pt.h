@@ -308,7 +308,15 @@ typedef struct pupil_pt_counters {
     /* ABI 6.  Device time of those one-launch frames (collect_stats bit 1 / 2): the frame kernel
      * traces and shades, so it is kept out of trace_ms */
     double frame_ms;
-    uint64_t coop_dma;   /* reserved, always 0 */
+    /* Terminal extension rays (those feeding the last shade of a path, which can only add the
+     * emission of the primitive it hits) resolved by the emitter test instead of a BVH walk,
+     * since the engine was created (a running total, like rays_traced_total).  They stay counted
+     * in extension_rays and rays_traced_total: those count rays resolved.  It does not grow while the
+     * scene has no cull set (environment map, more emissive primitives than the cap, object-mode
+     * two-level structure, PUPIL_TERMINAL_CULL=0) and keeps its value when a set goes away: 0
+     * only for an engine that never had one.  In the slot that was reserved as coop_dma
+     * (always 0 until now): the struct keeps its size and no ABI bump is needed */
+    uint64_t terminal_rays_culled;
     uint64_t coop_slots; /* reserved, always 0 */
     /* instances whose visibility mask hides them now (pupil_pt_update_instances_masked);
      * appended without an ABI bump: detect the entry by its symbol */

@@ -100,7 +100,9 @@ class Counters(C.Structure):
                 ("leaf_loop_lanes", C.c_uint64), ("refills", C.c_uint64), ("refill_lanes", C.c_uint64),
                 ("frame_launches", C.c_uint64),
                 # ABI 6
-                ("frame_ms", C.c_double), ("coop_dma", C.c_uint64), ("coop_slots", C.c_uint64),
+                ("frame_ms", C.c_double),
+                # the terminal-ray cull's running total, in the slot once reserved as coop_dma
+                ("terminal_rays_culled", C.c_uint64), ("coop_slots", C.c_uint64),
                 # appended with pupil_pt_update_instances_masked (no ABI bump: detect the symbol)
                 ("hidden_instances", C.c_uint64)]
 

@@ -120,6 +120,18 @@ struct pupil_pt {
     // render's own counts are [0..1] - [2..3] without a per-render clear (snap_taken)
     unsigned long long *ray_cum = nullptr;
     bool snap_taken = false;
+    // Terminal-ray cull (pt_shade.h terminal_ray_culled; PUPIL_TERMINAL_CULL=0 turns it off,
+    // PUPIL_TERMINAL_CULL_K sets the cap on the set).  d_cull: the scan's count, then the set
+    // DeviceScene::cull_set points at.  cull_cum: the sharded running total of culled rays, then
+    // its copy from the start of the last render, so that render's own count is the difference
+    // (cull_counted: some render has run with a set, the copies are being made)
+    bool cull_on = true;
+    uint32_t cull_k = 8;
+    uint32_t *d_cull = nullptr;
+    unsigned long long *cull_cum = nullptr;
+    bool cull_counted = false;
+    uint32_t cull_scanned = 0;  // entries of d_cull the last scan left, sorted (0: no scan holds for the records as they are)
+    bool cull_last = false;  // the last counted work was a render (a ray query culls nothing)
     uint64_t primary_cum = 0;                      // host running total of camera rays
     uint32_t last_paths = 0, last_iters = 0;
     uint64_t last_primary = 0;
@@ -900,6 +912,9 @@ void read_knobs(pupil_pt *pt) {
     if (const char *po = std::getenv("PUPIL_PRIMARY_ORDER")) pt->primary_interleave = std::strcmp(po, "path") != 0;
     derive_bins(pt);
     if (const char *fr = std::getenv("PUPIL_FRESH_SHADE")) pt->fresh_shade = std::atoi(fr) != 0;
+    if (const char *tc = std::getenv("PUPIL_TERMINAL_CULL")) pt->cull_on = std::atoi(tc) != 0;
+    if (const char *tk = std::getenv("PUPIL_TERMINAL_CULL_K"))
+        pt->cull_k = (uint32_t)std::min((int)kCullSetMax, std::max(1, std::atoi(tk)));
     if (const char *a = std::getenv("PUPIL_AHEAD")) pt->knobs.ahead_mode = std::min(2, std::max(0, std::atoi(a)));
     if (const char *k = std::getenv("PUPIL_PIPE")) pt->knobs.limit = (uint32_t)std::min(63, std::max(0, std::atoi(k)));
     {  // ring budget: a quarter of the device memory free now (after the scene and its BVH)
@@ -923,15 +938,63 @@ void read_knobs(pupil_pt *pt) {
 int alloc_workspace(pupil_pt *pt) {
     pt->ovf_threads = trace_grid_blocks() * (uint32_t)kTraceBlock;
     if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * kStackOvf) || pt->alloc(&pt->trace_counters, 32) ||
-        pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->q.counts, kCountSlots) || pt->alloc(&pt->q.work, kWorkSlots))
+        pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->q.counts, kCountSlots) || pt->alloc(&pt->q.work, kWorkSlots) ||
+        pt->alloc(&pt->d_cull, 1 + kCullSetMax) || pt->alloc(&pt->cull_cum, 2 * kCullShards * kCullStride))
         return fail(PUPIL_ERR_OOM, "workspace allocation failed");
     if (hipMemset(pt->q.work, 0, kWorkSlots * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(pt->cull_cum, 0, 2 * kCullShards * kCullStride * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(pt->ray_cum, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
         return fail(PUPIL_ERR_HIP, "workspace clear failed");
     if (hipEventCreate(&pt->ev_begin) != hipSuccess || hipEventCreate(&pt->ev_end) != hipSuccess ||
         hipEventCreateWithFlags(&pt->ev_sync, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&pt->ev_verts, hipEventDisableTiming) != hipSuccess)
         return fail(PUPIL_ERR_HIP, "event creation failed");
+    return PUPIL_OK;
+}
+
+// ------------------------------------------------------------------ terminal-ray cull set
+// DeviceScene::cull_set from the structure and the tables as they are now: the record slots of
+// every primitive of an instance that carries emitters, found by a scan of the traversal's own
+// world-space records (a refit keeps them, a rebuild moves them) and sorted.  Called whenever the
+// structure, an instance, the materials or the emitter tables change, on the engine's stream,
+// which the caller has ordered after the renders; returns when the set is written.
+// records_changed = false (material and emitter-table updates, which move no record and change no
+// instance's emitter range): only whether the scene may have a set is decided anew, and the last
+// scan is reused while it holds -- no pass over the records, no synchronisation.  No set (every
+// extension ray is traced, as before the cull existed) when the knob is off, the scene has an env
+// emitter (a terminal miss adds radiance), the traversal reads object-space records (two-level
+// object mode) or the emissive primitives number more than the cap (emissive meshes).  An
+// emitter of zero radiance stays in the set: its hit still multiplies the path's throughput by
+// that zero (inf * 0), which only the shade itself restates.
+int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
+    DeviceScene &sc = pt->sc;
+    sc.cull_set = pt->d_cull + 1;
+    sc.cull_n = 0;
+    if (records_changed) pt->cull_scanned = 0;
+    if (!pt->cull_on || sc.has_env || !sc.prims || (sc.two_level && !sc.tl_world)) return PUPIL_OK;
+    uint64_t emissive = 0;  // primitives: a mesh instance's faces, a sphere
+    for (size_t i = 0; i < pt->h_insts.size(); i++) {
+        const DevInstance &d = pt->h_insts[i];
+        if (d.emitter_offset < 0) continue;
+        emissive += d.kind == PUPIL_SHAPE_MESH ? pt->shapes[pt->accel.inst_shape[i]].num_faces : 1u;
+    }
+    if (emissive == 0 || emissive > pt->cull_k) return PUPIL_OK;
+    if (pt->cull_scanned == emissive) {  // the records have not moved since the scan
+        sc.cull_n = pt->cull_scanned;
+        return PUPIL_OK;
+    }
+    uint32_t found[1 + kCullSetMax] = {};
+    HIP_TRY(hipMemsetAsync(pt->d_cull, 0, sizeof(found), pt->own_stream));
+    launch_cull_scan(sc.prims, pt->accel.world_record_slots(), pt->d_insts, (uint32_t)pt->h_insts.size(), pt->d_cull,
+                     kCullSetMax, pt->own_stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(found, pt->d_cull, sizeof(found), hipMemcpyDeviceToHost, pt->own_stream));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (found[0] != emissive) return PUPIL_OK;  // the records do not show what the tables say: no set
+    std::sort(found + 1, found + 1 + found[0]);
+    HIP_TRY(hipMemcpyAsync(pt->d_cull, found, sizeof(found), hipMemcpyHostToDevice, pt->own_stream));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    sc.cull_n = pt->cull_scanned = found[0];
     return PUPIL_OK;
 }
 
@@ -1008,7 +1071,7 @@ int rebuild_emitters(pupil_pt *pt) {
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     pt->emit_refreshes++;
     pt->emit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PUPIL_OK;
+    return derive_cull_set(pt, false);
 }
 
 // pupil_pt_update_emitters replaced the table: the device-side mode stays on when the new scene
@@ -1077,6 +1140,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     if (!rc) read_knobs(pt);
     if (!rc) rc = alloc_workspace(pt);
     if (!rc) rc = pt->accel.publish();
+    if (!rc) rc = derive_cull_set(pt);
     if (rc) {
         delete pt;
         return rc;
@@ -1152,6 +1216,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     pt->accel.refits++;  // once the tables have changed, before the structure follows: a failed update counts
     if (const int rc = pt->accel.update_instances(changed)) return rc;
     pt->totals.build_ms = pt->accel.ms;
+    if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
     if (pt->dev_emit && emitters_moved) return rebuild_emitters(pt);
     return PUPIL_OK;
 }
@@ -1199,6 +1264,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
         pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     pt->accel.refits++;  // only once the structure has followed: a failed update does not count
+    if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
     if (pt->dev_emit && emissive) return rebuild_emitters(pt);
     return PUPIL_OK;
 }
@@ -1282,11 +1348,13 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
                 HIP_TRY(hipMemcpyAsync(pt->d_guide, pt->h_emit_guide.data(), sizeof(uint32_t) * pt->h_emit_guide.size(),
                                        hipMemcpyHostToDevice, pt->own_stream));
             HIP_TRY(hipStreamSynchronize(pt->own_stream));
+            if (const int rc = derive_cull_set(pt, false)) return rc;
             return keep_device_emitters(pt, scene);
         }
     }
     HIP_TRY(hipStreamSynchronize(pt->own_stream));  // the old tables are freed below
     if (const int rc = upload_emitters(pt, scene)) return rc;
+    if (const int rc = derive_cull_set(pt, false)) return rc;  // the scene may have gained or lost its env emitter
     return keep_device_emitters(pt, scene);
 }
 
@@ -1411,7 +1479,7 @@ int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
     for (void *p : stale) pt->release(p);  // the stream has passed them
     pt->mat_updates++;
     pt->mat_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PUPIL_OK;
+    return derive_cull_set(pt, false);
 }
 
 // The texels of one bitmap slot from device memory, ordered like PUPIL_VERTS_DEVICE: an event on
@@ -1507,6 +1575,12 @@ int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_laun
     fp.normal = (float *)out->normal;
     fp.test = (float *)out->test;
     fp.nee_count = stats ? pt->trace_counters + 16 : nullptr;
+    fp.cull_cum = pt->sc.cull_n ? pt->cull_cum : nullptr;
+    // the culled-ray totals as they are before this render (pupil_pt_stats: its own count)
+    pt->cull_counted = pt->cull_counted || pt->sc.cull_n != 0u;
+    if (pt->cull_counted)
+        HIP_TRY(hipMemcpyAsync(pt->cull_cum + kCullShards * kCullStride, pt->cull_cum,
+                               sizeof(unsigned long long) * kCullShards * kCullStride, hipMemcpyDeviceToDevice, s));
 
     // PUPIL_STATS_TRACE_TIMING: events around the traversal launches only, summed over
     // every render since pupil_pt_stats last read them (a timed sequence of renders)
@@ -1559,6 +1633,7 @@ int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_laun
     pt->trace_pairs = cx.pair;
     pt->last_paths = fp.num_paths;
     pt->last_stats = stats;
+    pt->cull_last = true;
     pt->last_stream = s;
     pt->rendered = true;
     return PUPIL_OK;
@@ -1571,7 +1646,17 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     pupil_pt_counters c = pt->totals;
     unsigned long long cum[4] = {0, 0, 0, 0};  // running totals, then their values before the last render
     HIP_TRY(hipMemcpy(cum, pt->ray_cum, sizeof(cum), hipMemcpyDeviceToHost));
-    c.rays_traced_total = pt->primary_cum + cum[0] + cum[1];
+    // extension rays the terminal-ray cull resolved: in all, and before the last render
+    unsigned long long culled[2] = {0, 0};
+    if (pt->cull_counted) {
+        std::vector<unsigned long long> shards(2 * kCullShards * kCullStride);
+        HIP_TRY(hipMemcpy(shards.data(), pt->cull_cum, sizeof(unsigned long long) * shards.size(), hipMemcpyDeviceToHost));
+        for (uint32_t h = 0; h < 2; h++)
+            for (uint32_t k = 0; k < kCullShards; k++) culled[h] += shards[(h * kCullShards + k) * kCullStride];
+    }
+    c.terminal_rays_culled = culled[0];
+    // rays resolved: a culled ray was cast by the integrator and is counted like a traced one
+    c.rays_traced_total = pt->primary_cum + cum[0] + cum[1] + culled[0];
     c.frames_in_flight = pt->pipe.frames_in_flight();
     c.pipeline_slots = pt->pipe.slots;
     c.tlas_sah_splits = pt->accel.two_level ? pt->accel.tl.sah_splits : 0u;
@@ -1586,7 +1671,8 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
         // flight; a render whose only iteration traced camera rays lists none)
         c.primary_rays = pt->last_primary;
         c.path_samples = pt->last_paths;
-        c.extension_rays = pt->snap_taken ? cum[0] - cum[2] : 0u;
+        const unsigned long long culled_last = pt->cull_last ? culled[0] - culled[1] : 0ull;  // by the last render
+        c.extension_rays = (pt->snap_taken ? cum[0] - cum[2] : 0u) + culled_last;
         c.shadow_rays = pt->snap_taken ? cum[1] - cum[3] : 0u;
         float ms = 0.f;
         if (pt->last_timed) HIP_TRY(hipEventElapsedTime(&ms, pt->ev_begin, pt->ev_end));
@@ -1659,10 +1745,12 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
             c.prim_tests = tc[1] + tc[15];
             c.shadow_rays_reference = tc[16];
             c.unique_node_fetches = tc[18];
-            c.queue_handed = tc[20];
-            c.queue_activated = tc[21];
-            c.queue_retired = tc[22];
-            c.queue_listed = tc[23];
+            // every ray the integrator handed over, each exactly once: the persistent launches'
+            // counters, and the rays the terminal-ray cull took and resolved in its one step
+            c.queue_handed = tc[20] + culled_last;
+            c.queue_activated = tc[21] + culled_last;
+            c.queue_retired = tc[22] + culled_last;
+            c.queue_listed = tc[23] + culled_last;
             c.extend_node_visits = tc[0];
             c.extend_prim_tests = tc[1];
             const double rays = (double)(c.primary_rays + c.extension_rays + c.shadow_rays);
@@ -1731,6 +1819,7 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
         pt->last_stats = true;
         pt->last_timed = true;
         pt->snap_taken = false;
+        pt->cull_last = false;
         pt->trace_pairs = 0;
         for (int k = 0; k < 4; k++) pt->kept_ms[k] = 0.0, pt->kept_n[k] = 0;
         pt->rendered = true;
@@ -1965,7 +2054,8 @@ int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value) {
                                hipMemcpyHostToDevice, pt->own_stream));
         HIP_TRY(hipStreamSynchronize(pt->own_stream));
     }
-    return pt->accel.publish();
+    if (const int rc = pt->accel.publish()) return rc;
+    return derive_cull_set(pt);
 }
 
 int pupil_debug_bvh_reinsert(int device, uint32_t n, const float *boxes, uint32_t rounds, double *cost,

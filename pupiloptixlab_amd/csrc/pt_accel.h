@@ -61,6 +61,10 @@ struct SceneAccel {
     // the material bins of instances changed (insts / d_insts hold the new ones): the bin words of
     // the record slots follow, enqueued on the stream.  No box or link changes: not a refit
     void update_bins();
+    // slots of the world-space records update_bins walks (the flattened BVH's, or the two-level
+    // world records; world mode: with the spheres' leaves), the array the terminal-ray cull set
+    // indexes when the traversal reads it (DeviceScene::prims: flat and world mode)
+    uint32_t world_record_slots() const;
     int publish();
     // BVH4 node array the traversal walks (its size bounds the 32-bit node offsets, kMaxNodes4)
     uint64_t nodes4_count() const;

@@ -216,12 +216,16 @@ int SceneAccel::update_instances(const std::vector<uint32_t> &changed) {
 // The records that carry a bin word: the flattened BVH's, or the two-level world records (world
 // mode: with one two-slot leaf per sphere appended; object mode traverses with the instances'
 // own bins, its world records are kept consistent all the same).
-void SceneAccel::update_bins() {
-    const std::vector<DevInstance> &insts = *t.insts;
+uint32_t SceneAccel::world_record_slots() const {
     uint64_t slots = two_level ? tl.num_wprims : bvh.num_records;
     if (two_level && tl.world)
-        for (const DevInstance &d : insts) slots += d.kind == PUPIL_SHAPE_SPHERE ? 2u : 0u;
-    launch_record_bins(two_level ? tl.wprims : bvh.prims, (uint32_t)slots, t.d_insts, (uint32_t)insts.size(), t.stream);
+        for (const DevInstance &d : *t.insts) slots += d.kind == PUPIL_SHAPE_SPHERE ? 2u : 0u;
+    return (uint32_t)slots;
+}
+
+void SceneAccel::update_bins() {
+    launch_record_bins(two_level ? tl.wprims : bvh.prims, world_record_slots(), t.d_insts, (uint32_t)t.insts->size(),
+                       t.stream);
 }
 
 // Flattened BVH: the shape's instances are flagged moved, refit_bvh4 rewrites their world records

@@ -149,6 +149,20 @@ __global__ __launch_bounds__(kEmitBlock) void k_emit_guide(EmitterJob job) {
     job.guide[k] = lo;
 }
 
+// The terminal-ray cull set's scan (engine.hip derive_cull_set): the record slots whose instance
+// carries emitters.  A hole slot names no instance (kRecHole); a hidden instance's slots are
+// listed too -- their NaN vertices fail the cull's test exactly as they fail the traversal's.
+__global__ __launch_bounds__(kEmitBlock) void k_cull_scan(const float4 *recs, uint32_t slots,
+                                                          const DevInstance *instances, uint32_t num_instances,
+                                                          uint32_t *out, uint32_t cap) {
+    const uint32_t r = blockIdx.x * kEmitBlock + threadIdx.x;
+    if (r >= slots) return;
+    const uint32_t id = __float_as_uint(recs[(size_t)kRecF4 * r + 1].w);
+    if (id >= num_instances || instances[id].emitter_offset < 0) return;
+    const uint32_t k = atomicAdd(out, 1u);
+    if (k < cap) out[1u + k] = r;
+}
+
 }  // namespace
 
 void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s) {
@@ -162,6 +176,13 @@ void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s) {
         const uint32_t entries = (1u << job.guide_bits) + 1u;
         hipLaunchKernelGGL(k_emit_guide, dim3((entries + kEmitBlock - 1) / kEmitBlock), dim3(kEmitBlock), 0, s, job);
     }
+}
+
+void launch_cull_scan(const float4 *recs, uint32_t slots, const DevInstance *instances, uint32_t num_instances,
+                      uint32_t *out, uint32_t cap, hipStream_t s) {
+    if (!recs || slots == 0u) return;
+    hipLaunchKernelGGL(k_cull_scan, dim3((slots + kEmitBlock - 1) / kEmitBlock), dim3(kEmitBlock), 0, s, recs, slots,
+                       instances, num_instances, out, cap);
 }
 
 }  // namespace pupil

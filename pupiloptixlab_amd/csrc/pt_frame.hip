@@ -181,6 +181,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(kFr
                     flags = shade_path<MAT>(sc, fp, ps, q, miss ? 0u : (sc.single_bin ? sc.single_bin : ps.mbin[q]));
                     if (!sc.single_bin) ps.mbin[q] = 0xFFu;  // the bins-mode invariant: untraced paths read 0xFF
                 }
+                // an extension ray the terminal-ray cull resolved is counted here, not by n_ext, and
+                // never queued (the engine adds both totals)
+                count_culled(fp, flags);
                 // both rays of the bounce are traced in the next round, concurrently; the round ends
                 // before any path is shaded again, so a shadow contribution is always added before
                 // the next bounce's shade adds to the radiance (main.cu:119-140 before :165-185)

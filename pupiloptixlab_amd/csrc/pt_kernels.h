@@ -69,6 +69,11 @@ constexpr uint32_t kStartNext = 25, kStartShadow = 26;                 // next /
 constexpr uint32_t kScratch = 27;
 constexpr uint32_t kCountSlots = 32;
 
+// Terminal-ray cull: the largest cull set (DeviceScene::cull_set; the engine's cap is
+// PUPIL_TERMINAL_CULL_K, 8 unless set) and the sharded counter of culled rays
+constexpr uint32_t kCullSetMax = 32;
+constexpr uint32_t kCullShards = 64, kCullStride = 16;  // counters, and 64-bit words between two
+
 struct Queues {
     uint32_t *bins;      // capacity: material bin b occupies [counts[kStartBins + b], + counts[b])
     uint32_t *nxsh;      // 2 * capacity: next ids from counts[kStartNext] (= 0), shadow ids from counts[kStartShadow]
@@ -101,6 +106,10 @@ struct FrameParams {
     float *normal;
     float *test;
     unsigned long long *nee_count;  // collect_stats: paths that reached the shadow test (main.cu:113-123)
+    // terminal-ray cull (pt_shade.h terminal_ray_culled): running total of the extension rays the
+    // emitter test resolved, kCullShards counters one 128-B line apart (a wave adds to the one of
+    // its block); null = the cull is off for this render
+    unsigned long long *cull_cum;
     // shade: the AOV pointers above are indexed by the local pixel (compact output, or the
     // per-slot AOV scratch of a frame that completes in a later render); else by y*w+x
     uint32_t aov_local;
@@ -246,6 +255,10 @@ struct EmitterJob {
     float *sum;                 // scratch, one float
 };
 void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s);
+// the cull set's scan (pt_emitters.hip): out[0] (zero at launch) counts the record slots of `recs`
+// whose instance is emissive, out[1 + k] holds the k-th found for k < cap, in no order
+void launch_cull_scan(const float4 *recs, uint32_t slots, const DevInstance *instances, uint32_t num_instances,
+                      uint32_t *out, uint32_t cap, hipStream_t s);
 // GetPixelAverage (optix_material.cpp:15-42) in two halves the host (engine.hip pixel_average) and
 // the device (pt_materials.hip) share: the average of a texture without texels, and of a bitmap
 // from the sequential float sums of its r, g, b (vec3 / float multiplies by the reciprocal)

@@ -110,6 +110,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(4))
             if (m && __lane_id() == __ffsll((unsigned long long)__builtin_amdgcn_read_exec()) - 1)
                 atomicAdd(fp.nee_count, (unsigned long long)__popcll(m));
         }
+        count_culled(fp, flags);
         ps.sflags[p] = (uint8_t)((flags & 3u) | tag << 2);
         if (LIST == kShadeBins) ps.mbin[p] = 0xFFu;  // listed again only if the next extend traces this path
     }
@@ -142,6 +143,7 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(sha
             if (m && __lane_id() == __ffsll((unsigned long long)__builtin_amdgcn_read_exec()) - 1)
                 atomicAdd(fp.nee_count, (unsigned long long)__popcll(m));
         }
+        count_culled(fp, flags);
         ps.sflags[p] = (uint8_t)((flags & 3u) | tag << 2);
     }
 }

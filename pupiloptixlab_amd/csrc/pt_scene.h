@@ -203,6 +203,12 @@ struct DeviceScene {
     uint32_t num_areas;
     uint32_t has_env;
     const DevEmitter *env;
+    // Terminal-ray cull set (engine.hip derive_cull_set): the record slots in `prims` of every
+    // emissive primitive, in increasing order, when there are at most kCullSetMax of them, the
+    // scene has no env emitter and `prims` holds world-space records (flat BVH, two-level world
+    // mode).  cull_n = 0: no set, every extension ray is traced
+    const uint32_t *cull_set;
+    uint32_t cull_n;
     Camera camera;
 };
 

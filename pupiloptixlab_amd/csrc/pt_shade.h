@@ -190,7 +190,9 @@ __device__ __forceinline__ const DevEmitter *select_emitter(const DeviceScene &s
 
 // One path that hit a surface of material MAT (0 = unknown type): emission and
 // MIS at the hit, loop head, NEE sample, BSDF sample (main.cu:84-163).
-// Returns the next/shadow flags byte (bit 0 extension ray, bit 1 shadow ray).
+// Returns the next/shadow flags byte (bit 0 extension ray, bit 1 shadow ray), bit 2 for the
+// reference's shadow-ray count and bit 3 for an extension ray the terminal-ray cull resolved
+// (count_culled; never both bits 0 and 3).
 // p: path id (in a pipelined ring: slot * num_paths + sample * num_local + local pixel);
 // its bounce is PathState::misc.y (loaded inside shade_hit / shade_miss: passing the
 // record in from the launch kept it live across the whole shade, 137 instead of 123
@@ -205,12 +207,39 @@ __device__ __forceinline__ bool last_sample(const FrameParams &fp, uint32_t p, u
     return q - s * fp.spp + 1u == fp.spp;
 }
 
+// Terminal-ray cull.  The extension ray (o, d) feeds the path's last shade (bounce + 1 >=
+// max_depth there), which can only add the emission of the primitive the ray hits first; the scene
+// has no env emitter, so a miss adds nothing.  True when the ray hits none of the scene's emissive
+// primitives (DeviceScene::cull_set) over [0.001, kMaxDistance]: the traversal could then report
+// none of them either, whatever lies in front, and the path is dead.  The test is the traversal's
+// own (intersect_leaf_dyn: ray_pre, intersect_triangle / intersect_unit_sphere) on its own records,
+// from the o and d the shade would store for it, so "rejected here" implies "rejected there" bit
+// for bit; a ray that passes is traced as ever.  The loop is wave-uniform.
+__device__ __forceinline__ bool terminal_ray_culled(const DeviceScene &sc, vec3 o, vec3 d) {
+    const RayPre r = ray_pre(o, d);
+    bool hit = false;
+    for (uint32_t k = 0; k < sc.cull_n; k++) {
+        const uint32_t i = sc.cull_set[k];
+        const float4 a = sc.prims[kRecF4 * i + 0];
+        const float4 b = sc.prims[kRecF4 * i + 1];
+        const float4 c = sc.prims[kRecF4 * i + 2];
+        float t, b1, b2;
+        if (__float_as_uint(a.w) & kPrimSphereBit)
+            hit = hit || intersect_unit_sphere(sc.instances[__float_as_uint(b.w)].to_object, r.o, d, 0.001f,
+                                               kMaxDistance, t);
+        else
+            hit = hit || intersect_triangle(r, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), 0.001f,
+                                            kMaxDistance, t, b1, b2);
+    }
+    return !hit;
+}
+
 // fresh: a path of the frame generated for this launch (bounce 0, throughput 1, radiance 0,
 // RNG `fresh_rng`; k_generate stored only its camera ray)
 template <uint32_t MAT>
 __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const FrameParams &fp, const PathState &ps,
                                               uint32_t p, bool fresh, uint32_t fresh_p, uint32_t fresh_seed0) {
-    bool push_next = false, push_shadow = false;
+    bool push_next = false, push_shadow = false, culled = false;
     const float4 h = ld_ps(ps.hit + p);
     const vec3 ray_d = f3(ld_ps(ps.ray_d + p));
     // a fresh path's RNG after its camera draws, recomputed (k_generate stored only the ray)
@@ -324,10 +353,17 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
         } else {
             T = T * (br.f * fabs_(br.wi.z) / br.pdf);
             const vec3 nd = to_world(br.wi, geo.normal);
-            st_ps(ps.ray_d + p, f4(nd, 0.f));
             pdf_b = br.pdf;
             delta = (br.sampled_type & kLobeDelta) ? 1u : 0u;
-            push_next = true;
+            // Terminal-ray cull: the ray's shade is the path's last (its depth check fails: bounce + 2
+            // >= max_depth).  A ray the test resolves was cast and is counted, but it is not listed
+            // and its path state is not stored.
+            if (fp.cull_cum && bounce + 2u >= fp.max_depth && terminal_ray_culled(sc, geo.position, nd)) {
+                culled = true;
+            } else {
+                st_ps(ps.ray_d + p, f4(nd, 0.f));
+                push_next = true;
+            }
         }
     }
     // the shadow ray starts where the extension ray does (main.cu:119-123,158): one origin
@@ -345,7 +381,16 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
         const vec3 L = f3(fresh ? make_float4(0.f, 0.f, 0.f, 0.f) : ld_ps(ps.rad + p)) + L_add;
         st_ps(ps.rad + p, f4(L, 0.f));
     }
-    return (push_next ? 1u : 0u) | (push_shadow ? 2u : 0u) | (nee ? 4u : 0u);
+    return (push_next ? 1u : 0u) | (push_shadow ? 2u : 0u) | (nee ? 4u : 0u) | (culled ? 8u : 0u);
+}
+
+// The culled rays of a wave's shades (bit 3 of shade_hit's flags; 0 on the lanes that shaded
+// nothing) into the running total: one atomic per wave, on its block's shard.
+__device__ __forceinline__ void count_culled(const FrameParams &fp, uint32_t flags) {
+    if (!fp.cull_cum) return;
+    const unsigned long long m = __ballot((flags & 8u) != 0u);
+    if (m && __lane_id() == __ffsll((unsigned long long)__builtin_amdgcn_read_exec()) - 1)
+        atomicAdd(fp.cull_cum + (blockIdx.x % kCullShards) * kCullStride, (unsigned long long)__popcll(m));
 }
 
 // Paths whose ray left the scene (__miss__default, main.cu:196-212, and the
