@@ -1175,7 +1175,7 @@ int pupil_pt_set_camera(pupil_pt *pt, const float sample_to_camera[16], const fl
 // RenderObject::visibility_mask into OptixInstance::visibilityMask next to the transform.  A
 // hidden instance ((mask & 0xFF) == 0; every optixTrace passes 255) is the same refit with "no
 // geometry" as the new geometry: its records get NaN vertices, which no ray hits and no box
-// includes, and keep their id words, so showing it again restores them (bvh_build.hip
+// includes, and keep their id words, so showing it again restores them (bvh_refit.hip
 // k_refit_records; accel_two_level.hip k_world_records / rebuild_tlas).  The rebuild paths
 // (PUPIL_FLAT_UPDATE / PUPIL_TL_UPDATE = rebuild, the depth-overflow fallback, a tree without a
 // level order) build over all the geometry and then apply the masks the same way.  The emitter

@@ -313,7 +313,8 @@ void launch_partition(const uint8_t *keys, uint32_t n, uint32_t nbins, PartMode 
                       hipStream_t s, unsigned long long *cum_out = nullptr, unsigned long long *snap_out = nullptr,
                       uint32_t bin_mask = 0u);
 
-// LBVH builder (bvh_build.hip)
+// BVH builder (bvh_build.hip and the bvh_*.hip stage files; refit_bvh4 and the launch_*
+// updates: bvh_refit.hip)
 struct BvhBuildInput {
     uint32_t num_prims;
     const uint32_t *prim_inst;      // device, global prim -> instance
