@@ -509,6 +509,45 @@ int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
 int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slot, const void *rgba_device,
                                    uint32_t width, uint32_t height, void *hip_stream);
 int pupil_pt_material_info(pupil_pt *pt, uint64_t *updates, double *last_ms);
+/* The env map updated in place, its texels from device memory.  The reference builds the map's
+ * tables once per scene load (BuildEnvMapCdfTable, world/emitter.cpp:107-149): there is no
+ * reference event behind these entries.  No ABI bump: detect the symbols.
+ *
+ * pupil_pt_update_env_device replaces the texels of the env map: width * height float4, row-major,
+ * the layout of pupil_texture::rgba.  The engine's env emitter must be a PUPIL_EMITTER_ENV_MAP of
+ * exactly width x height.  PUPIL_ERR_INVALID otherwise -- no env emitter, a constant env, another
+ * size (the message says to set the size with pupil_pt_update_emitters first), pt or rgba_device
+ * NULL -- and PUPIL_ERR_OOM when the first call cannot allocate its scratch (height floats, owned
+ * by the engine until pupil_pt_destroy; no later call of the same size allocates).  Everything is
+ * checked before anything changes: a refused call leaves the engine rendering exactly as before.
+ * As with pupil_pt_update_texture_device the copy, device to device into the engine's own texels,
+ * is ordered after the work enqueued so far on hip_stream (a hipStream_t, NULL = the null stream)
+ * by an event, with no device-wide sync, and after every render enqueued so far; frames in flight
+ * are dropped.  The tables col_cdf, row_cdf and the normalization are then rebuilt on the engine's
+ * stream, in place, in the host's summation order (pt_envmap.hip), so they are bit for bit what
+ * pupil_pt_create would derive from the same texels; row_weight depends on the height only and
+ * stays.  Nothing else of the emitter is written.  Returns once the engine's stream has passed
+ * the kernels.  Precondition, as for the host path: the texels are finite and every row's
+ * luminance sum is > 0 (the host's tables hold NaN otherwise, whose bits the device need not
+ * match).
+ *
+ * pupil_pt_update_env_params rewrites scale, to_world and to_local (row-major 3x3; to_local must
+ * be the inverse the world computes, pupil_world_invert3x3) of the device's env map, whether its
+ * texels came from the host or the device: no table is built and no texel copied.  Ordered after
+ * every render enqueued so far; frames in flight are dropped; returns once the copies have run.
+ * PUPIL_ERR_INVALID: pt or a matrix NULL, no env map.
+ *
+ * After either call the engine's env no longer equals the pupil_emitter it was created from.  A
+ * later pupil_pt_update_emitters therefore never takes its in-place path on the strength of an
+ * unchanged env: it rebuilds the env from the scene it is given (host texels, host tables), even
+ * when that scene's env is byte for byte the one given before.
+ *
+ * pupil_pt_env_info: successful calls of the two entries since create, and the host's time around
+ * the last one (as build_ms is taken); either out pointer may be NULL. */
+int pupil_pt_update_env_device(pupil_pt *pt, const void *rgba_device, uint32_t width, uint32_t height,
+                               void *hip_stream);
+int pupil_pt_update_env_params(pupil_pt *pt, float scale, const float to_world[9], const float to_local[9]);
+int pupil_pt_env_info(pupil_pt *pt, uint64_t *updates, double *last_ms);
 /* Asynchronous on hip_stream (a hipStream_t; NULL = the default null stream): the
  * output buffers are complete once work later enqueued on that stream runs.  Exception:
  * with max_depth > 64 the call synchronises hip_stream every 16 bounces to read the list
@@ -575,6 +614,12 @@ int pupil_debug_read_emitter_guide(pupil_pt *pt, uint32_t *bits, uint32_t *guide
  *         position along in.xyz: out = radiance(3), pdf, 0, 0, 0, 0.
  * PUPIL_ERR_INVALID without an env emitter. */
 int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const float *pos_nrm, uint32_t mode, float *out);
+/* the device's env-map tables, read back after everything enqueued so far: col_cdf
+ * ((*width + 1) * *height floats), row_cdf (*height + 1), row_weight (*height) and the
+ * normalization.  The size comes back through width and height; call with the four out pointers
+ * NULL to size the arrays, and any of them may be NULL.  PUPIL_ERR_INVALID without an env map. */
+int pupil_debug_read_env_tables(pupil_pt *pt, uint32_t *width, uint32_t *height, float *col_cdf, float *row_cdf,
+                                float *row_weight, float *normalization);
 /* the device's cuda::Texture::Sample (framework/cuda/texture.h:33-57) of texture `slot`
  * (0..3) of a material on n (u, v) pairs: out = rgb per input */
 int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out);
@@ -679,6 +724,11 @@ int pupil_world_add_instance(pupil_world *w, uint32_t shape, uint32_t material, 
                              uint32_t flip_normals, uint32_t flip_tex_coords, uint32_t is_emitter,
                              const pupil_texture *radiance, uint32_t *out_instance);
 int pupil_world_add_const_env(pupil_world *w, const float radiance[3]);
+/* the inverse of a row-major 3x3 by the routine pupil_world_get_desc derives an env emitter's
+ * to_local from its to_world with (the 4x4 inverse in double of the matrix without translation):
+ * what pupil_pt_update_env_params needs to match a freshly loaded scene bit for bit.
+ * PUPIL_ERR_INVALID: a NULL argument or a singular matrix. */
+int pupil_world_invert3x3(const float m[9], float out[9]);
 /* RenderInstanceUpdate on the host side: new to_world (row-major 4x4) of instance `instance`
  * (index into pupil_scene_desc.instances); the next pupil_world_get_desc has the new
  * instance matrices and area emitters (world/world.cpp:45-54) */

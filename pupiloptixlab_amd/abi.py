@@ -142,6 +142,11 @@ SIGNATURES = {
     "pupil_pt_update_texture_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                   C.c_uint32, C.c_void_p]),
     "pupil_pt_material_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_pt_update_env_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "pupil_pt_update_env_params": (C.c_int, [C.c_void_p, C.c_float, f32p, f32p]),
+    "pupil_pt_env_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_debug_read_env_tables": (C.c_int, [C.c_void_p, u32p, u32p, f32p, f32p, f32p, f32p]),
+    "pupil_world_invert3x3": (C.c_int, [f32p, f32p]),
     "pupil_debug_read_material": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p]),
     "pupil_debug_read_emitters": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p]),
     "pupil_debug_read_emitter_guide": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -169,6 +170,17 @@ struct pupil_pt {
     uint32_t *d_guide = nullptr;
     pupil_emitter env_src{};  // the env emitter the tables were built from (same_env)
     bool env_src_valid = false;
+    // The env map from device memory (pupil_pt_update_env_device / _update_env_params).  h_env: the
+    // host mirror of *d_env as upload_emitters wrote it -- its type, size and device pointers;
+    // normalization is stale after a device update.  env_stale: env_src no longer describes the
+    // device (same_env answers false until the next upload_emitters).  d_env_sums: the row sums
+    // the table kernels pass between their stages (pt_envmap.hip), sized on first use
+    DevEmitter h_env{};
+    bool env_stale = false;
+    float *d_env_sums = nullptr;
+    uint32_t env_sums_cap = 0;
+    uint64_t env_updates = 0;
+    double env_ms = 0.0;  // host clock around the last update
     std::vector<DevEmitter> h_emit_areas;  // host sources of in-place emitter updates
     std::vector<float> h_emit_cdf;
     std::vector<uint32_t> h_emit_guide;
@@ -395,6 +407,7 @@ int emitter_tables(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<DevE
 bool same_env(const pupil_pt *pt, const pupil_scene_desc *scene) {
     const bool has = scene->env && scene->env->type != PUPIL_EMITTER_NONE;
     if (has != pt->env_src_valid) return false;
+    if (pt->env_stale) return false;  // texels or parameters came from pupil_pt_update_env_*: env_src is not the device's
     return !has || std::memcmp(&pt->env_src, scene->env, sizeof(pupil_emitter)) == 0;
 }
 
@@ -412,6 +425,7 @@ int upload_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
         return fail(PUPIL_ERR_OOM, "emitter upload failed");
     if (!g.empty() && pt->upload(&d_guide, g.data(), g.size())) return fail(PUPIL_ERR_OOM, "emitter guide upload failed");
     pt->env_src_valid = false;
+    DevEmitter h_env{};
     if (scene->env && scene->env->type != PUPIL_EMITTER_NONE) {
         pt->env_src = *scene->env;
         pt->env_src_valid = true;
@@ -419,6 +433,7 @@ int upload_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
         int rc = convert_emitter(pt, *scene->env, env);
         if (rc) return rc;
         if (pt->upload(&d_env, &env, 1)) return fail(PUPIL_ERR_OOM, "env upload failed");
+        h_env = env;
     }
     pt->release(pt->d_areas);
     pt->release(pt->d_cdf);
@@ -430,6 +445,8 @@ int upload_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     pt->sc.area_guide = d_guide;
     pt->sc.guide_bits = bits;
     pt->d_env = d_env;
+    pt->h_env = h_env;
+    pt->env_stale = false;  // env_src describes the device again
     pt->sc.areas = d_areas;
     pt->sc.area_cdf = d_cdf;
     pt->sc.num_areas = scene->num_area_emitters;
@@ -1524,6 +1541,91 @@ int pupil_pt_material_info(pupil_pt *pt, uint64_t *updates, double *last_ms) {
     return PUPIL_OK;
 }
 
+extern "C++" {
+namespace {
+// the engine holds an env map (not a constant env, not none) the two entries below can rewrite
+int env_map_held(const pupil_pt *pt) {
+    const DevEmitter &e = pt->h_env;
+    if (!pt->d_env || e.type != PUPIL_EMITTER_ENV_MAP || !e.radiance.data || !e.col_cdf)
+        return fail(PUPIL_ERR_INVALID, "the scene has no env map: give it one with pupil_pt_update_emitters first");
+    return PUPIL_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+// The texels of the env map from device memory, ordered like pupil_pt_update_texture_device: an
+// event on the caller's stream, the engine's stream waits for it, then the copy device to device
+// into the engine's own texels and the two table stages of pt_envmap.hip, which rewrite col_cdf,
+// row_cdf and normalization in place.  Everything that can refuse the call, the scratch
+// allocation of the first call included, runs before anything of the engine changes.
+int pupil_pt_update_env_device(pupil_pt *pt, const void *rgba_device, uint32_t width, uint32_t height,
+                               void *hip_stream) {
+    if (!pt || !rgba_device) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (const int rc = env_map_held(pt)) return rc;
+    const DevEmitter &e = pt->h_env;
+    if (e.map_w != width || e.map_h != height)
+        return fail(PUPIL_ERR_INVALID, "the env map is " + std::to_string(e.map_w) + " x " + std::to_string(e.map_h) +
+                                           ": set the size with pupil_pt_update_emitters first");
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (pt->env_sums_cap < height) {  // the first call, or the first since the map grew
+        float *sums = nullptr;
+        if (pt->alloc(&sums, height) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(PUPIL_ERR_OOM, "env scratch allocation failed");
+        }
+        pt->release(pt->d_env_sums);  // no kernel reads it: every call returns behind its own
+        pt->d_env_sums = sums;
+        pt->env_sums_cap = height;
+    }
+    HIP_TRY(order_after_renders(pt));  // no render may still read the old texels and tables
+    pt->pipe.invalidate();
+    pt->env_stale = true;  // from here env_src no longer describes the device
+    HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));  // after the caller's work; no device-wide sync
+    HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    HIP_TRY(hipMemcpyAsync((void *)e.radiance.data, rgba_device, sizeof(float4) * (size_t)width * height,
+                           hipMemcpyDeviceToDevice, pt->own_stream));
+    launch_env_tables({e.radiance.data, width, height, const_cast<float *>(e.col_cdf), const_cast<float *>(e.row_cdf),
+                       e.row_weight, pt->d_env_sums, pt->d_env},
+                      pt->own_stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    pt->env_updates++;
+    pt->env_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+// scale, to_world and to_local of the device's env emitter: two small copies, no table, no texel
+int pupil_pt_update_env_params(pupil_pt *pt, float scale, const float to_world[9], const float to_local[9]) {
+    if (!pt || !to_world || !to_local) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (const int rc = env_map_held(pt)) return rc;
+    static_assert(offsetof(DevEmitter, to_local) == offsetof(DevEmitter, to_world) + 9 * sizeof(float),
+                  "to_world and to_local go up in one copy");
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(order_after_renders(pt));  // no render may still read the old parameters
+    pt->pipe.invalidate();
+    pt->env_stale = true;
+    DevEmitter &e = pt->h_env;  // outlives the copies (synchronised below)
+    e.scale = scale;
+    std::memcpy(e.to_world, to_world, sizeof(e.to_world));
+    std::memcpy(e.to_local, to_local, sizeof(e.to_local));
+    HIP_TRY(hipMemcpyAsync(&pt->d_env->scale, &e.scale, sizeof(float), hipMemcpyHostToDevice, pt->own_stream));
+    HIP_TRY(hipMemcpyAsync(pt->d_env->to_world, e.to_world, sizeof(e.to_world) + sizeof(e.to_local), hipMemcpyHostToDevice,
+                           pt->own_stream));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    pt->env_updates++;
+    pt->env_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+int pupil_pt_env_info(pupil_pt *pt, uint64_t *updates, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (updates) *updates = pt->env_updates;
+    if (last_ms) *last_ms = pt->env_ms;
+    return PUPIL_OK;
+}
+
 int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_launch *launch, void *hip_stream) {
     if (!pt || !out || !launch || !out->accum) return fail(PUPIL_ERR_INVALID, "null argument");
     if (launch->spp == 0) return PUPIL_OK;
@@ -2016,6 +2118,26 @@ int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const floa
     return debug_probe(pt, n, xi_or_dir, 3, out, 8, [&](const float *din, float *dout) {
         launch_debug_env(pt->sc, din, pos_nrm, mode, dout, n, pt->own_stream);
     });
+}
+
+int pupil_debug_read_env_tables(pupil_pt *pt, uint32_t *width, uint32_t *height, float *col_cdf, float *row_cdf,
+                                float *row_weight, float *normalization) {
+    if (!pt || !width || !height) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (const int rc = env_map_held(pt)) return rc;
+    const DevEmitter &e = pt->h_env;
+    const size_t w = e.map_w, h = e.map_h;
+    *width = e.map_w;
+    *height = e.map_h;
+    if (!col_cdf && !row_cdf && !row_weight && !normalization) return PUPIL_OK;
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(order_after_renders(pt));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (col_cdf) HIP_TRY(hipMemcpy(col_cdf, e.col_cdf, sizeof(float) * (w + 1) * h, hipMemcpyDeviceToHost));
+    if (row_cdf) HIP_TRY(hipMemcpy(row_cdf, e.row_cdf, sizeof(float) * (h + 1), hipMemcpyDeviceToHost));
+    if (row_weight) HIP_TRY(hipMemcpy(row_weight, e.row_weight, sizeof(float) * h, hipMemcpyDeviceToHost));
+    if (normalization)
+        HIP_TRY(hipMemcpy(normalization, &pt->d_env->normalization, sizeof(float), hipMemcpyDeviceToHost));
+    return PUPIL_OK;
 }
 
 int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out) {

@@ -1115,6 +1115,18 @@ int pupil_world_add_const_env(pupil_world *w, const float radiance[3]) {
     return PUPIL_OK;
 }
 
+int pupil_world_invert3x3(const float m[9], float out[9]) {
+    if (!m || !out) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    Pupil::util::Mat4 t = Pupil::util::Mat4::Identity();
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) t.at(r, c) = m[3 * r + c];
+    const Pupil::util::Mat4 inv = t.Inverse();  // the routine the env emitter's to_local comes from
+    if (inv.at(3, 3) == 0.f) return Pupil::werr(PUPIL_ERR_INVALID, "singular matrix");
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) out[3 * r + c] = inv.at(r, c);
+    return PUPIL_OK;
+}
+
 int pupil_world_get_desc(pupil_world *w, pupil_scene_desc *desc) {
     if (!w || !desc) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
     if (w->w.scene.instances.empty()) return Pupil::werr(PUPIL_ERR_INVALID, "world has no shape instances");

@@ -290,6 +290,20 @@ PT_HD float specular_sampling_weight(vec3 diffuse_average, vec3 specular_average
 void launch_specular_weight(DevMaterial *mat, hipStream_t s);
 void launch_record_bins(float4 *recs, uint32_t slots, const DevInstance *instances, uint32_t num_instances,
                         hipStream_t s);
+// The env map's tables rebuilt in place from the engine's own texels (pt_envmap.hip): col_cdf
+// ((w + 1) * h), row_cdf (h + 1) and env->normalization, bit for bit what convert_emitter
+// (engine.hip) derives from the same texels.  row_weight (h, the host's std::sin) is read only;
+// col_sum: scratch, h floats.  kEnvStage: the values a wave stages in the LDS per chunk of a chain.
+constexpr uint32_t kEnvStage = 1024;
+struct EnvTablesJob {
+    const float4 *texels;  // w * h, row-major
+    uint32_t w, h;
+    float *col_cdf, *row_cdf;
+    const float *row_weight;
+    float *col_sum;
+    DevEmitter *env;
+};
+void launch_env_tables(const EnvTablesJob &job, hipStream_t s);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

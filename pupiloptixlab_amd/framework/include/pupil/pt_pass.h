@@ -54,6 +54,15 @@ public:
     bool UpdateMaterials(const std::vector<uint32_t> &ids) noexcept;
     bool UpdateTextureDevice(uint32_t material, uint32_t slot, const void *rgba_device, uint32_t width, uint32_t height,
                              hipStream_t stream) noexcept;
+    // The env map in place (pupil_pt_update_env_device / _update_env_params), applied now, under the
+    // same threading rule: between OnRuns, from OnRun's thread.  UpdateEnvDevice: width x height
+    // float4 texels in device memory for the scene's env map of that size, copied after the work
+    // enqueued so far on `stream` (a hipStream_t); the map's CDF tables follow on the device.
+    // UpdateEnvParams: scale and rotation (row-major 3x3) of the env map; to_local is the world's
+    // own inverse of to_world (pupil_world_invert3x3), as a freshly loaded scene's is.  Both
+    // restart accumulation at the next OnRun.  False: no scene, or the engine refused.
+    bool UpdateEnvDevice(const void *rgba_device, uint32_t width, uint32_t height, void *stream) noexcept;
+    bool UpdateEnvParams(float scale, const float to_world[9]) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in

@@ -297,6 +297,28 @@ bool PTPass::UpdateTextureDevice(uint32_t material, uint32_t slot, const void *r
     return true;
 }
 
+bool PTPass::UpdateEnvDevice(const void *rgba_device, uint32_t width, uint32_t height, void *stream) noexcept {
+    if (!m_engine) return false;
+    if (pupil_pt_update_env_device(m_engine, rgba_device, width, height, stream) != PUPIL_OK) {
+        Log("%s: env map update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    m_dirty = true;
+    return true;
+}
+
+bool PTPass::UpdateEnvParams(float scale, const float to_world[9]) noexcept {
+    if (!m_engine || !to_world) return false;
+    float to_local[9];
+    if (pupil_world_invert3x3(to_world, to_local) != PUPIL_OK ||
+        pupil_pt_update_env_params(m_engine, scale, to_world, to_local) != PUPIL_OK) {
+        Log("%s: env parameter update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    m_dirty = true;
+    return true;
+}
+
 bool PTPass::Stats(pupil_pt_counters &out) noexcept { return m_engine && pupil_pt_stats(m_engine, &out) == PUPIL_OK; }
 
 void PTPass::BindingEventCallback() noexcept {

@@ -301,6 +301,71 @@ class PTPass(Pass):
         check(self._lib.pupil_debug_read_material(self._pt, int(material), C.byref(t), out.ctypes.data_as(abi.f32p)))
         return {"type": t.value, "eta": out[0], "int_fdr": out[1], "specular_sampling_weight": out[2]}
 
+    # ---- the env map in place (pupil_pt_update_env_device / _update_env_params)
+    def update_env_device(self, tensor, stream=None):
+        """The texels of the env map from a contiguous float32 tensor of shape (h, w, 4) on the
+        pass's device; the scene's env must already be an h x w env map (a scene load or
+        pupil_pt_update_emitters sets the size).  The copy is ordered after the work enqueued so far
+        on `stream` (default: the current stream) and never passes through the host; the map's CDF
+        tables follow on the device, bit for bit the host's.  Restarts accumulation."""
+        torch = self._torch
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        if not isinstance(tensor, torch.Tensor):
+            raise ValueError("update_env_device needs a torch tensor")
+        if tensor.dim() != 3 or tensor.shape[2] != 4 or tensor.shape[0] == 0 or tensor.shape[1] == 0:
+            raise ValueError(f"update_env_device needs an (h, w, 4) tensor, got {tuple(tensor.shape)}")
+        if not (tensor.is_cuda and tensor.dtype == torch.float32 and tensor.is_contiguous()):
+            raise ValueError("update_env_device needs a contiguous float32 device tensor")
+        if tensor.device.index != self.device_index:  # the copy runs device to device on the engine's GPU
+            raise ValueError(f"update_env_device needs a tensor on {self.device}, got {tensor.device}")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        check(self._lib.pupil_pt_update_env_device(self._pt, C.c_void_p(tensor.data_ptr()), int(tensor.shape[1]),
+                                                   int(tensor.shape[0]), C.c_void_p(s.cuda_stream)))
+        self.mark_dirty()
+
+    def update_env_params(self, scale: float, to_world3x3):
+        """scale and rotation of the env map (to_world3x3: 9 floats, row-major) without touching
+        its texels or tables.  to_local is the inverse of to_world3x3 as float32, computed on the
+        host in float64 by the routine the World uses (pupil_world_invert3x3): a fresh engine's
+        to_local comes from the world's own inverse of the emitter's transform, and this is that
+        inverse, so the updated engine equals a scene loaded with the same rotation and scale bit
+        for bit.  Restarts accumulation."""
+        import numpy as np
+
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        tw = np.ascontiguousarray(np.asarray(to_world3x3, np.float32).reshape(-1))
+        if tw.size != 9:
+            raise ValueError("update_env_params needs a 3 x 3 matrix")
+        tl = np.zeros(9, np.float32)
+        check(self._lib.pupil_world_invert3x3(tw.ctypes.data_as(abi.f32p), tl.ctypes.data_as(abi.f32p)))
+        check(self._lib.pupil_pt_update_env_params(self._pt, float(scale), tw.ctypes.data_as(abi.f32p),
+                                                   tl.ctypes.data_as(abi.f32p)))
+        self.mark_dirty()
+
+    def env_info(self) -> dict:
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_env_info(self._pt, C.byref(n), C.byref(ms)))
+        return {"updates": n.value, "last_ms": ms.value}
+
+    def env_tables(self) -> dict:
+        """The device's env-map tables (pupil_debug_read_env_tables): col_cdf (h, w + 1), row_cdf
+        (h + 1,), row_weight (h,) and normalization, float32."""
+        import numpy as np
+
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        check(self._lib.pupil_debug_read_env_tables(self._pt, C.byref(w), C.byref(h), None, None, None, None))
+        col = np.zeros((h.value, w.value + 1), np.float32)
+        row = np.zeros(h.value + 1, np.float32)
+        weight = np.zeros(h.value, np.float32)
+        norm = np.zeros(1, np.float32)
+        check(self._lib.pupil_debug_read_env_tables(self._pt, C.byref(w), C.byref(h), col.ctypes.data_as(abi.f32p),
+                                                    row.ctypes.data_as(abi.f32p), weight.ctypes.data_as(abi.f32p),
+                                                    norm.ctypes.data_as(abi.f32p)))
+        return {"width": w.value, "height": h.value, "col_cdf": col, "row_cdf": row, "row_weight": weight,
+                "normalization": norm[0]}
+
     # ---- engine-owned emitter table (pupil_pt_enable_device_emitters)
     @property
     def device_emitters(self):
