@@ -319,6 +319,51 @@ static bool DeviceEmittersFromEnv(Pupil::pt::PTPass &pass) {
     return false;
 }
 
+// PUPIL_PICK="x,y": what lies under the centre of pixel (x, y) (row 0 = bottom), printed after the
+// last OnRun -- instance, face within its shape, material and distance.  The inspector's selection
+// works on a RenderObject the user clicked in a list; this is the lookup a click in the viewport
+// needs (PTPass::QueryCamera over the frame, one pixel read back).  Single GPU.
+static int PickFromEnv(Pupil::System &system, Pupil::pt::PTPass &pass, int w, int h) {
+    const char *spec = std::getenv("PUPIL_PICK");
+    if (!spec) return 0;
+    int x = -1, y = -1;
+    if (std::sscanf(spec, "%d,%d", &x, &y) != 2 || x < 0 || y < 0 || x >= w || y >= h) {
+        std::fprintf(stderr, "PUPIL_PICK must be x,y inside the %dx%d film\n", w, h);
+        return 2;
+    }
+    if (system.Gather()) {
+        std::fprintf(stderr, "PUPIL_PICK runs on one GPU\n");
+        return 2;
+    }
+    const size_t n = (size_t)w * h;
+    float *hit = nullptr;
+    int32_t *ids = nullptr;  // instance | primitive | material, n each
+    int rc = 1;
+    if (hipMalloc((void **)&hit, 4 * n * sizeof(float)) == hipSuccess &&
+        hipMalloc((void **)&ids, 3 * n * sizeof(int32_t)) == hipSuccess) {
+        pupil_ray_hits out{};
+        out.hit = hit;
+        out.instance = ids;
+        out.primitive = ids + n;
+        out.material = ids + 2 * n;
+        const size_t i = (size_t)y * w + x;
+        float t = -1.f;
+        int32_t got[3] = {-1, -1, -1};
+        if (pass.QueryCamera(out) && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(&t, hit + 4 * i, sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&got[0], ids + i, sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&got[1], ids + n + i, sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&got[2], ids + 2 * n + i, sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess) {
+            if (got[0] < 0) std::printf("pick %d,%d: nothing\n", x, y);
+            else std::printf("pick %d,%d: instance %d, primitive %d, material %d, distance %.6f\n", x, y, got[0], got[1], got[2], t);
+            rc = 0;
+        }
+    }
+    if (hit) (void)hipFree(hit);
+    if (ids) (void)hipFree(ids);
+    return rc;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <scene.xml> [frames=16] [out.exr|.hdr|.pfm] [device=0]\n", argv[0]);
@@ -389,6 +434,7 @@ int main(int argc, char **argv) {
                 std::printf("frames %d, %dx%d, mean radiance %.6f, last frame %.3f ms\n", frames, w, h,
                             mean / (3.0 * w * h), pt_pass->LastExecTimeMs());
             }
+            if (rc == 0) rc = PickFromEnv(*system, *pt_pass, w, h);
         }
         system->Destroy();
     }

@@ -578,10 +578,70 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
                             uint32_t tile_size, uint32_t tile_rank, uint32_t tile_world,
                             void *hip_stream);
 
+/* Ray queries from device memory: what does this ray hit.  The engine's production traversal over
+ * a ray list that is already on the device, and the hits resolved into ids and hit geometry that
+ * mean something without the engine's tables (picking, depth / position / instance-id maps,
+ * line-of-sight tests, range scans).  The reference has no such entry (its inspector works on
+ * the selected RenderObject): no ABI bump, detect the symbols.
+ *
+ * pupil_ray_hits: device pointers to n elements each, NULL = not wanted.  On a miss t = -1, the
+ * prim id bits are 0xFFFFFFFF, the ids are -1 and position, normal and texcoord are exactly 0
+ * (what a render writes to the normal AOV on a miss).  Alignment: hit 16 B, texcoord 8 B,
+ * everything else 4 B; the ray list 16 B (the resolve kernel loads rays and hits as float4 and
+ * stores a texcoord as one float2; ids, positions and normals are stored by dwords).
+ *
+ * pupil_pt_query_rays: n rays (ox, oy, oz, dx, dy, dz, tmin, tmax), read in place from
+ * rays_device.  Closest hit unless PUPIL_QUERY_ANY_HIT; `hit` is bit for bit what
+ * pupil_pt_trace_rays returns for the same rays (same kernel), degenerate rays included.  With
+ * PUPIL_QUERY_ANY_HIT only `hit` may be set (t = 1 occluded, -1 not).  A hidden instance is hit by
+ * no ray.  n = 0: PUPIL_OK, nothing is enqueued.  PUPIL_ERR_INVALID, before anything is
+ * enqueued: pt, out or (n > 0) rays_device NULL, every field of out NULL, n >= 2^31, an unknown
+ * flag, any hit with a resolved output, a misaligned pointer.
+ * Asynchronous on hip_stream (NULL = the null stream), with no device-wide sync: ordered by stream
+ * events after every render, flow pass and query enqueued so far (they share the traversal's
+ * overflow stacks), and later ones order themselves behind it.  The outputs are complete once
+ * work later enqueued on hip_stream runs.  Adds nothing to the ray counters of pupil_pt_stats and
+ * touches neither the accumulation, the sample count nor the frames in flight.  When `hit` is NULL
+ * but resolved outputs are wanted the hits go to engine-owned scratch, which grows geometrically
+ * and never shrinks; a flat (one-level) acceleration structure also keeps 4 B per primitive for
+ * the resolve of position, normal or texcoord, allocated by the first query that wants one.  A
+ * call that fits what is there allocates nothing and synchronises nothing; a growth waits for
+ * the queries in flight.
+ *
+ * pupil_pt_query_camera: the G-buffer form.  One camera ray per local pixel of the tiling -- the
+ * ray a render traces for film jitter (jitter_x, jitter_y), (0.5, 0.5) = the pixel centre -- then
+ * the same trace and resolve.  Outputs are indexed like the frame buffers (compact = rank-local
+ * order; else y*width + x, where a rank writes only its own pixels); tile_* as in
+ * pupil_pt_motion_vectors.  rays_out_device (optional, 16-B aligned): receives the rays, 8 floats
+ * per local pixel in rank-local order; NULL = they stay in the engine's scratch (the flow pass's).
+ *
+ * pupil_pt_query_info: queries and rays since create, growths of the engine-owned scratch, and
+ * the device time of the last query from events around it (the call waits for that query); any
+ * out pointer may be NULL. */
+typedef struct pupil_ray_hits {
+    void *hit;       /* float4: t, b1, b2, prim id bits -- pupil_pt_trace_rays' layout and values */
+    void *instance;  /* int32: index into pupil_scene_desc.instances */
+    void *primitive; /* int32: face index within the instance's shape (0 for a sphere) */
+    void *material;  /* int32: the instance's material index */
+    void *position;  /* float3, world space */
+    void *normal;    /* float3: GetHitLocalGeometry's normal (geometry.h:272-320), flip_normals and
+                        the two-sided flip towards the ray included: the value of the "normal" AOV */
+    void *texcoord;  /* float2 */
+} pupil_ray_hits;
+enum { PUPIL_QUERY_ANY_HIT = 1 };
+int pupil_pt_query_rays(pupil_pt *pt, uint32_t n, const void *rays_device /* 8 floats per ray */, uint32_t flags,
+                        const pupil_ray_hits *out, void *hip_stream);
+int pupil_pt_query_camera(pupil_pt *pt, float jitter_x, float jitter_y, uint32_t compact, uint32_t tile_size,
+                          uint32_t tile_rank, uint32_t tile_world, void *rays_out_device, const pupil_ray_hits *out,
+                          void *hip_stream);
+int pupil_pt_query_info(pupil_pt *pt, uint64_t *queries, uint64_t *rays, uint64_t *scratch_grows, double *last_ms);
+
 /* ---- verification entry points (used by the parity tests) ----
  * closest (any_hit = 0) or any hit (any_hit = 1) for n host rays packed as
  * (ox, oy, oz, dx, dy, dz, tmin, tmax); out (host) = (t, b1, b2, prim id bits)
- * per ray, prim id = 0xFFFFFFFF and t = -1 on a miss (any hit: t = 1 if occluded). */
+ * per ray, prim id = 0xFFFFFFFF and t = -1 on a miss (any hit: t = 1 if occluded).
+ * Synchronises the device and allocates per call: production code traces rays that are on
+ * the device with pupil_pt_query_rays, which returns the same hits. */
 int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out, int any_hit);
 /* copies the flattened BVH4 the traversal kernels read (64-B quantized nodes, 12-float
  * world-space primitive records, root link) to host memory, for the CPU baseline that

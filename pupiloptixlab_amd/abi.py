@@ -121,6 +121,16 @@ class DenoiseData(C.Structure):
                 ("albedo", C.c_void_p), ("normal", C.c_void_p), ("motion_vector", C.c_void_p)]
 
 
+QUERY_ANY_HIT = 1  # pupil_pt_query_rays flags
+
+
+class RayHits(C.Structure):
+    """pupil_ray_hits: device pointers, NULL = not wanted."""
+    _fields_ = [("hit", C.c_void_p), ("instance", C.c_void_p), ("primitive", C.c_void_p),
+                ("material", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p),
+                ("texcoord", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every entry is declared in include/pupil_pt.h
 SIGNATURES = {
     "pupil_last_error": (C.c_char_p, []),
@@ -158,6 +168,11 @@ SIGNATURES = {
     "pupil_pt_destroy": (None, [C.c_void_p]),
     "pupil_pt_motion_vectors": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_void_p, C.c_uint32, C.c_uint32,
                                            C.c_uint32, C.c_uint32, C.c_void_p]),
+    "pupil_pt_query_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(RayHits), C.c_void_p]),
+    "pupil_pt_query_camera": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_void_p, C.POINTER(RayHits), C.c_void_p]),
+    "pupil_pt_query_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "pupil_pt_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, C.c_int]),
     "pupil_pt_export_bvh4": (C.c_int, [C.c_void_p, u32p, C.c_void_p, u32p, f32p, C.POINTER(C.c_int32)]),
     "pupil_debug_math": (C.c_int, [C.c_int, C.c_uint32, f32p, f32p, f32p]),

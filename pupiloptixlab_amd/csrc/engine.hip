@@ -214,6 +214,18 @@ struct pupil_pt {
     uint32_t snapshots = 0;
     bool flow_verts_stale = false;
     hipEvent_t ev_snap = nullptr;
+    // ray queries (pupil_pt_query_rays / _query_camera).  query_hits: the compact hits of a call that
+    // wants resolved outputs but not the hits themselves; grown geometrically, never shrunk
+    // (query_cap rays, query_grows growths; the first build of query_slot counts as one).
+    // query_slot: flat BVH only, global primitive id -> record slot for the resolve kernel,
+    // rebuilt from the records by the first such query after they moved (query_slot_valid is
+    // cleared with the cull set's scan).  ev_q0 / ev_q1 bracket the last query on its stream
+    float4 *query_hits = nullptr;
+    size_t query_cap = 0;
+    uint32_t *query_slot = nullptr;
+    bool query_slot_valid = false;
+    uint64_t queries = 0, query_rays = 0, query_grows = 0;
+    hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -261,6 +273,8 @@ struct pupil_pt {
         if (ev_sync) (void)hipEventDestroy(ev_sync);
         if (ev_flow) (void)hipEventDestroy(ev_flow);
         if (ev_snap) (void)hipEventDestroy(ev_snap);
+        if (ev_q0) (void)hipEventDestroy(ev_q0);
+        if (ev_q1) (void)hipEventDestroy(ev_q1);
         if (ev_verts) (void)hipEventDestroy(ev_verts);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -988,6 +1002,7 @@ int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
     sc.cull_set = pt->d_cull + 1;
     sc.cull_n = 0;
     if (records_changed) pt->cull_scanned = 0;
+    if (records_changed) pt->query_slot_valid = false;  // a rebuild moves the records the map names
     if (!pt->cull_on || sc.has_env || !sc.prims || (sc.two_level && !sc.tl_world)) return PUPIL_OK;
     uint64_t emissive = 0;  // primitives: a mesh instance's faces, a sphere
     for (size_t i = 0; i < pt->h_insts.size(); i++) {
@@ -2008,13 +2023,185 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
     job.n = num_local;
     job.compact = compact;
     HIP_TRY(hipMemsetAsync(pt->q.work + kWorkFlow, 0, kWorkKind * sizeof(uint32_t), s));
-    launch_flow_rays(pt->sc, pt->width, pt->height, job.pixel_map, num_local, pt->flow_rays, s);
+    launch_flow_rays(pt->sc, pt->width, pt->height, job.pixel_map, num_local, 0.5f, 0.5f, pt->flow_rays, s);
     launch_trace_debug(pt->sc, (const float *)pt->flow_rays, (float *)pt->flow_hits, num_local, 0, pt->ovf,
                        pt->ovf_threads, pt->q.work + kWorkFlow, s);
     launch_flow_project(pt->sc, job, pt->flow_rays, pt->flow_hits, (float2 *)out_flow, s, prev_verts);
     HIP_TRY(hipGetLastError());
     pt->last_stream = s;
     pt->rendered = true;
+    return PUPIL_OK;
+}
+
+extern "C++" {
+namespace {
+
+// what both query entries check of their outputs before anything is enqueued: some array is
+// wanted, any hit fills none but the hits, and every pointer is aligned for the accesses the
+// kernels make -- 16 B for the hits (k_query_resolve loads a float4; the traversal's own four
+// 4-B stores need less), 8 B for the texcoords (one float2 store), 4 B for the rest (the ids
+// are dword stores, position and normal one 12-B global_store_dwordx3 each, which needs the
+// alignment of its dwords only)
+int check_query_outputs(const pupil_ray_hits *out, uint32_t flags) {
+    if (!out) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (flags & ~(uint32_t)PUPIL_QUERY_ANY_HIT) return fail(PUPIL_ERR_INVALID, "unknown query flag");
+    const bool resolved =
+        out->instance || out->primitive || out->material || out->position || out->normal || out->texcoord;
+    if (!out->hit && !resolved) return fail(PUPIL_ERR_INVALID, "no output array is wanted");
+    if ((flags & PUPIL_QUERY_ANY_HIT) && resolved)
+        return fail(PUPIL_ERR_INVALID, "an any-hit query fills only the hit array");
+    auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0u; };
+    if (misaligned(out->hit, 16) || misaligned(out->texcoord, 8) || misaligned(out->instance, 4) ||
+        misaligned(out->primitive, 4) || misaligned(out->material, 4) || misaligned(out->position, 4) ||
+        misaligned(out->normal, 4))
+        return fail(PUPIL_ERR_INVALID, "misaligned output array (hit: 16 B, texcoord: 8 B, the others: 4 B)");
+    return PUPIL_OK;
+}
+
+// The traversal of n rays and the resolve of their hits, enqueued on s.  Ordered by stream events
+// after every render, flow pass and query enqueued so far -- the overflow stacks are shared --
+// and what follows orders itself behind it the same way (last_stream).  make_rays (or null):
+// enqueues what writes the ray list, after the ordering and inside the timed span.  scatter (or
+// null): ray l's outputs go to element scatter[l] (a tiled camera query in the frame's index
+// space); the traversal writes hits in ray order, so they pass through the scratch and the resolve
+// kernel puts them in place.  A call whose scratch fits allocates nothing and synchronises nothing.
+template <typename MakeRays>
+int run_query(pupil_pt *pt, uint32_t n, const float4 *rays, uint32_t flags, const pupil_ray_hits *out, hipStream_t s,
+              const uint32_t *scatter, MakeRays make_rays) {
+    const bool any = (flags & PUPIL_QUERY_ANY_HIT) != 0u;
+    const bool geo = out->position || out->normal || out->texcoord;
+    const bool resolved = geo || out->instance || out->primitive || out->material;
+    if (!pt->ev_q0) {
+        HIP_TRY(hipEventCreate(&pt->ev_q0));
+        HIP_TRY(hipEventCreate(&pt->ev_q1));
+    }
+    float4 *hits = (float4 *)out->hit;
+    if (!hits || scatter) {  // resolved outputs without the hits: the engine's scratch holds them
+        if (pt->query_cap < n) {
+            // the scratch a query still in flight reads is freed only once its stream has passed it
+            if (pt->query_hits && pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
+            const size_t cap = std::max<size_t>(n, 2 * pt->query_cap);
+            float4 *grown = nullptr;
+            HIP_TRY(pt->alloc(&grown, cap));
+            pt->release(pt->query_hits);
+            pt->query_hits = grown;
+            pt->query_cap = cap;
+            pt->query_grows++;
+        }
+        hits = pt->query_hits;
+    }
+    const bool slots = geo && !pt->sc.two_level;  // reconstruct() names flat records by slot
+    if (slots && !pt->query_slot) {
+        HIP_TRY(pt->alloc(&pt->query_slot, pt->num_prims));
+        pt->query_grows++;
+    }
+    if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
+        HIP_TRY(hipEventRecord(pt->ev_sync, pt->last_stream));
+        HIP_TRY(hipStreamWaitEvent(s, pt->ev_sync, 0));
+    }
+    HIP_TRY(hipEventRecord(pt->ev_q0, s));
+    make_rays();
+    HIP_TRY(hipMemsetAsync(pt->q.work + kWorkQuery, 0, kWorkKind * sizeof(uint32_t), s));
+    launch_trace_debug(pt->sc, (const float *)rays, (float *)hits, n, any ? 1 : 0, pt->ovf, pt->ovf_threads,
+                       pt->q.work + kWorkQuery, s);
+    if (resolved || scatter) {
+        const uint32_t rec_slots = slots ? pt->accel.world_record_slots() : 1u;
+        if (slots && !pt->query_slot_valid) {
+            launch_query_prim_slots(pt->sc.prims, rec_slots, pt->num_prims, pt->query_slot, s);
+            pt->query_slot_valid = true;
+        }
+        const QueryJob job{rays,
+                           hits,
+                           n,
+                           rec_slots,
+                           slots ? pt->query_slot : nullptr,
+                           (int32_t *)out->instance,
+                           (int32_t *)out->primitive,
+                           (int32_t *)out->material,
+                           (float *)out->position,
+                           (float *)out->normal,
+                           (float2 *)out->texcoord,
+                           scatter,
+                           scatter ? (float4 *)out->hit : nullptr};
+        launch_query_resolve(pt->sc, job, s);
+    }
+    HIP_TRY(hipEventRecord(pt->ev_q1, s));
+    HIP_TRY(hipGetLastError());
+    pt->queries++;
+    pt->query_rays += n;
+    pt->last_stream = s;
+    pt->rendered = true;
+    return PUPIL_OK;
+}
+
+}  // namespace
+}
+
+// Ray queries from device memory: the production traversal over a caller's ray list, read in
+// place, then k_query_resolve (pt_query.hip) for whatever of pupil_ray_hits is wanted.  Its
+// traversal has its own work-counter slot (kWorkQuery); it adds to none of the ray totals
+// pupil_pt_stats reports and touches neither the accumulation nor the frames in flight.
+int pupil_pt_query_rays(pupil_pt *pt, uint32_t n, const void *rays_device, uint32_t flags, const pupil_ray_hits *out,
+                        void *hip_stream) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (const int rc = check_query_outputs(out, flags)) return rc;
+    if (n >= (1u << 31)) return fail(PUPIL_ERR_INVALID, "too many rays in one query");
+    if (n == 0) return PUPIL_OK;
+    if (!rays_device) return fail(PUPIL_ERR_INVALID, "null argument");
+    // the resolve kernel loads a ray as two float4 (the traversal's scalar loads need 4 B)
+    if ((uintptr_t)rays_device & 15u) return fail(PUPIL_ERR_INVALID, "misaligned ray list (16 B)");
+    HIP_TRY(hipSetDevice(pt->device));
+    return run_query(pt, n, (const float4 *)rays_device, flags, out, (hipStream_t)hip_stream, nullptr, [] {});
+}
+
+// The G-buffer form: camera_path's ray at film jitter (jitter_x, jitter_y) through every local
+// pixel (k_flow_rays, into the flow pass's ray scratch or rays_out_device), then the same trace
+// and resolve; outputs indexed like the frame buffers.
+int pupil_pt_query_camera(pupil_pt *pt, float jitter_x, float jitter_y, uint32_t compact, uint32_t tile_size,
+                          uint32_t tile_rank, uint32_t tile_world, void *rays_out_device, const pupil_ray_hits *out,
+                          void *hip_stream) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (const int rc = check_query_outputs(out, 0u)) return rc;
+    if ((uintptr_t)rays_out_device & 15u) return fail(PUPIL_ERR_INVALID, "misaligned ray list (16 B)");
+    const uint32_t world = tile_world ? tile_world : 1u;
+    const uint32_t ts = tile_size ? tile_size : 32u;
+    if (tile_rank >= world) return fail(PUPIL_ERR_INVALID, "tile_rank >= tile_world");
+    HIP_TRY(hipSetDevice(pt->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const uint32_t key[5] = {pt->width, pt->height, ts, tile_rank, world};
+    const uint32_t *map = nullptr;
+    uint32_t num_local = 0;
+    if (const int rc = local_pixel_map(pt, key, &map, &num_local)) return rc;
+    if (num_local == 0) return PUPIL_OK;
+    // a rank's outputs in the frame's index space go to their pixels (the map; null = every pixel)
+    const uint32_t *scatter = compact ? nullptr : map;
+    float4 *rays = (float4 *)rays_out_device;
+    if (!rays) {  // the flow pass's list, sized for the whole image: it serves every tiling
+        if (!pt->flow_rays) HIP_TRY(pt->alloc(&pt->flow_rays, 2 * (size_t)pt->width * pt->height));
+        rays = pt->flow_rays;
+    }
+    return run_query(pt, num_local, rays, 0u, out, s, scatter, [&] {
+        launch_flow_rays(pt->sc, pt->width, pt->height, map, num_local, jitter_x, jitter_y, rays, s);
+    });
+}
+
+// queries and rays since create, growths of the engine-owned scratch, and the device time of
+// the last query from the events around it (waits for that query); any out pointer may be NULL
+int pupil_pt_query_info(pupil_pt *pt, uint64_t *queries, uint64_t *rays, uint64_t *scratch_grows, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (queries) *queries = pt->queries;
+    if (rays) *rays = pt->query_rays;
+    if (scratch_grows) *scratch_grows = pt->query_grows;
+    if (last_ms) {
+        *last_ms = 0.0;
+        if (pt->queries) {
+            HIP_TRY(hipSetDevice(pt->device));
+            HIP_TRY(hipEventSynchronize(pt->ev_q1));
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, pt->ev_q0, pt->ev_q1));
+            *last_ms = ms;
+        }
+    }
     return PUPIL_OK;
 }
 

@@ -24,11 +24,12 @@ namespace {
 
 constexpr int kFlowBlock = 256;
 
-// The camera ray of camera_path (pt_shade.h) with the film jitter fixed at the pixel centre:
-// the same operations in the same order, so the ray is the one a render would trace for a
-// jitter of exactly (0.5, 0.5).
-__device__ __forceinline__ vec3 centre_ray(const Camera &cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y) {
-    const vec4 film = v4(((float)x + 0.5f) / (float)width, ((float)y + 0.5f) / (float)height, 0.f, 1.f);
+// The camera ray of camera_path (pt_shade.h) with the film jitter given instead of drawn: the
+// same operations in the same order, so the ray is the one a render would trace for a jitter of
+// exactly (jx, jy) -- the pixel centre (0.5, 0.5) for the flow pass.
+__device__ __forceinline__ vec3 jittered_ray(const Camera &cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
+                                             float jx, float jy) {
+    const vec4 film = v4(((float)x + jx) / (float)width, ((float)y + jy) / (float)height, 0.f, 1.f);
     const float *m = cam.s2c;
     vec4 d = v4(dot(v4(m[0], m[1], m[2], m[3]), film), dot(v4(m[4], m[5], m[6], m[7]), film),
                 dot(v4(m[8], m[9], m[10], m[11]), film), dot(v4(m[12], m[13], m[14], m[15]), film));
@@ -44,13 +45,14 @@ __device__ __forceinline__ vec3 centre_ray(const Camera &cam, uint32_t width, ui
 // ray l = (o, d, tmin, tmax) of local pixel l, the 8-float format of the kModeRays traversal;
 // tmin / tmax are the render's camera-ray interval
 __global__ __launch_bounds__(kFlowBlock) void k_flow_rays(Camera cam, uint32_t width, uint32_t height,
-                                                          const uint32_t *pixel_map, uint32_t n, float4 *rays) {
+                                                          const uint32_t *pixel_map, uint32_t n, float jx, float jy,
+                                                          float4 *rays) {
     const uint32_t l = blockIdx.x * kFlowBlock + threadIdx.x;
     if (l >= n) return;
     const uint32_t pixel = pixel_map ? pixel_map[l] : l;
     const uint32_t y = pixel / width;
     const uint32_t x = pixel - y * width;
-    const vec3 d = centre_ray(cam, width, height, x, y);
+    const vec3 d = jittered_ray(cam, width, height, x, y, jx, jy);
     rays[2 * (size_t)l] = make_float4(cam.c2w[3], cam.c2w[7], cam.c2w[11], d.x);
     rays[2 * (size_t)l + 1] = make_float4(d.y, d.z, 0.001f, kMaxDistance);
 }
@@ -138,9 +140,9 @@ __global__ __launch_bounds__(kFlowBlock) void k_flow_project_deform(DeviceScene 
 }  // namespace
 
 void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, const uint32_t *pixel_map, uint32_t n,
-                      float4 *rays, hipStream_t s) {
+                      float jitter_x, float jitter_y, float4 *rays, hipStream_t s) {
     hipLaunchKernelGGL(k_flow_rays, dim3((n + kFlowBlock - 1) / kFlowBlock), dim3(kFlowBlock), 0, s, sc.camera, width,
-                       height, pixel_map, n, rays);
+                       height, pixel_map, n, jitter_x, jitter_y, rays);
 }
 
 void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays, const float4 *hits,

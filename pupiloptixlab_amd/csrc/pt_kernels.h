@@ -63,7 +63,8 @@ constexpr uint32_t kWorkShards = 8, kWorkStride = 32, kWorkKind = (2 * kWorkShar
 // slot 1 * kWorkKind is unused (it served the separate any-hit launch, retired in r01)
 constexpr uint32_t kWorkExtend = 0, kWorkRays = 2 * kWorkKind, kWorkFrame = 3 * kWorkKind;
 constexpr uint32_t kWorkFlow = 4 * kWorkKind;  // the flow pass's traversal (pupil_pt_motion_vectors)
-constexpr uint32_t kWorkSlots = 5 * kWorkKind;
+constexpr uint32_t kWorkQuery = 5 * kWorkKind;  // ray queries from device memory (pupil_pt_query_rays / _query_camera)
+constexpr uint32_t kWorkSlots = 6 * kWorkKind;
 constexpr uint32_t kStartBins = 16;                                    // [16..24] material bin starts
 constexpr uint32_t kStartNext = 25, kStartShadow = 26;                 // next / shadow regions of nxsh
 constexpr uint32_t kScratch = 27;
@@ -231,13 +232,39 @@ struct FlowJob {
     uint32_t n;                  // local pixels
     uint32_t compact;
 };
+// (jitter_x, jitter_y): the film jitter of every ray, camera_path's (jx, jy); the flow pass passes
+// the pixel centre (0.5, 0.5)
 void launch_flow_rays(const DeviceScene &sc, uint32_t width, uint32_t height, const uint32_t *pixel_map, uint32_t n,
-                      float4 *rays, hipStream_t s);
+                      float jitter_x, float jitter_y, float4 *rays, hipStream_t s);
 // prev_verts (deforming meshes, pupil_pt_snapshot_shape_vertices): device, per instance the
 // vertices its shape had before the update (3 floats per vertex) or null.  null = no shape holds
 // a snapshot: the kernel and its arguments are then those of the rigid-only pass.
 void launch_flow_project(const DeviceScene &sc, const FlowJob &job, const float4 *rays, const float4 *hits,
                          float2 *flow, hipStream_t s, const float *const *prev_verts = nullptr);
+// ray queries (pt_query.hip): the compact hits of a kModeRays launch (launch_trace_debug's 4 floats
+// per ray) resolved into the arrays that are not null -- instance, face within its shape, material
+// (-1 on a miss), and reconstruct()'s position, normal (two-sided flip applied) and texcoord (0 on
+// a miss).  rays: the list the hits were traced from, 2 float4 per ray.  prim_slot / slots (flat
+// scenes with a position, normal or texcoord wanted): global primitive id -> record slot, as
+// launch_query_prim_slots derives it from the `slots` record slots of DeviceScene::prims;
+// two-level scenes pass null and any slots > 0
+struct QueryJob {
+    const float4 *rays;
+    const float4 *hits;
+    uint32_t n;
+    uint32_t slots;
+    const uint32_t *prim_slot;
+    int32_t *instance, *primitive, *material;
+    float *position, *normal;  // 3 floats per ray
+    float2 *texcoord;
+    // a tiled camera query in the frame's index space: ray l's outputs go to element out_index[l]
+    // (null = l), and its hit is copied to hit_out there (null = the hits are where they belong)
+    const uint32_t *out_index;
+    float4 *hit_out;
+};
+void launch_query_prim_slots(const float4 *recs, uint32_t slots, uint32_t num_prims, uint32_t *prim_slot,
+                             hipStream_t s);
+void launch_query_resolve(const DeviceScene &sc, const QueryJob &job, hipStream_t s);
 // the area-emitter table rebuilt in place from the engine's own arrays (pt_emitters.hip): in every
 // DevEmitter pos, nrm, area and select_probability (a sphere: center, radius, area and
 // select_probability), the selection CDF and, unless null, its guide table

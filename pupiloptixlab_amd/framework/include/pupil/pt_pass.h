@@ -69,6 +69,17 @@ public:
     // compact order when the frame is gathered) for optix::Denoiser::ExecutionData::motion_vector.
     // Synchronised like OnRun.  After a single OnRun the flow is zero on every surface.
     bool ComputeMotionVectors() noexcept;
+    // Ray queries from device memory (pupil_pt_query_rays / _query_camera): what n device rays
+    // (8 floats each: origin, direction, tmin, tmax) hit, or what the camera ray through every
+    // pixel of this rank's tiles hits at film jitter (jitter_x, jitter_y), into the device arrays
+    // of `out` that are not null.  Enqueued on `stream` (a hipStream_t; QueryCamera: the pass's
+    // own), ordered after every OnRun enqueued so far; the caller synchronises before reading.
+    // Between OnRuns, from OnRun's thread.  Nothing the pass renders changes.  False: no scene,
+    // or the engine refused (pupil_last_error()).
+    bool QueryRays(uint32_t n, const void *rays_device, const pupil_ray_hits &out, bool any_hit = false,
+                   void *stream = nullptr) noexcept;
+    bool QueryCamera(const pupil_ray_hits &out, float jitter_x = 0.5f, float jitter_y = 0.5f,
+                     void *rays_out_device = nullptr) noexcept;
 
 private:
     void BindingEventCallback() noexcept;

@@ -226,6 +226,30 @@ bool PTPass::ComputeMotionVectors() noexcept {
     return hipStreamSynchronize(m_stream) == hipSuccess;
 }
 
+bool PTPass::QueryRays(uint32_t n, const void *rays_device, const pupil_ray_hits &out, bool any_hit,
+                       void *stream) noexcept {
+    if (!m_engine) return false;
+    if (pupil_pt_query_rays(m_engine, n, rays_device, any_hit ? (uint32_t)PUPIL_QUERY_ANY_HIT : 0u, &out, stream) !=
+        PUPIL_OK) {
+        Log("%s: ray query failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    return true;
+}
+
+bool PTPass::QueryCamera(const pupil_ray_hits &out, float jitter_x, float jitter_y, void *rays_out_device) noexcept {
+    if (!m_engine) return false;
+    FrameGather *gather = util::Singleton<System>::instance()->Gather();
+    const uint32_t tile = gather ? gather->Info().tile : 0u, rank = gather ? (uint32_t)gather->Info().rank : 0u,
+                   world = gather ? (uint32_t)gather->Info().world : 1u;
+    if (pupil_pt_query_camera(m_engine, jitter_x, jitter_y, gather ? 1u : 0u, tile, rank, world, rays_out_device, &out,
+                              m_stream) != PUPIL_OK) {
+        Log("%s: camera query failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    return true;
+}
+
 void PTPass::SetMaxDepth(int depth) noexcept {
     depth = std::clamp(depth, 1, 128);  // Inspector clamp, pt_pass.cpp:229
     if (depth != m_max_depth) {

@@ -27,6 +27,37 @@ from .abi import check, load_library
 
 FINAL_RESULT = "final result"  # BufferManager::DEFAULT_FINAL_RESULT_BUFFER_NAME
 
+# outputs of a ray query (the fields of pupil_ray_hits): channels and f(loat32) / i(nt32)
+QUERY_OUTPUTS = {"hit": (4, "f"), "instance": (1, "i"), "primitive": (1, "i"), "material": (1, "i"),
+                 "position": (3, "f"), "normal": (3, "f"), "texcoord": (2, "f")}
+QUERY_WANT_ALL = tuple(QUERY_OUTPUTS)
+
+
+def camera_ray(s2c, c2w, width, height, x, y, jitter=(0.5, 0.5)):
+    """The camera ray through pixel (x, y) at film jitter `jitter` as 8 float32 (o, d, tmin, tmax
+    of a camera ray), computed in float32 in the engine's order of operations (camera_path):
+    s2c, c2w are the (4, 4) sample_to_camera and camera_to_world."""
+    import numpy as np
+
+    f = np.float32
+
+    def dot(a, b):
+        acc = f(a[0]) * f(b[0])
+        for k in range(1, len(a)):
+            acc = f(acc + f(a[k]) * f(b[k]))
+        return acc
+
+    def normalize(v):
+        inv = f(1.0) / np.sqrt(dot(v, v))
+        return [f(c * inv) for c in v]
+
+    film = [f(f(f(x) + f(jitter[0])) / f(width)), f(f(f(y) + f(jitter[1])) / f(height)), f(0.0), f(1.0)]
+    d = [dot(s2c[r], film) for r in range(4)]
+    inv_w = f(1.0) / d[3]
+    d = normalize([f(d[0] * inv_w), f(d[1] * inv_w), f(d[2] * inv_w), f(0.0)])
+    d = normalize([dot(c2w[r], d) for r in range(3)])
+    return np.array([c2w[0][3], c2w[1][3], c2w[2][3], d[0], d[1], d[2], 0.001, 1e16], np.float32)
+
 
 class Events:
     """util::Event dispatcher subset: CameraChange / RenderInstanceUpdate / SceneLoad."""
@@ -613,6 +644,126 @@ class PTPass(Pass):
         check(self._lib.pupil_pt_motion_vectors(self._pt, s2c, c2w, ptw, C.c_void_p(mv.data_ptr()),
                                                 1 if world > 1 else 0, ts, rank, world, C.c_void_p(s.cuda_stream)))
         return mv
+
+    # ---- ray queries from device memory (pupil_pt_query_rays / _query_camera)
+    def _query_outputs(self, n, want, out):
+        """The tensors of a query's outputs, (n, channels) each, taken from `out` where it holds a
+        fitting one and allocated otherwise, and the pupil_ray_hits that names them."""
+        torch = self._torch
+        tensors = {}
+        hits = abi.RayHits()
+        for name in want:
+            if name not in QUERY_OUTPUTS:
+                raise ValueError(f"unknown query output {name!r} (one of {', '.join(QUERY_OUTPUTS)})")
+            channels, kind = QUERY_OUTPUTS[name]
+            dtype = torch.float32 if kind == "f" else torch.int32
+            shape = (n, channels) if channels > 1 else (n,)
+            t = out.get(name) if out else None
+            if t is not None:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device_index
+                        and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+                    raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on "
+                                     f"{self.device}")
+            else:
+                t = torch.empty(shape, dtype=dtype, device=self.device)
+            tensors[name] = t
+            setattr(hits, name, t.data_ptr() if n else None)
+        return tensors, hits
+
+    def _query_stream(self, stream, tensors):
+        """The stream a query runs on.  Tensors allocated on the current stream and written on
+        another one are made known to torch's caching allocator (record_stream), so their memory
+        is not handed out again before the query has passed it."""
+        torch = self._torch
+        current = torch.cuda.current_stream(self.device_index)
+        s = stream if stream is not None else current
+        if s.cuda_stream != current.cuda_stream:
+            for t in tensors:
+                if t is not None and t.numel():
+                    t.record_stream(s)
+        return s
+
+    def trace(self, rays, any_hit: bool = False, want=QUERY_WANT_ALL, out=None, stream=None) -> dict:
+        """What the rays hit (pupil_pt_query_rays).  rays: (n, 8) contiguous float32 tensor on the
+        pass's device, (ox, oy, oz, dx, dy, dz, tmin, tmax) per ray, traced in place.  Returns
+        the outputs named in `want` as device tensors: "hit" (n, 4) = t, b1, b2, primitive id
+        bits (t = -1 on a miss); "instance", "primitive" (face within the shape), "material" (n,)
+        int32, -1 on a miss; "position", "normal" (n, 3) and "texcoord" (n, 2), 0 on a miss.
+        any_hit: occlusion only, want = ("hit",), t = 1 or -1.  out: tensors of an earlier call
+        to write into.  Asynchronous on `stream` (default: the current stream), after every
+        render enqueued so far; nothing of the pass's accumulation changes.  On a stream other
+        than the current one the rays and outputs are recorded on it (Tensor.record_stream), and
+        the caller orders its own reads behind that stream."""
+        torch = self._torch
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("trace needs a torch tensor of rays")
+        # what the kernels would read out of bounds first, then where the tensor lives
+        if rays.dtype != torch.float32:
+            raise ValueError(f"trace needs float32 rays, got {rays.dtype}")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace needs an (n, 8) tensor of rays, got {tuple(rays.shape)}")
+        if not rays.is_contiguous():
+            raise ValueError("trace needs contiguous rays")
+        if not rays.is_cuda or rays.device.index != self.device_index:
+            raise ValueError(f"trace needs rays on {self.device}, got a {rays.device} tensor")
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        n = int(rays.shape[0])
+        if any_hit and want is QUERY_WANT_ALL:
+            want = ("hit",)
+        tensors, hits = self._query_outputs(n, tuple(want), out)
+        if n == 0 and tensors:
+            return tensors
+        s = self._query_stream(stream, [rays, *tensors.values()])
+        check(self._lib.pupil_pt_query_rays(self._pt, n, C.c_void_p(rays.data_ptr()),
+                                            abi.QUERY_ANY_HIT if any_hit else 0, C.byref(hits),
+                                            C.c_void_p(s.cuda_stream)))
+        return tensors
+
+    def primary_hits(self, jitter=(0.5, 0.5), want=QUERY_WANT_ALL, return_rays: bool = False, stream=None) -> dict:
+        """The G-buffer (pupil_pt_query_camera): trace()'s outputs for the camera ray through every
+        pixel at film jitter `jitter` ((0.5, 0.5) = the pixel centre), in the index space of the
+        other buffers (the current tiling, as motion_vectors()).  return_rays: the rays too, as
+        "rays" (n, 8).  The camera is the one in the engine (that of the last render)."""
+        torch = self._torch
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        ts, rank, world = self.tile
+        n = self.local_pixel_count() if world > 1 else self.width * self.height
+        tensors, hits = self._query_outputs(n, tuple(want), None)
+        rays = torch.empty((n, 8), dtype=torch.float32, device=self.device) if return_rays else None
+        s = self._query_stream(stream, [rays, *tensors.values()])
+        if n:
+            check(self._lib.pupil_pt_query_camera(self._pt, float(jitter[0]), float(jitter[1]), 1 if world > 1 else 0,
+                                                  ts, rank, world,
+                                                  C.c_void_p(rays.data_ptr()) if rays is not None else None,
+                                                  C.byref(hits), C.c_void_p(s.cuda_stream)))
+        if rays is not None:
+            tensors["rays"] = rays
+        return tensors
+
+    def pick(self, x: int, y: int):
+        """What lies under the centre of pixel (x, y) (row 0 = bottom, as image()): a dict of
+        instance, primitive, material (ints) and t (float), or None where the ray leaves the
+        scene.  One ray through trace(); waits for the result."""
+        import numpy as np
+
+        if not (0 <= int(x) < self.width and 0 <= int(y) < self.height):
+            raise ValueError(f"pixel ({x}, {y}) is outside the {self.width} x {self.height} film")
+        s2c, c2w = (np.asarray(m, np.float32).reshape(4, 4) for m in self._cam)
+        ray = camera_ray(s2c, c2w, self.width, self.height, int(x), int(y))
+        rays = self._torch.from_numpy(ray.reshape(1, 8)).to(self.device)
+        r = self.trace(rays, want=("hit", "instance", "primitive", "material"))
+        t = float(r["hit"][0, 0].item())  # the copy waits for the query
+        if int(r["instance"][0].item()) < 0:
+            return None
+        return {"instance": int(r["instance"][0].item()), "primitive": int(r["primitive"][0].item()),
+                "material": int(r["material"][0].item()), "t": t}
+
+    def query_info(self) -> dict:
+        q, r, g, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_query_info(self._pt, C.byref(q), C.byref(r), C.byref(g), C.byref(ms)))
+        return {"queries": q.value, "rays": r.value, "scratch_grows": g.value, "last_ms": ms.value}
 
     def on_run(self):
         self.render(1)
