@@ -636,6 +636,66 @@ int pupil_pt_query_camera(pupil_pt *pt, float jitter_x, float jitter_y, uint32_t
                           void *hip_stream);
 int pupil_pt_query_info(pupil_pt *pt, uint64_t *queries, uint64_t *rays, uint64_t *scratch_grows, double *last_ms);
 
+/* Path-traced radiance along rays from device memory: what does this ray see.  The integrator of
+ * pupil_pt_render (MIS, every BSDF, area and env emitters) over a ray list that is already on the
+ * device instead of the scene's pinhole camera: training batches of rays from many cameras,
+ * light-probe and lightmap baking, panoramic / fisheye / orthographic / thin-lens cameras, a second
+ * view.  The reference has no such entry: no ABI bump, detect the symbols.
+ *
+ * Rays: the layout of pupil_pt_query_rays (ox, oy, oz, dx, dy, dz, tmin, tmax), 16-B aligned, read in
+ * place.  The direction must be unit length; it is used as given, not re-normalised.  Floats 6 and
+ * 7 are IGNORED: every segment of a path, the first included, uses the path tracer's window
+ * [0.001, 1e16], so one tensor serves both entries.
+ *
+ * Launch: random_seed, sample_cnt, spp, accumulate and max_depth (0 = the scene's) mean what they
+ * mean for pupil_pt_render; tile_*, collect_stats and hints are ignored.
+ *
+ * Sample s of ray i is one path of __raygen__main (main.cu:36-194) whose first ray is ray i.  Its
+ * RNG is rng_init(id_i, random_seed + s) followed by two discarded draws (the film jitter a camera
+ * path draws), id_i = stream_ids_device[i], or i when that is NULL.  The path's radiance enters
+ * radiance[i] by the render's running mean, the count being sample_cnt + s when accumulate is set
+ * (main.cu:187-191); without accumulate the last sample stays, as in a frame.  So if ray i is the
+ * camera ray a render of seed random_seed draws for pixel id_i, radiance[i], albedo[i] and
+ * normal[i] equal that render's pixel bit for bit.  The result does not depend on how the call is
+ * cut into chunks.
+ *
+ * Asynchronous on hip_stream (NULL = the null stream), with no device-wide sync: ordered by stream
+ * events after every render, flow pass, query and radiance call enqueued so far (they share the
+ * traversal's overflow stacks), and later ones order themselves behind it.  Adds nothing to the
+ * ray counters of pupil_pt_stats, touches neither any frame's accumulation, the sample count nor
+ * the frames in flight, and reads the engine's camera nowhere.
+ *
+ * Scratch: paths are processed in chunks of at most PUPIL_RADIANCE_CHUNK paths (environment, read
+ * at pupil_pt_create; default 16777216, at least 64), 146 B each, so the scratch is bounded
+ * whatever n * spp is.  It grows geometrically up to that bound and never shrinks; a growth waits
+ * for the calls in flight.  A call that fits allocates nothing and synchronises nothing (depths
+ * above 64 read the list lengths back every 16 bounces, as a render of such a depth does).
+ * Memory budget: the scratch an engine holds is 146 B x min(PUPIL_RADIANCE_CHUNK, the largest
+ * n * spp of any call so far; up to twice that after a growth), kept until pupil_pt_destroy: with
+ * the default, at most 2.4 GB, reached by the first call of 16.8 M paths or more (1920x1080 rays at
+ * 8 spp is 16.6 M) and held from then on.  PUPIL_RADIANCE_CHUNK=4194304 caps it at 0.6 GB; such a
+ * call then runs as four chunks and takes about 1.15 times as long (every stage drains four launch
+ * tails instead of one).
+ *
+ * n = 0: PUPIL_OK, nothing is enqueued.  PUPIL_ERR_INVALID, before anything is enqueued: pt, launch,
+ * out, out->radiance or (n > 0) rays_device NULL, spp = 0, n >= 2^31, a misaligned pointer
+ * (radiance and the rays 16 B, everything else 4 B).
+ *
+ * pupil_pt_radiance_info: calls and rays since create, the extension and shadow rays their paths
+ * cast (the first ray of a path is not among them; totals of the radiance calls' own), growths of
+ * the scratch, and the device time of the last call from events around it.  Asking for the ray
+ * totals or the time waits for the last call; any out pointer may be NULL. */
+typedef struct pupil_ray_radiance {
+    void *radiance; /* float4 per ray, required: rgb + 1, the running mean exactly as the frame's accum buffer */
+    void *albedo;   /* float3 per ray, optional: the first hit's albedo AOV (0 on a miss) */
+    void *normal;   /* float3 per ray, optional: the first hit's normal AOV (0 on a miss) */
+} pupil_ray_radiance;
+int pupil_pt_radiance_rays(pupil_pt *pt, uint32_t n, const void *rays_device /* 8 floats per ray */,
+                           const uint32_t *stream_ids_device /* n, or NULL = the ray's index */,
+                           const pupil_pt_launch *launch, const pupil_ray_radiance *out, void *hip_stream);
+int pupil_pt_radiance_info(pupil_pt *pt, uint64_t *calls, uint64_t *rays, uint64_t *extension_rays,
+                           uint64_t *shadow_rays, uint64_t *scratch_grows, double *last_ms);
+
 /* ---- verification entry points (used by the parity tests) ----
  * closest (any_hit = 0) or any hit (any_hit = 1) for n host rays packed as
  * (ox, oy, oz, dx, dy, dz, tmin, tmax); out (host) = (t, b1, b2, prim id bits)

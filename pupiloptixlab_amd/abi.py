@@ -131,6 +131,11 @@ class RayHits(C.Structure):
                 ("texcoord", C.c_void_p)]
 
 
+class RayRadiance(C.Structure):
+    """pupil_ray_radiance: device pointers; radiance is required, NULL = not wanted for the AOVs."""
+    _fields_ = [("radiance", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every entry is declared in include/pupil_pt.h
 SIGNATURES = {
     "pupil_last_error": (C.c_char_p, []),
@@ -173,6 +178,11 @@ SIGNATURES = {
                                          C.c_uint32, C.c_void_p, C.POINTER(RayHits), C.c_void_p]),
     "pupil_pt_query_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_pt_radiance_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Launch),
+                                          C.POINTER(RayRadiance), C.c_void_p]),
+    "pupil_pt_radiance_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_double)]),
     "pupil_pt_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, C.c_int]),
     "pupil_pt_export_bvh4": (C.c_int, [C.c_void_p, u32p, C.c_void_p, u32p, f32p, C.POINTER(C.c_int32)]),
     "pupil_debug_math": (C.c_int, [C.c_int, C.c_uint32, f32p, f32p, f32p]),

@@ -226,6 +226,23 @@ struct pupil_pt {
     bool query_slot_valid = false;
     uint64_t queries = 0, query_rays = 0, query_grows = 0;
     hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
+    // radiance along rays (pupil_pt_radiance_rays): a path state, queues and identity id list of
+    // its own, carved from one block (rad_block) of rad_cap paths, which grows geometrically up to
+    // rad_chunk (PUPIL_RADIANCE_CHUNK, read at create) and never shrinks.  rad_cum: its own device
+    // totals -- the kCullShards sharded counters of the extension rays its terminal-ray cull
+    // resolved, each on its own 128-B line as in cull_cum, then (kRadTotals) the extension [0] and
+    // shadow [1] rays its flags partitions listed.
+    // ev_r0 / ev_r1 bracket the last call on its stream
+    size_t rad_chunk = (size_t)1 << 24;
+    size_t rad_cap = 0;
+    void *rad_block = nullptr;
+    PathState rad_ps{};
+    Queues rad_q{};
+    uint32_t *rad_ids = nullptr;
+    static constexpr uint32_t kRadTotals = kCullShards * kCullStride;  // words of rad_cum before the two totals
+    unsigned long long *rad_cum = nullptr;
+    uint64_t rad_calls = 0, rad_rays = 0, rad_grows = 0;
+    hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -275,6 +292,9 @@ struct pupil_pt {
         if (ev_snap) (void)hipEventDestroy(ev_snap);
         if (ev_q0) (void)hipEventDestroy(ev_q0);
         if (ev_q1) (void)hipEventDestroy(ev_q1);
+        if (rad_block) (void)hipFree(rad_block);
+        if (ev_r0) (void)hipEventDestroy(ev_r0);
+        if (ev_r1) (void)hipEventDestroy(ev_r1);
         if (ev_verts) (void)hipEventDestroy(ev_verts);
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
@@ -961,6 +981,9 @@ void read_knobs(pupil_pt *pt) {
     if (const char *g = std::getenv("PUPIL_PIPE_SPLIT")) pt->knobs.split = std::atoi(g) != 0;
     if (const char *g = std::getenv("PUPIL_PIPE_RAMP")) pt->knobs.ramp = (uint32_t)std::max(0, std::atoi(g));
     if (const char *g = std::getenv("PUPIL_FRAME_PATHS")) pt->knobs.frame_paths = std::max(0.0, std::atof(g));
+    // most paths of one chunk of pupil_pt_radiance_rays, which bounds its scratch (at least a wave)
+    if (const char *g = std::getenv("PUPIL_RADIANCE_CHUNK"))
+        pt->rad_chunk = (size_t)std::min(2147483647.0, std::max(64.0, std::atof(g)));
     sc.trace_node_min = 8;  // node phase ends below 8 active lanes (7 waves: 8 and 12 beat 4 by 1.5 %; 2 is slower)
     if (const char *r = std::getenv("PUPIL_NODE_MIN")) sc.trace_node_min = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
 }
@@ -970,9 +993,11 @@ int alloc_workspace(pupil_pt *pt) {
     pt->ovf_threads = trace_grid_blocks() * (uint32_t)kTraceBlock;
     if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * kStackOvf) || pt->alloc(&pt->trace_counters, 32) ||
         pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->q.counts, kCountSlots) || pt->alloc(&pt->q.work, kWorkSlots) ||
-        pt->alloc(&pt->d_cull, 1 + kCullSetMax) || pt->alloc(&pt->cull_cum, 2 * kCullShards * kCullStride))
+        pt->alloc(&pt->d_cull, 1 + kCullSetMax) || pt->alloc(&pt->cull_cum, 2 * kCullShards * kCullStride) ||
+        pt->alloc(&pt->rad_cum, pupil_pt::kRadTotals + 2))
         return fail(PUPIL_ERR_OOM, "workspace allocation failed");
     if (hipMemset(pt->q.work, 0, kWorkSlots * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(pt->rad_cum, 0, (pupil_pt::kRadTotals + 2) * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(pt->cull_cum, 0, 2 * kCullShards * kCullStride * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(pt->ray_cum, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
         return fail(PUPIL_ERR_HIP, "workspace clear failed");
@@ -2201,6 +2226,197 @@ int pupil_pt_query_info(pupil_pt *pt, uint64_t *queries, uint64_t *rays, uint64_
             HIP_TRY(hipEventElapsedTime(&ms, pt->ev_q0, pt->ev_q1));
             *last_ms = ms;
         }
+    }
+    return PUPIL_OK;
+}
+
+extern "C++" {
+namespace {
+
+// The radiance call's scratch for `need` <= rad_chunk paths: path state, queues and the identity
+// id list carved from one block.  Grows geometrically up to rad_chunk and never shrinks; a growth
+// waits for the calls in flight (everything later enqueued is ordered behind them on
+// last_stream) and fills the id list on s.  A call that fits allocates and synchronises nothing.
+int ensure_radiance_state(pupil_pt *pt, size_t need, hipStream_t s) {
+    if (need <= pt->rad_cap) return PUPIL_OK;
+    if (pt->rad_block && pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
+    const size_t cap = std::min(pt->rad_chunk, std::max(need, 2 * pt->rad_cap));
+    auto up = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
+    const size_t rec = up(16 * cap), byte = up(cap);
+    const size_t hist = up(sizeof(uint32_t) * partition_hist_entries((uint32_t)cap));
+    const size_t total = 8 * rec + 2 * byte + up(4 * cap) + up(8 * cap) + up(4 * cap) + hist + up(4 * kCountSlots);
+    if (pt->rad_block) (void)hipFree(pt->rad_block);
+    pt->rad_block = nullptr;
+    pt->rad_cap = 0;
+    HIP_TRY(hipMalloc(&pt->rad_block, total));
+    char *b = (char *)pt->rad_block;
+    auto take = [&b](size_t bytes) {
+        char *p = b;
+        b += bytes;
+        return (void *)p;
+    };
+    PathState &ps = pt->rad_ps;
+    ps.ray_o = (float4 *)take(rec);
+    ps.ray_d = (float4 *)take(rec);
+    ps.hit = (float4 *)take(rec);
+    ps.thr = (float4 *)take(rec);
+    ps.rad = (float4 *)take(rec);
+    ps.misc = (uint4 *)take(rec);
+    ps.sh_d = (float4 *)take(rec);
+    ps.sh_c = (float4 *)take(rec);
+    ps.mbin = (uint8_t *)take(byte);
+    ps.sflags = (uint8_t *)take(byte);
+    Queues &q = pt->rad_q;
+    q.bins = (uint32_t *)take(up(4 * cap));
+    q.nxsh = (uint32_t *)take(up(8 * cap));
+    pt->rad_ids = (uint32_t *)take(up(4 * cap));
+    q.hist = (uint32_t *)take(hist);
+    q.counts = (uint32_t *)take(up(4 * kCountSlots));
+    q.work = pt->q.work + kWorkRadiance;
+    q.capacity = (uint32_t)cap;
+    pt->rad_cap = cap;
+    pt->rad_grows++;
+    launch_identity_ids(pt->rad_ids, (uint32_t)cap, s);
+    return PUPIL_OK;
+}
+
+// One chunk of a radiance call, enqueued on s: samples [s0, s0 + ns) of rays [r0, r0 + nr), ns * nr
+// paths in the call's own path state.  Generate, the primary extend in its queue form (origins
+// from the path state), then per bounce what render_pipelined runs for one frame without a ring --
+// flags partition, mixed traversal, material partition (or list shading), shade -- and the
+// accumulate into the caller's arrays at the chunk's offset.  Per path every operation and its
+// order are the render's.
+int radiance_chunk(pupil_pt *pt, hipStream_t s, const float4 *rays, const uint32_t *stream_ids,
+                   const pupil_pt_launch *launch, const pupil_ray_radiance *out, uint32_t depth, uint32_t r0,
+                   uint32_t nr, uint32_t s0, uint32_t ns) {
+    const PathState &ps = pt->rad_ps;
+    const Queues &q = pt->rad_q;
+    const uint32_t np = nr * ns;
+    // no flags byte of an earlier chunk is listed, no bin byte of one is partitioned (list
+    // shading partitions no bin bytes)
+    HIP_TRY(hipMemsetAsync(ps.sflags, 0, np, s));
+    if (!pt->shade_list) HIP_TRY(hipMemsetAsync(ps.mbin, 0xFF, np, s));
+    launch_generate_rays(RayGenJob{rays, stream_ids, r0, nr, np, launch->random_seed + s0}, ps, s);
+    FrameParams fp{};
+    fp.num_local = nr;
+    fp.num_paths = np;
+    fp.spp = ns;
+    fp.seed0 = launch->random_seed + s0;
+    fp.cnt0 = launch->sample_cnt + (launch->accumulate ? s0 : 0u);
+    fp.accumulate = launch->accumulate;
+    fp.max_depth = depth;
+    fp.compact = 1;
+    fp.aov_local = 1;  // AOVs and radiance are indexed by the ray, from the chunk's first
+    fp.group = 1;
+    fp.accum = (float4 *)out->radiance + r0;
+    fp.albedo = out->albedo ? (float *)out->albedo + 3 * (size_t)r0 : nullptr;
+    fp.normal = out->normal ? (float *)out->normal + 3 * (size_t)r0 : nullptr;
+    fp.cull_cum = pt->sc.cull_n ? pt->rad_cum : nullptr;
+    for (uint32_t b = 0; b < depth; b++) {
+        if (b == 0) {
+            launch_extend(pt->sc, ps, q, pt->rad_ids, nullptr, np, pt->ovf, pt->ovf_threads, nullptr, s);
+        } else {
+            // the rays the last shade spawned, in increasing path id: next and shadow lists -> q.nxsh
+            launch_partition(ps.sflags, np, 2, kPartFlags, sflag_tag(depth, b - 1), q.nxsh, q.hist, q.counts + kCntNext,
+                             q.counts + kStartNext, nullptr, nullptr, s, pt->rad_cum + pupil_pt::kRadTotals, nullptr);
+            if (depth > 64 && b % 16 == 0) {  // as a render of such a depth: stop once no path is left
+                uint32_t c[2] = {1, 1};
+                HIP_TRY(hipMemcpyAsync(c, q.counts + kCntNext, sizeof(c), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                if (c[0] == 0 && c[1] == 0) break;
+            }
+            launch_trace_mixed(pt->sc, ps, q, pt->ovf, pt->ovf_threads, nullptr, s);
+        }
+        if (!pt->shade_list)
+            launch_partition(ps.mbin, np, kPartMaxBins, kPartExclusive, 0u, q.bins, q.hist, q.counts,
+                             q.counts + kStartBins, q.counts + kScratch, nullptr, s, nullptr, nullptr, pt->bin_mask);
+        if (depth > 63) HIP_TRY(hipMemsetAsync(ps.sflags, 0, np, s));  // the 6-bit tags would alias
+        const ShadeList list = !pt->shade_list ? kShadeBins : (b == 0 ? kShadeAll : kShadeNext);
+        launch_shade(pt->sc, fp, ps, q, sflag_tag(depth, b), s, list, 0u, b == 0 ? np : 0u, np);
+    }
+    launch_accumulate(fp, ps, nullptr, false, s);
+    return PUPIL_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+// Path-traced radiance along rays from device memory: every path of __raygen__main with the
+// caller's ray as its first, through the wavefront stages over a path state of the call's own
+// (its own Queues, work-counter slot kWorkRadiance and ray totals).  Reads the engine's camera
+// nowhere, adds to none of the ray totals pupil_pt_stats reports and touches neither a frame's
+// accumulation nor the frames in flight of the pipelined ring.
+int pupil_pt_radiance_rays(pupil_pt *pt, uint32_t n, const void *rays_device, const uint32_t *stream_ids_device,
+                           const pupil_pt_launch *launch, const pupil_ray_radiance *out, void *hip_stream) {
+    if (!pt || !launch || !out || !out->radiance) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (launch->spp == 0) return fail(PUPIL_ERR_INVALID, "spp = 0");
+    if (n >= (1u << 31)) return fail(PUPIL_ERR_INVALID, "too many rays in one call");
+    // k_generate_rays loads a ray as two float4, k_accumulate the radiance as one; the AOVs and
+    // the ids are read and written by dwords
+    if (((uintptr_t)rays_device & 15u) || ((uintptr_t)out->radiance & 15u) || ((uintptr_t)stream_ids_device & 3u) ||
+        ((uintptr_t)out->albedo & 3u) || ((uintptr_t)out->normal & 3u))
+        return fail(PUPIL_ERR_INVALID, "misaligned pointer (rays, radiance: 16 B, the others: 4 B)");
+    if (n == 0) return PUPIL_OK;
+    if (!rays_device) return fail(PUPIL_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(pt->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const uint32_t depth = std::max(1u, launch->max_depth ? launch->max_depth : pt->max_depth);
+    // chunks of at most rad_chunk paths: `per` rays by `sb` samples (all of them unless spp alone
+    // exceeds the chunk; a later range of samples continues the running mean of the earlier ones)
+    const uint32_t sb = (uint32_t)std::min<size_t>(launch->spp, pt->rad_chunk);
+    const uint32_t per = (uint32_t)std::min<size_t>(n, pt->rad_chunk / sb);
+    if (!pt->ev_r0) {
+        HIP_TRY(hipEventCreate(&pt->ev_r0));
+        HIP_TRY(hipEventCreate(&pt->ev_r1));
+    }
+    if (const int rc = ensure_radiance_state(pt, (size_t)sb * per, s)) return rc;
+    if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
+        HIP_TRY(hipEventRecord(pt->ev_sync, pt->last_stream));
+        HIP_TRY(hipStreamWaitEvent(s, pt->ev_sync, 0));
+    }
+    HIP_TRY(hipEventRecord(pt->ev_r0, s));
+    // from here work is on s: whatever follows orders itself behind it, also when a chunk fails
+    pt->last_stream = s;
+    pt->rendered = true;
+    for (uint32_t s0 = 0; s0 < launch->spp; s0 += sb)
+        for (uint32_t r0 = 0; r0 < n; r0 += per)
+            if (const int rc = radiance_chunk(pt, s, (const float4 *)rays_device, stream_ids_device, launch, out, depth,
+                                              r0, std::min(per, n - r0), s0, std::min(sb, launch->spp - s0)))
+                return rc;
+    HIP_TRY(hipEventRecord(pt->ev_r1, s));
+    HIP_TRY(hipGetLastError());
+    pt->rad_calls++;
+    pt->rad_rays += n;
+    return PUPIL_OK;
+}
+
+// calls and rays since create, the extension and shadow rays their paths cast (device totals of
+// the call's own: reading them waits for the last call, as last_ms does), growths of the scratch
+// and the device time of the last call from the events around it; any out pointer may be NULL
+int pupil_pt_radiance_info(pupil_pt *pt, uint64_t *calls, uint64_t *rays, uint64_t *extension_rays,
+                           uint64_t *shadow_rays, uint64_t *scratch_grows, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (calls) *calls = pt->rad_calls;
+    if (rays) *rays = pt->rad_rays;
+    if (scratch_grows) *scratch_grows = pt->rad_grows;
+    if (extension_rays) *extension_rays = 0;
+    if (shadow_rays) *shadow_rays = 0;
+    if (last_ms) *last_ms = 0.0;
+    if (!pt->rad_calls || !(extension_rays || shadow_rays || last_ms)) return PUPIL_OK;
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(hipEventSynchronize(pt->ev_r1));
+    if (extension_rays || shadow_rays) {
+        std::vector<unsigned long long> cum(pupil_pt::kRadTotals + 2);
+        HIP_TRY(hipMemcpy(cum.data(), pt->rad_cum, sizeof(unsigned long long) * cum.size(), hipMemcpyDeviceToHost));
+        unsigned long long culled = 0;  // cast by the integrator and counted like a traced ray
+        for (uint32_t k = 0; k < kCullShards; k++) culled += cum[k * kCullStride];
+        if (extension_rays) *extension_rays = cum[pupil_pt::kRadTotals] + culled;
+        if (shadow_rays) *shadow_rays = cum[pupil_pt::kRadTotals + 1];
+    }
+    if (last_ms) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, pt->ev_r0, pt->ev_r1));
+        *last_ms = ms;
     }
     return PUPIL_OK;
 }

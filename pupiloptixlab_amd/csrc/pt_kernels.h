@@ -64,7 +64,10 @@ constexpr uint32_t kWorkShards = 8, kWorkStride = 32, kWorkKind = (2 * kWorkShar
 constexpr uint32_t kWorkExtend = 0, kWorkRays = 2 * kWorkKind, kWorkFrame = 3 * kWorkKind;
 constexpr uint32_t kWorkFlow = 4 * kWorkKind;  // the flow pass's traversal (pupil_pt_motion_vectors)
 constexpr uint32_t kWorkQuery = 5 * kWorkKind;  // ray queries from device memory (pupil_pt_query_rays / _query_camera)
-constexpr uint32_t kWorkSlots = 6 * kWorkKind;
+// path-traced radiance along rays (pupil_pt_radiance_rays): the work pointer of its own Queues, whose
+// launches add kWorkExtend like every other
+constexpr uint32_t kWorkRadiance = 6 * kWorkKind;
+constexpr uint32_t kWorkSlots = 7 * kWorkKind;
 constexpr uint32_t kStartBins = 16;                                    // [16..24] material bin starts
 constexpr uint32_t kStartNext = 25, kStartShadow = 26;                 // next / shadow regions of nxsh
 constexpr uint32_t kScratch = 27;
@@ -265,6 +268,22 @@ struct QueryJob {
 void launch_query_prim_slots(const float4 *recs, uint32_t slots, uint32_t num_prims, uint32_t *prim_slot,
                              hipStream_t s);
 void launch_query_resolve(const DeviceScene &sc, const QueryJob &job, hipStream_t s);
+// radiance along rays (pt_radiance.hip): the full path records (k_generate's, full = 1) of a chunk
+// of a caller's ray list -- path sample * num_local + l is sample `sample` of ray ray_base + l,
+// its origin and direction the ray's (2 float4 per ray; floats 6 and 7 are not read), its RNG
+// rng_init(id, seed0 + sample) after two discarded draws, id = stream_ids[ray_base + l] or, when
+// null, ray_base + l.  launch_identity_ids: ids[i] = i, the queue that makes launch_extend read
+// each path's origin from its state
+struct RayGenJob {
+    const float4 *rays;
+    const uint32_t *stream_ids;
+    uint32_t ray_base;
+    uint32_t num_local;  // rays of the chunk
+    uint32_t num_paths;  // num_local * samples of the chunk
+    uint32_t seed0;      // seed of the chunk's first sample
+};
+void launch_generate_rays(const RayGenJob &job, const PathState &ps, hipStream_t s);
+void launch_identity_ids(uint32_t *ids, uint32_t n, hipStream_t s);
 // the area-emitter table rebuilt in place from the engine's own arrays (pt_emitters.hip): in every
 // DevEmitter pos, nrm, area and select_probability (a sphere: center, radius, area and
 // select_probability), the selection CDF and, unless null, its guide table

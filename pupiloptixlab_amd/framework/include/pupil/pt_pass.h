@@ -80,6 +80,17 @@ public:
                    void *stream = nullptr) noexcept;
     bool QueryCamera(const pupil_ray_hits &out, float jitter_x = 0.5f, float jitter_y = 0.5f,
                      void *rays_out_device = nullptr) noexcept;
+    // Path-traced radiance along rays from device memory (pupil_pt_radiance_rays): what the n rays
+    // at rays_device see (QueryRays' layout; unit directions, tmin and tmax ignored), spp samples
+    // each, into out.radiance (float4 per ray, required) and the optional first-hit AOVs.  Sample
+    // s of ray i draws from the RNG of pixel stream_ids_device[i] (null: i) at seed + s, so a
+    // pixel's camera ray reproduces an OnRun's pixel; sample_cnt and accumulate as in OnRun,
+    // max_depth 0 = the scene's.  The pass's camera plays no part, and nothing it renders
+    // changes.  Enqueued on `stream`, ordered after every OnRun enqueued so far; the caller
+    // synchronises before reading.  False: no scene, or the engine refused (pupil_last_error()).
+    bool RadianceRays(uint32_t n, const void *rays_device, const pupil_ray_radiance &out, uint32_t spp = 1,
+                      uint32_t seed = 0, const uint32_t *stream_ids_device = nullptr, uint32_t sample_cnt = 0,
+                      bool accumulate = false, uint32_t max_depth = 0, void *stream = nullptr) noexcept;
 
 private:
     void BindingEventCallback() noexcept;

@@ -237,6 +237,23 @@ bool PTPass::QueryRays(uint32_t n, const void *rays_device, const pupil_ray_hits
     return true;
 }
 
+bool PTPass::RadianceRays(uint32_t n, const void *rays_device, const pupil_ray_radiance &out, uint32_t spp,
+                          uint32_t seed, const uint32_t *stream_ids_device, uint32_t sample_cnt, bool accumulate,
+                          uint32_t max_depth, void *stream) noexcept {
+    if (!m_engine) return false;
+    pupil_pt_launch launch{};
+    launch.random_seed = seed;
+    launch.sample_cnt = sample_cnt;
+    launch.spp = spp;
+    launch.max_depth = max_depth;
+    launch.accumulate = accumulate ? 1u : 0u;
+    if (pupil_pt_radiance_rays(m_engine, n, rays_device, stream_ids_device, &launch, &out, stream) != PUPIL_OK) {
+        Log("%s: radiance along rays failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    return true;
+}
+
 bool PTPass::QueryCamera(const pupil_ray_hits &out, float jitter_x, float jitter_y, void *rays_out_device) noexcept {
     if (!m_engine) return false;
     FrameGather *gather = util::Singleton<System>::instance()->Gather();

@@ -31,6 +31,8 @@ FINAL_RESULT = "final result"  # BufferManager::DEFAULT_FINAL_RESULT_BUFFER_NAME
 QUERY_OUTPUTS = {"hit": (4, "f"), "instance": (1, "i"), "primitive": (1, "i"), "material": (1, "i"),
                  "position": (3, "f"), "normal": (3, "f"), "texcoord": (2, "f")}
 QUERY_WANT_ALL = tuple(QUERY_OUTPUTS)
+# outputs of radiance() (the fields of pupil_ray_radiance): float32 channels
+RADIANCE_OUTPUTS = {"radiance": 4, "albedo": 3, "normal": 3}
 
 
 def camera_ray(s2c, c2w, width, height, x, y, jitter=(0.5, 0.5)):
@@ -764,6 +766,101 @@ class PTPass(Pass):
         q, r, g, ms = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_double(0.0)
         check(self._lib.pupil_pt_query_info(self._pt, C.byref(q), C.byref(r), C.byref(g), C.byref(ms)))
         return {"queries": q.value, "rays": r.value, "scratch_grows": g.value, "last_ms": ms.value}
+
+    # ---- path-traced radiance along rays from device memory (pupil_pt_radiance_rays)
+    def radiance(self, rays, spp: int = 1, seed: int = 0, sample_cnt: int = 0, accumulate: bool = False,
+                 max_depth=None, stream_ids=None, want=("radiance",), out=None, stream=None) -> dict:
+        """What the rays see (pupil_pt_radiance_rays): the render's integrator along each ray of an
+        (n, 8) contiguous float32 tensor on the pass's device, (ox, oy, oz, dx, dy, dz, tmin, tmax)
+        per ray as trace() takes them.  The direction must be unit length; tmin and tmax are
+        ignored (every segment uses the path tracer's window [0.001, 1e16]).  Returns the outputs
+        named in `want`: "radiance" (n, 4), rgb + 1, always among them; "albedo" and "normal"
+        (n, 3), the first hit's AOVs, 0 on a miss.
+
+        Sample s of ray i is a path with the RNG of pixel stream_ids[i] (default: i) at seed
+        `seed` + s, so the camera ray a render of that seed draws for that pixel gives that
+        render's pixel bit for bit.  spp samples enter "radiance" by the render's running mean
+        when `accumulate` is set (count sample_cnt + s; pass the earlier result in
+        out["radiance"] to continue it), else the last one stays.  max_depth: None = the
+        scene's.  stream_ids: (n,) int32 or uint32 tensor.  out: tensors of an earlier call to
+        write into.  Asynchronous on `stream` (default: the current stream), after every render
+        enqueued so far; nothing the pass renders changes, and its camera plays no part.  On a
+        stream other than the current one the rays, ids and outputs are recorded on it
+        (Tensor.record_stream) and the caller orders its own reads and writes of them, as for
+        trace(); outputs allocated here are written by the call alone."""
+        torch = self._torch
+        if not isinstance(rays, torch.Tensor):
+            raise ValueError("radiance needs a torch tensor of rays")
+        if rays.dtype != torch.float32:
+            raise ValueError(f"radiance needs float32 rays, got {rays.dtype}")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"radiance needs an (n, 8) tensor of rays, got {tuple(rays.shape)}")
+        if not rays.is_contiguous():
+            raise ValueError("radiance needs contiguous rays")
+        if not rays.is_cuda or rays.device.index != self.device_index:
+            raise ValueError(f"radiance needs rays on {self.device}, got a {rays.device} tensor")
+        n = int(rays.shape[0])
+        if stream_ids is not None:
+            if not (isinstance(stream_ids, torch.Tensor) and stream_ids.dtype in (torch.int32, getattr(torch, "uint32", torch.int32))
+                    and tuple(stream_ids.shape) == (n,) and stream_ids.is_contiguous() and stream_ids.is_cuda
+                    and stream_ids.device.index == self.device_index):
+                raise ValueError(f"stream_ids must be a contiguous int32 or uint32 tensor of shape ({n},) on "
+                                 f"{self.device}")
+        want = tuple(want)
+        for name in want:
+            if name not in RADIANCE_OUTPUTS:
+                raise ValueError(f"unknown radiance output {name!r} (one of {', '.join(RADIANCE_OUTPUTS)})")
+        if "radiance" not in want:
+            raise ValueError('radiance always returns "radiance": name it in want')
+        if int(spp) < 1:
+            raise ValueError("radiance needs spp >= 1")
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        tensors = {}
+        filled = False
+        arrays = abi.RayRadiance()
+        for name in want:
+            shape = (n, RADIANCE_OUTPUTS[name])
+            t = out.get(name) if out else None
+            if t is not None:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device_index
+                        and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()):
+                    raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of shape {shape} on "
+                                     f"{self.device}")
+            elif name == "radiance" and accumulate and int(sample_cnt) > 0:
+                # the one case in which the engine reads what the array holds: a mean continued
+                # without the earlier result starts from 0.  The fill runs on the current stream
+                t = torch.zeros(shape, dtype=torch.float32, device=self.device)
+                filled = True
+            else:  # written whole, as trace()'s outputs: nothing of torch's is enqueued for it
+                t = torch.empty(shape, dtype=torch.float32, device=self.device)
+            tensors[name] = t
+            setattr(arrays, name, t.data_ptr() if n else None)
+        if n == 0:
+            return tensors
+        la = abi.Launch()
+        la.random_seed = int(seed) & 0xFFFFFFFF
+        la.sample_cnt = int(sample_cnt)
+        la.spp = int(spp)
+        la.max_depth = 0 if max_depth is None else int(max_depth)
+        la.accumulate = int(bool(accumulate))
+        s = self._query_stream(stream, [rays, stream_ids, *tensors.values()])
+        if filled and s.cuda_stream != torch.cuda.current_stream(self.device_index).cuda_stream:
+            s.wait_stream(torch.cuda.current_stream(self.device_index))  # the fill above, before the call reads it
+        check(self._lib.pupil_pt_radiance_rays(self._pt, n, C.c_void_p(rays.data_ptr()),
+                                               C.c_void_p(stream_ids.data_ptr()) if stream_ids is not None else None,
+                                               C.byref(la), C.byref(arrays), C.c_void_p(s.cuda_stream)))
+        return tensors
+
+    def radiance_info(self) -> dict:
+        """Calls and rays of radiance() since the scene was set, the extension and shadow rays their
+        paths cast, growths of the engine's scratch, and the device time of the last call (waits
+        for it)."""
+        u = [C.c_uint64(0) for _ in range(5)]
+        ms = C.c_double(0.0)
+        check(self._lib.pupil_pt_radiance_info(self._pt, *[C.byref(x) for x in u], C.byref(ms)))
+        return {"calls": u[0].value, "rays": u[1].value, "extension_rays": u[2].value, "shadow_rays": u[3].value,
+                "scratch_grows": u[4].value, "last_ms": ms.value}
 
     def on_run(self):
         self.render(1)
