@@ -364,6 +364,69 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
 int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *ids,
                                      const float *to_world, const float *to_object,
                                      const uint32_t *visibility_mask);
+/* Instances moved from device memory: the update above for callers whose transforms are produced
+ * on the GPU (a rigid-body step, a particle system, a pose optimiser).  No matrix passes through
+ * the host on its way in, and in the flattened BVH and in world-mode two-level the kernel
+ * launches and stream synchronisations of one call do not depend on n.  No ABI bump: detect the
+ * symbols.
+ *
+ * pupil_pt_update_instances_device: list entry k moves instance ids_device[k] (NULL: instance k)
+ * to to_world_device[12k..12k+11], row-major 3x4.  ids must be distinct; with a repeated id it
+ * is unspecified which entry wins, but every write stays in bounds.
+ *   Ordering, caller's stream: the three arrays are read in place, after the work enqueued so far
+ *     on hip_stream (a hipStream_t, NULL = the null stream), by an event as PUPIL_VERTS_DEVICE
+ *     does; no device-wide sync.  They must stay valid and unchanged until the call returns.
+ *   Ordering, engine's stream: after every render, flow pass, ray query and radiance call enqueued
+ *     so far.  Frames in flight are dropped.  Returns once the structure is updated;
+ *     accel_refits + 1, build_ms = the call's time.
+ *   Result: the next render, query and flow pass equal those of an engine created on a world with
+ *     these transforms, bit for bit.
+ *   to_object_device NULL: the engine inverts on the device.  Each to_world is completed with the
+ *     row (0, 0, 0, 1) and inverted in double by the cofactor expansion the world uses (the same
+ *     terms in the same order, det == 0 gives all zeros, 1.0 / det, one rounding to float): bit
+ *     for bit the to_object pupil_world_get_desc produces for an affine matrix.  Otherwise n x 12
+ *     floats that must be that inverse, as for the host entry.
+ *   Two-level box margins are recomputed on the device for every moved mesh instance, in the
+ *     host's order of operations.
+ *   Visibility does not change: a hidden instance takes the new transform and stays hidden, and
+ *     pupil_pt_update_instances_masked shows it later at the new transform.
+ *   An id >= num_instances writes nothing and reads nothing out of bounds: the kernel skips it
+ *     and counts it; the call returns PUPIL_OK with a message in pupil_last_error(), and the
+ *     running total is `skipped` of pupil_pt_instances_device_info.
+ *   n == 0: PUPIL_OK, nothing enqueued.  PUPIL_ERR_INVALID, before anything is enqueued: pt or
+ *     to_world_device NULL, n > num_instances, a pointer not 4-byte aligned.
+ *   Host mirror: the call reads back 4n bytes of ids before it changes anything, and after the
+ *     kernels one contiguous staging block of the moved instances' to_world, to_object, margins
+ *     and world boxes; no other transfer depends on n.  Every later host-path call sees the move.
+ *   Emissive instances: with the device-side emitter table off (pupil_pt_enable_device_emitters),
+ *     a moved id that is emissive returns PUPIL_ERR_UNSUPPORTED before anything changes, as
+ *     PUPIL_VERTS_DEVICE does on an emissive shape; with it on, the table is rebuilt before the
+ *     call returns.
+ *   Two-level object mode (PUPIL_TL_MODE=object) rebuilds its TLAS on the host on every update:
+ *     there the call is correct and no more, it goes through the host path after the readback.
+ *
+ * pupil_pt_get_instance_transforms: the engine's host mirror of instances [first, first + n),
+ * whichever path wrote it, 12 floats each; either out pointer may be NULL.  PUPIL_ERR_INVALID:
+ * pt NULL or the range out of bounds.
+ *
+ * pupil_pt_instances_device_info: successful device calls and instances moved by them since
+ * create; the skipped ids; the kernel launches and hipStreamSynchronize / hipEventSynchronize
+ * calls of the LAST call, counted by the host code where it makes them; the host's time around
+ * it.  Any out pointer may be NULL.
+ *
+ * pupil_debug_invert3x4: the inverse above on the host, from the text the kernel compiles; no GPU
+ * is touched.  PUPIL_ERR_INVALID: a NULL argument. */
+int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *ids_device,
+                                     const void *to_world_device, const void *to_object_device, void *hip_stream);
+int pupil_pt_get_instance_transforms(pupil_pt *pt, uint32_t first, uint32_t n, float *to_world, float *to_object);
+int pupil_pt_instances_device_info(pupil_pt *pt, uint64_t *updates, uint64_t *instances, uint64_t *skipped,
+                                   uint32_t *last_launches, uint32_t *last_syncs, double *last_ms);
+int pupil_debug_invert3x4(const float m[12], float out[12]);
+/* Kernel launches and stream / event synchronisations of the last instance update, by the host
+ * entries or the device entry, counted by the host code where it makes them, up to the TLAS refit
+ * (a TLAS or BVH that is built anew adds its own, uncounted).  For tools that compare the two
+ * paths; either out pointer may be NULL. */
+int pupil_debug_update_counts(pupil_pt *pt, uint32_t *launches, uint32_t *syncs);
 /* Deformable meshes: new vertices for mesh shape `shape` (index into pupil_scene_desc.shapes),
  * the geometry-AS counterpart (OPTIX_BUILD_OPERATION_UPDATE) of the instance update above.
  * positions: 3 * num_vertices floats as at create; normals: the same count, or NULL = the

@@ -145,6 +145,13 @@ SIGNATURES = {
     "pupil_pt_update_instance": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
     "pupil_pt_update_instances": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p]),
     "pupil_pt_update_instances_masked": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p, f32p, u32p]),
+    "pupil_pt_update_instances_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    "pupil_pt_get_instance_transforms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p, f32p]),
+    "pupil_pt_instances_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64), u32p, u32p, C.POINTER(C.c_double)]),
+    "pupil_debug_invert3x4": (C.c_int, [f32p, f32p]),
+    "pupil_debug_update_counts": (C.c_int, [C.c_void_p, u32p, u32p]),
     "pupil_pt_update_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                   C.c_void_p]),
     "pupil_pt_snapshot_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32]),

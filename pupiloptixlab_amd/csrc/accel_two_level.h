@@ -43,6 +43,9 @@ struct TwoLevelAccel {
     std::vector<std::vector<std::pair<int, std::array<float, 6>>>> entries;  // per instance: TLAS entries
     std::vector<uint32_t> inst_shape;                  // shape of each instance (0xFFFFFFFF: sphere)
     std::vector<uint8_t> in_tlas;  // world mode: the instance was visible when the TLAS topology was built
+    // world mode: entries[i] is older than the instance's world copy (move_world_instances refits
+    // the TLAS and needs no entry); whatever BUILDS a TLAS recomputes the stale ones first
+    std::vector<uint8_t> entries_stale;
     // world-mode TLAS refits (GPU, one launch per level, deepest first): the TLAS node ids
     // ordered by level from the deepest (d_tlas_order) and where each level starts in it
     uint32_t *d_tlas_order = nullptr;
@@ -65,6 +68,23 @@ PT_HD int rebase_link(int link, uint32_t node_base, uint32_t prim_base) {
     return make_leaf(leaf_first(link) + prim_base, leaf_count(link));
 }
 
+// The two margin terms of an instance (accel_two_level.hip instance_margin derives them), one text
+// for the host and for the kernel that moves instances on the device (pt_instances.hip): infinity
+// norms of the 3x3 parts and of the translations, in this order of operations.
+PT_HD void instance_margin_values(const float *to_world, const float *to_object, float vmax, float *margin) {
+    auto mx = [](float a, float b) { return a < b ? b : a; };  // std::max
+    float anorm = 0.f, at = 0.f, mnorm = 0.f, mt = 0.f;
+    for (int r = 0; r < 3; r++) {
+        anorm = mx(anorm, fabsf(to_object[4 * r]) + fabsf(to_object[4 * r + 1]) + fabsf(to_object[4 * r + 2]));
+        mnorm = mx(mnorm, fabsf(to_world[4 * r]) + fabsf(to_world[4 * r + 1]) + fabsf(to_world[4 * r + 2]));
+        at = mx(at, fabsf(to_object[4 * r + 3]));
+        mt = mx(mt, fabsf(to_world[4 * r + 3]));
+    }
+    const float c = 0x1p-18f;
+    margin[0] = c * anorm;
+    margin[1] = c * (anorm * (mnorm * vmax + mt) + at);
+}
+
 // Builds the BLASes, fills the two-level fields of every instance (host copy
 // `insts`, uploaded to d_insts), their world boxes and the TLAS.
 // inst_shape[i] = shape index of instance i (ignored for spheres).  Returns 0, -1 on a HIP
@@ -78,8 +98,27 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
 // insts / d_insts) and rebuilds the TLAS.  -3: the TLAS + BLAS depth exceeds the
 // traversal stacks (kTraceStackEntries).
 // refit (world mode): keep the TLAS topology and refit its boxes instead of rebuilding.
+// launches / syncs (or null): the kernels launched and the stream synchronisations made up to the
+// refit's are added (a build's own are not counted).
 int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
-                 const std::vector<uint32_t> &changed, hipStream_t s, bool refit = false);
+                 const std::vector<uint32_t> &changed, hipStream_t s, bool refit = false, uint32_t *launches = nullptr,
+                 uint32_t *syncs = nullptr);
+// Instances moved on the device (pupil_pt_update_instances_device): acc.d_list holds `count` ids in
+// range (repeats allowed) and d_insts their new transforms and margins.
+// instance_boxes_device: their world boxes into acc.d_boxes and the device instances' wlo / whi,
+// and, box (or null), 6 floats each at box[stride * k] for list entry k.  Two launches.
+void instance_boxes_device(TwoLevelAccel &acc, DevInstance *d_insts, uint32_t count, float *box, uint32_t stride,
+                           hipStream_t s);
+// move_world_instances (world mode; insts already hold what the device computed, the boxes
+// included): world records, then the world BLAS copies with ONE launch per BLAS level of each
+// moved shape (grid.y over the list; the node arithmetic is k_world_refit's), then the TLAS refit.
+// The braided entries of `changed` are only marked stale.  Launches and synchronisations do not
+// depend on count.  A TLAS that must be built (PUPIL_TL_UPDATE=rebuild, an instance shown that
+// the topology does not hold, no level order) goes through rebuild_tlas.  launches (or null): the
+// kernels launched are added.  Returns as rebuild_tlas.
+int move_world_instances(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
+                         const std::vector<uint32_t> &changed, uint32_t count, hipStream_t s, bool refit,
+                         uint32_t *launches, uint32_t *syncs);
 // Deformed mesh: shape `shape` (its device arrays in `sh` hold the new vertices) gets its
 // object-space BLAS records rewritten in place, its BLAS boxes refitted bottom up and its
 // shading records refreshed; topology, record slots and id words stay.  vmax (or null):

@@ -143,58 +143,95 @@ __global__ __launch_bounds__(kBlock) void k_world_records(const DevInstance *ins
 // to the instance's world records (+ wrec_delta).  Records bounded exactly keep
 // the leaf test's hits; the boxes are as tight as a fresh world-space build of the
 // same topology (transforming object boxes would inflate every box it rotates).
+__device__ __forceinline__ void world_refit_node(const DevInstance &in, uint32_t j, const Bvh4Node *obj,
+                                                 const float4 *wrec, Bvh4Node *wn, float *wbox) {
+    const Bvh4Node n = obj[in.obj_nbase + j];
+    float clo[3][4], chi[3][4], nlo[3], nhi[3];
+    int link[4];
+    int nk = 0;
+    for (int a = 0; a < 3; a++) {
+        nlo[a] = __builtin_huge_valf();
+        nhi[a] = -__builtin_huge_valf();
+    }
+    for (int k = 0; k < 4; k++) {
+        const int l = n.child[k];
+        if (l == kEmptyLink) continue;
+        float bl[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
+        float bh[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
+        if (l >= 0) {
+            const int w = (int)(l - (int)in.obj_nbase + (int)in.wnode_base);
+            for (int a = 0; a < 3; a++) {
+                bl[a] = wbox[6 * (size_t)w + a];
+                bh[a] = wbox[6 * (size_t)w + 3 + a];
+            }
+            link[nk] = w;
+        } else {
+            const uint32_t first = (uint32_t)((int64_t)leaf_first(l) + in.wrec_delta), cnt = leaf_count(l);
+            for (uint32_t r = first; r < first + cnt; r++)
+                for (int v = 0; v < 3; v++) {
+                    const float4 p = wrec[kRecF4 * (size_t)r + v];
+                    bl[0] = fminf(bl[0], p.x);
+                    bl[1] = fminf(bl[1], p.y);
+                    bl[2] = fminf(bl[2], p.z);
+                    bh[0] = fmaxf(bh[0], p.x);
+                    bh[1] = fmaxf(bh[1], p.y);
+                    bh[2] = fmaxf(bh[2], p.z);
+                }
+            link[nk] = make_leaf(first, cnt);
+        }
+        for (int a = 0; a < 3; a++) {
+            clo[a][nk] = bl[a];
+            chi[a][nk] = bh[a];
+            nlo[a] = fminf(nlo[a], bl[a]);
+            nhi[a] = fmaxf(nhi[a], bh[a]);
+        }
+        nk++;
+    }
+    wn[in.wnode_base + j] = encode_bvh4(nlo, nhi, clo, chi, link, nk);
+    float *b = wbox + 6 * (size_t)(in.wnode_base + j);
+    for (int a = 0; a < 3; a++) {
+        b[a] = nlo[a];
+        b[3 + a] = nhi[a];
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_world_refit(const DevInstance *insts, const uint32_t *inst,
                                                         uint32_t lo, uint32_t hi, const Bvh4Node *obj,
                                                         const float4 *wrec, Bvh4Node *wn, float *wbox) {
     const DevInstance &in = insts[*inst];
-    for (uint32_t j = lo + blockIdx.x * blockDim.x + threadIdx.x; j < hi; j += gridDim.x * blockDim.x) {
-        const Bvh4Node n = obj[in.obj_nbase + j];
-        float clo[3][4], chi[3][4], nlo[3], nhi[3];
-        int link[4];
-        int nk = 0;
-        for (int a = 0; a < 3; a++) {
-            nlo[a] = __builtin_huge_valf();
-            nhi[a] = -__builtin_huge_valf();
-        }
-        for (int k = 0; k < 4; k++) {
-            const int l = n.child[k];
-            if (l == kEmptyLink) continue;
-            float bl[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
-            float bh[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
-            if (l >= 0) {
-                const int w = (int)(l - (int)in.obj_nbase + (int)in.wnode_base);
-                for (int a = 0; a < 3; a++) {
-                    bl[a] = wbox[6 * (size_t)w + a];
-                    bh[a] = wbox[6 * (size_t)w + 3 + a];
-                }
-                link[nk] = w;
-            } else {
-                const uint32_t first = (uint32_t)((int64_t)leaf_first(l) + in.wrec_delta), cnt = leaf_count(l);
-                for (uint32_t r = first; r < first + cnt; r++)
-                    for (int v = 0; v < 3; v++) {
-                        const float4 p = wrec[kRecF4 * (size_t)r + v];
-                        bl[0] = fminf(bl[0], p.x);
-                        bl[1] = fminf(bl[1], p.y);
-                        bl[2] = fminf(bl[2], p.z);
-                        bh[0] = fmaxf(bh[0], p.x);
-                        bh[1] = fmaxf(bh[1], p.y);
-                        bh[2] = fmaxf(bh[2], p.z);
-                    }
-                link[nk] = make_leaf(first, cnt);
-            }
-            for (int a = 0; a < 3; a++) {
-                clo[a][nk] = bl[a];
-                chi[a][nk] = bh[a];
-                nlo[a] = fminf(nlo[a], bl[a]);
-                nhi[a] = fmaxf(nhi[a], bh[a]);
-            }
-            nk++;
-        }
-        wn[in.wnode_base + j] = encode_bvh4(nlo, nhi, clo, chi, link, nk);
-        float *b = wbox + 6 * (size_t)(in.wnode_base + j);
-        for (int a = 0; a < 3; a++) {
-            b[a] = nlo[a];
-            b[3 + a] = nhi[a];
+    for (uint32_t j = lo + blockIdx.x * blockDim.x + threadIdx.x; j < hi; j += gridDim.x * blockDim.x)
+        world_refit_node(in, j, obj, wrec, wn, wbox);
+}
+
+// The same level [lo, hi) of the BLAS whose object nodes start at nbase, for every listed instance
+// of that shape in one launch: grid.y strides over the list (entries of other shapes, spheres and
+// empty meshes drop out), grid.x over the level's nodes.  A repeated id writes the same bytes twice.
+__global__ __launch_bounds__(kBlock) void k_world_refit_batch(const DevInstance *insts, const uint32_t *list,
+                                                              uint32_t count, uint32_t nbase, uint32_t lo, uint32_t hi,
+                                                              const Bvh4Node *obj, const float4 *wrec, Bvh4Node *wn,
+                                                              float *wbox) {
+    for (uint32_t e = blockIdx.y; e < count; e += gridDim.y) {
+        const DevInstance &in = insts[list[e]];
+        if (in.kind == PUPIL_SHAPE_SPHERE || in.obj_ncount == 0 || in.obj_nbase != nbase) continue;
+        for (uint32_t j = lo + blockIdx.x * blockDim.x + threadIdx.x; j < hi; j += gridDim.x * blockDim.x)
+            world_refit_node(in, j, obj, wrec, wn, wbox);
+    }
+}
+
+// The boxes k_inst_bounds left for the listed instances go into their device instances (wlo / whi,
+// which the object-mode traversal reads) and, box != null, to box[stride * k] for list entry k.
+__global__ __launch_bounds__(kBlock) void k_gather_boxes(DevInstance *insts, const uint32_t *list, uint32_t count,
+                                                         const float *boxes, float *box, uint32_t stride) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t id = list[k];
+    for (int a = 0; a < 3; a++) {
+        const float lo = boxes[6 * (size_t)id + a], hi = boxes[6 * (size_t)id + 3 + a];
+        insts[id].wlo[a] = lo;
+        insts[id].whi[a] = hi;
+        if (box) {
+            box[(size_t)stride * k + a] = lo;
+            box[(size_t)stride * k + 3 + a] = hi;
         }
     }
 }
@@ -445,25 +482,15 @@ int build_tlas_node(std::vector<uint32_t> &ids, uint32_t b, uint32_t e, const st
 // test reports.
 void instance_margin(DevInstance &d, float vmax) {
     d.vmax = vmax;
-    float anorm = 0.f, at = 0.f, mnorm = 0.f, mt = 0.f;
-    for (int r = 0; r < 3; r++) {
-        anorm = std::max(anorm, std::fabs(d.to_object[4 * r]) + std::fabs(d.to_object[4 * r + 1]) +
-                                    std::fabs(d.to_object[4 * r + 2]));
-        mnorm = std::max(mnorm, std::fabs(d.to_world[4 * r]) + std::fabs(d.to_world[4 * r + 1]) +
-                                    std::fabs(d.to_world[4 * r + 2]));
-        at = std::max(at, std::fabs(d.to_object[4 * r + 3]));
-        mt = std::max(mt, std::fabs(d.to_world[4 * r + 3]));
-    }
-    const float c = 0x1p-18f;
-    d.margin[0] = c * anorm;
-    d.margin[1] = c * (anorm * (mnorm * vmax + mt) + at);
+    instance_margin_values(d.to_world, d.to_object, vmax, d.margin);
 }
 
 // World mode: the TLAS entries of instance `id` -- its world BLAS root expanded
 // `braid` levels down (partial re-braiding, Benthin et al. 2017), each with its
 // world box decoded from the quantised parent (or the instance box at the root).
 // The copy's top nodes come first in breadth-first order, so one download covers them.
-bool world_entries(TwoLevelAccel &acc, const DevInstance &d, uint32_t id, uint32_t sphere_rec, hipStream_t s) {
+bool world_entries(TwoLevelAccel &acc, const DevInstance &d, uint32_t id, uint32_t sphere_rec, hipStream_t s,
+                   uint32_t *syncs = nullptr) {
     auto &out = acc.entries[id];
     out.clear();
     if (d.hidden) return true;  // no entry: a TLAS built now cannot reach the instance
@@ -481,6 +508,7 @@ bool world_entries(TwoLevelAccel &acc, const DevInstance &d, uint32_t id, uint32
     for (uint32_t l = 0; l < acc.braid; l++, width *= 4) levels_nodes += width;
     const uint32_t ntop = std::min(d.obj_ncount, levels_nodes);
     std::vector<Bvh4Node> top(ntop);
+    if (ntop && syncs) (*syncs)++;
     if (ntop && (hipMemcpyAsync(top.data(), acc.wnodes + d.wnode_base, sizeof(Bvh4Node) * ntop, hipMemcpyDeviceToHost,
                                 s) != hipSuccess ||
                  hipStreamSynchronize(s) != hipSuccess))
@@ -582,7 +610,7 @@ int shape_abs_max(TwoLevelAccel &acc, const TwoLevelShape &sh, float *vmax, hipS
 // refitted bottom up on the GPU, one launch per TLAS level from the deepest (r03; the
 // host refit it replaces re-encoded every node on the CPU: 26 ms at braid 6, 0.8 s at
 // braid 8).  false: no level order (no TLAS nodes, or a failed build) -- rebuild.
-bool refit_world_tlas(TwoLevelAccel &acc, hipStream_t s) {
+bool refit_world_tlas(TwoLevelAccel &acc, hipStream_t s, uint32_t *launches = nullptr) {
     if (acc.tlas_nodes == 0 || acc.tlas_level_start.size() < 2 || !acc.d_tlas_order) return false;
     for (size_t L = 0; L + 1 < acc.tlas_level_start.size(); L++) {
         const uint32_t lo = acc.tlas_level_start[L], hi = acc.tlas_level_start[L + 1];
@@ -590,13 +618,72 @@ bool refit_world_tlas(TwoLevelAccel &acc, hipStream_t s) {
         const uint32_t g = std::min(1024u, (hi - lo + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_tlas_refit, dim3(std::max(1u, g)), dim3(kBlock), 0, s, acc.d_tlas_order, lo, hi,
                            acc.wprims, acc.d_boxes, acc.wnodes, acc.d_wbox);
+        if (launches) (*launches)++;
     }
     return hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
 }
 
-int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
-                 const std::vector<uint32_t> &changed, hipStream_t s, bool refit) {
+void instance_boxes_device(TwoLevelAccel &acc, DevInstance *d_insts, uint32_t count, float *box, uint32_t stride,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(k_inst_bounds, dim3(count), dim3(kBlock), 0, s, d_insts, acc.d_list, acc.d_verts, acc.d_boxes);
+    hipLaunchKernelGGL(k_gather_boxes, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d_insts, acc.d_list,
+                       count, acc.d_boxes, box, stride);
+}
+
+int move_world_instances(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
+                         const std::vector<uint32_t> &changed, uint32_t count, hipStream_t s, bool refit,
+                         uint32_t *launches, uint32_t *syncs) {
     const uint32_t n = (uint32_t)insts.size();
+    uint32_t launched = 0;
+    const uint32_t gy = std::min(count, 65535u);
+    uint32_t slots = 1;  // most record slots of a moved shape: grid.x covers them, up to the host path's 256 blocks
+    for (uint32_t id : changed)
+        if (insts[id].kind != PUPIL_SHAPE_SPHERE) slots = std::max(slots, acc.shape_slots[acc.inst_shape[id]]);
+    const uint32_t rx = std::min(256u, (slots + kBlock - 1) / kBlock);
+    for (uint32_t first = 0; first < count; first += gy) {  // grid.y holds 65535 entries: one launch below that
+        hipLaunchKernelGGL(k_world_records, dim3(rx, std::min(gy, count - first)), dim3(kBlock), 0, s, d_insts,
+                           acc.d_list + first, acc.d_faces, acc.prims, acc.wprims);
+        launched++;
+    }
+    // the moved shapes, each once: one launch per level of its BLAS, from the deepest
+    std::vector<uint8_t> seen(acc.shape_levels.size(), 0);
+    for (uint32_t id : changed) {
+        const uint32_t shape = acc.inst_shape[id];
+        if (insts[id].kind == PUPIL_SHAPE_SPHERE || insts[id].obj_ncount == 0 || seen[shape]) continue;
+        seen[shape] = 1;
+        const std::vector<uint32_t> &ls = acc.shape_levels[shape];
+        for (size_t L = ls.size() - 1; L-- > 0;) {
+            const uint32_t lo = ls[L], hi = ls[L + 1];
+            if (hi <= lo) continue;
+            // a level narrower than a block takes one wave per instance
+            const uint32_t block = hi - lo <= 64u ? 64u : (uint32_t)kBlock;
+            const uint32_t gx = std::min(1024u, (hi - lo + block - 1) / block);
+            hipLaunchKernelGGL(k_world_refit_batch, dim3(gx, gy), dim3(block), 0, s, d_insts, acc.d_list, count,
+                               insts[id].obj_nbase, lo, hi, acc.nodes4, acc.wprims, acc.wnodes, acc.d_wbox);
+            launched++;
+        }
+    }
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (acc.entries_stale.size() != n) acc.entries_stale.assign(n, 0);
+    if (acc.in_tlas.size() != n) acc.in_tlas.assign(n, 0);
+    for (uint32_t id : changed) {
+        acc.entries_stale[id] = 1;
+        if (!insts[id].hidden && !acc.in_tlas[id]) refit = false;  // shown, but not in the topology: a build
+    }
+    if (launches) *launches += launched;
+    if (refit && refit_world_tlas(acc, s, launches)) {
+        if (syncs) (*syncs)++;
+        return 0;
+    }
+    return rebuild_tlas(acc, insts, d_insts, {}, s, false, launches, syncs);  // builds from the entries, the stale ones anew
+}
+
+int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstance *d_insts,
+                 const std::vector<uint32_t> &changed, hipStream_t s, bool refit, uint32_t *launches, uint32_t *syncs) {
+    const uint32_t n = (uint32_t)insts.size();
+    uint32_t none[2] = {0, 0};  // the counts of a caller who wants none
+    if (!launches) launches = &none[0];
+    if (!syncs) syncs = &none[1];
     std::vector<DevInstance> staged;  // device copies of the changed instances: every path below synchronises s
     if (!changed.empty()) {
         if (hipMemcpyAsync(acc.d_list, changed.data(), sizeof(uint32_t) * changed.size(), hipMemcpyHostToDevice, s) !=
@@ -604,6 +691,7 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
             return -1;
         hipLaunchKernelGGL(k_inst_bounds, dim3((uint32_t)changed.size()), dim3(kBlock), 0, s, d_insts, acc.d_list,
                            acc.d_verts, acc.d_boxes);
+        *launches += acc.wprims ? 2u : 1u;
         if (acc.wprims)  // the changed instances' world-space triangle records
             hipLaunchKernelGGL(k_world_records, dim3(256, (uint32_t)changed.size()), dim3(kBlock), 0, s, d_insts,
                                acc.d_list, acc.d_faces, acc.prims, acc.wprims);
@@ -617,12 +705,14 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
                     const uint32_t g = std::min(1024u, (hi - lo + kBlock - 1) / kBlock);
                     hipLaunchKernelGGL(k_world_refit, dim3(std::max(1u, g)), dim3(kBlock), 0, s, d_insts,
                                        acc.d_list + c, lo, hi, acc.nodes4, acc.wprims, acc.wnodes, acc.d_wbox);
+                    (*launches)++;
                 }
             }
         std::vector<float> h(6 * (size_t)n);
         if (hipMemcpyAsync(h.data(), acc.d_boxes, sizeof(float) * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return -1;
+        (*syncs)++;
         for (uint32_t id : changed) {
             for (int k = 0; k < 3; k++) {
                 insts[id].wlo[k] = h[6 * (size_t)id + k];
@@ -647,15 +737,27 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
                 sphere_rec[i] = srec;
                 srec += leaf_slots(1u);
             }
-        for (uint32_t id : changed)
-            if (!world_entries(acc, insts[id], id, sphere_rec[id], s)) return -1;
+        if (acc.entries_stale.size() != n) acc.entries_stale.assign(n, 0);
+        for (uint32_t id : changed) {
+            if (!world_entries(acc, insts[id], id, sphere_rec[id], s, syncs)) return -1;
+            acc.entries_stale[id] = 0;
+        }
         // A refit keeps the topology: hiding empties the instance's boxes (NaN records, the empty
         // instance box) and every node above them is re-encoded without it.  Showing an instance
         // that was hidden when this TLAS was BUILT needs its entries, i.e. a build.
         if (acc.in_tlas.size() != n) acc.in_tlas.assign(n, 0);
         for (uint32_t id : changed)
             if (!insts[id].hidden && !acc.in_tlas[id]) refit = false;
-        if (refit && refit_world_tlas(acc, s)) return 0;
+        if (refit && refit_world_tlas(acc, s, launches)) {
+            (*syncs)++;
+            return 0;
+        }
+        // a build reads every instance's entries: those a device update left stale come first
+        for (uint32_t i = 0; i < n; i++)
+            if (acc.entries_stale[i]) {
+                if (!world_entries(acc, insts[i], i, sphere_rec[i], s, syncs)) return -1;
+                acc.entries_stale[i] = 0;
+            }
         for (uint32_t i = 0; i < n; i++) acc.in_tlas[i] = insts[i].hidden ? 0 : 1;
         std::vector<HostBox> eb;
         std::vector<int> links;

@@ -243,6 +243,19 @@ struct pupil_pt {
     unsigned long long *rad_cum = nullptr;
     uint64_t rad_calls = 0, rad_rays = 0, rad_grows = 0;
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
+    // instances from device memory (pupil_pt_update_instances_device).  d_move_stage: kMoveHeader
+    // floats whose first word counts the skipped ids (a running total the kernel adds to), then
+    // kMoveStageFloats per list entry (pt_kernels.h MoveInstancesJob), sized for every instance on
+    // the first call; the host's copies of the id list and of the block; the totals since create
+    // and what the last call launched, synchronised and took
+    static constexpr uint32_t kMoveHeader = 8;
+    float *d_move_stage = nullptr;
+    std::vector<uint32_t> h_move_ids;
+    std::vector<uint8_t> h_move_seen;
+    std::vector<float> h_move_stage;
+    uint64_t inst_dev_updates = 0, inst_dev_moved = 0, inst_dev_skipped = 0;
+    uint32_t inst_dev_launches = 0, inst_dev_syncs = 0;
+    double inst_dev_ms = 0.0;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -1047,10 +1060,12 @@ int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(found, pt->d_cull, sizeof(found), hipMemcpyDeviceToHost, pt->own_stream));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    pt->accel.counts.launches++, pt->accel.counts.syncs++;  // pupil_pt_instances_device_info
     if (found[0] != emissive) return PUPIL_OK;  // the records do not show what the tables say: no set
     std::sort(found + 1, found + 1 + found[0]);
     HIP_TRY(hipMemcpyAsync(pt->d_cull, found, sizeof(found), hipMemcpyHostToDevice, pt->own_stream));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    pt->accel.counts.syncs++;
     sc.cull_n = pt->cull_scanned = found[0];
     return PUPIL_OK;
 }
@@ -1126,6 +1141,9 @@ int rebuild_emitters(pupil_pt *pt) {
     launch_emitter_rebuild(job, pt->own_stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    // four stages and the guide's (pt_emitters.hip), one synchronisation: pupil_pt_instances_device_info
+    pt->accel.counts.launches += job.count ? (job.guide ? 5u : 4u) : 0u;
+    pt->accel.counts.syncs++;
     pt->emit_refreshes++;
     pt->emit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return derive_cull_set(pt, false);
@@ -1247,6 +1265,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
     pt->pipe.invalidate();          // frames in flight were traced against the old geometry
+    pt->accel.counts = SceneAccel::Counts{};  // pupil_debug_update_counts
     std::vector<uint32_t> changed;
     bool emitters_moved = false;  // device-side emitter table: a transform of an emissive instance
     for (uint32_t k = 0; k < n; k++) {
@@ -1370,6 +1389,150 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
 int pupil_pt_update_instance(pupil_pt *pt, uint32_t instance, const float to_world[12], const float to_object[12]) {
     if (!pt || !to_world || !to_object) return fail(PUPIL_ERR_INVALID, "null argument");
     return pupil_pt_update_instances(pt, 1, &instance, to_world, to_object);
+}
+
+// The same update with ids and matrices in device memory (header: the contract).  The ids come
+// back first (4n bytes) so that everything that can refuse the call runs before anything changes
+// and the host knows which mirror entries follow; then one kernel writes the instance table
+// (pt_instances.hip), the structure's own kernels follow on the id list it left on the device
+// (SceneAccel::move_*), and one staging block brings the host mirror up to date.
+int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *ids_device, const void *to_world_device,
+                                     const void *to_object_device, void *hip_stream) {
+    if (!pt || !to_world_device) return fail(PUPIL_ERR_INVALID, "null argument");
+    const uint32_t ni = (uint32_t)pt->h_insts.size();
+    if (n > ni) return fail(PUPIL_ERR_INVALID, "more list entries than instances");
+    for (const void *p : {(const void *)ids_device, to_world_device, to_object_device})
+        if ((uintptr_t)p & 3u) return fail(PUPIL_ERR_INVALID, "device pointer not 4-byte aligned");
+    if (n == 0) return PUPIL_OK;
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    SceneAccel::Counts &cnt = pt->accel.counts;
+    cnt = SceneAccel::Counts{};
+    if (!pt->d_move_stage) {  // the first call: the staging block (a header line, then one line per instance)
+        if (pt->alloc(&pt->d_move_stage, pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * ni) != hipSuccess) {
+            (void)hipGetLastError();
+            pt->d_move_stage = nullptr;
+            return fail(PUPIL_ERR_OOM, "instance staging allocation failed");
+        }
+        HIP_TRY(hipMemset(pt->d_move_stage, 0, sizeof(float) * pupil_pt::kMoveHeader));  // [0]: the skipped ids, a running total
+    }
+    // after the work enqueued so far on the caller's stream; no device-wide sync
+    HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
+    HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    std::vector<uint32_t> &ids = pt->h_move_ids;  // the list as the caller gave it
+    ids.resize(n);
+    if (ids_device) {
+        HIP_TRY(hipMemcpyAsync(ids.data(), ids_device, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, pt->own_stream));
+        HIP_TRY(hipStreamSynchronize(pt->own_stream));
+        cnt.syncs++;
+    } else {
+        for (uint32_t k = 0; k < n; k++) ids[k] = k;
+    }
+    std::vector<uint32_t> changed;  // the ids in range, each once
+    std::vector<uint8_t> &seen = pt->h_move_seen;
+    seen.assign(ni, 0);
+    bool emissive = false;
+    for (uint32_t id : ids) {
+        if (id >= ni || seen[id]) continue;
+        seen[id] = 1;
+        changed.push_back(id);
+        emissive = emissive || pt->h_insts[id].emitter_offset >= 0;
+    }
+    if (emissive && !pt->dev_emit)
+        return fail(PUPIL_ERR_UNSUPPORTED,
+                    "device transforms of an emissive instance: the emitter table needs the host path");
+    HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
+    pt->pipe.invalidate();          // frames in flight were traced against the old geometry
+    MoveInstancesJob job{};
+    job.instances = pt->d_insts;
+    job.num_instances = ni;
+    job.n = n;
+    job.ids = ids_device;
+    job.to_world = (const float *)to_world_device;
+    job.to_object = (const float *)to_object_device;
+    job.margins = pt->accel.two_level ? 1u : 0u;
+    job.fallback = changed.empty() ? 0u : changed[0];
+    job.stage = pt->d_move_stage + pupil_pt::kMoveHeader;
+    job.skipped = reinterpret_cast<uint32_t *>(pt->d_move_stage);
+    if (!changed.empty())
+        if (const int rc = pt->accel.move_begin(&job.list, &job.moved)) return rc;
+    launch_move_instances(job, pt->own_stream);
+    HIP_TRY(hipGetLastError());
+    cnt.launches++;
+    if (!changed.empty()) pt->accel.move_boxes(n, job.stage + kMoveStageBox, kMoveStageFloats);
+    // the host mirror: what the device computed, in one copy
+    std::vector<float> &st = pt->h_move_stage;
+    st.resize(pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * n);
+    HIP_TRY(hipMemcpyAsync(st.data(), pt->d_move_stage, sizeof(float) * st.size(), hipMemcpyDeviceToHost, pt->own_stream));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    cnt.syncs++;
+    uint32_t skipped_total = 0;
+    std::memcpy(&skipped_total, st.data(), sizeof(skipped_total));
+    const uint64_t skipped_now = skipped_total - (uint32_t)pt->inst_dev_skipped;
+    pt->inst_dev_skipped += skipped_now;
+    const bool boxes = pt->accel.two_level && pt->accel.tl.world;
+    seen.assign(ni, 0);
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t id = ids[k];
+        if (id >= ni || seen[id]) continue;  // of a repeated id the first entry is mirrored
+        seen[id] = 1;
+        const float *e = st.data() + pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * k;
+        DevInstance &d = pt->h_insts[id];
+        std::memcpy(d.to_world, e, sizeof(d.to_world));
+        std::memcpy(d.to_object, e + 12, sizeof(d.to_object));
+        if (pt->accel.two_level) std::memcpy(d.margin, e + 24, sizeof(d.margin));
+        if (boxes) {
+            std::memcpy(d.wlo, e + kMoveStageBox, sizeof(d.wlo));
+            std::memcpy(d.whi, e + kMoveStageBox + 3, sizeof(d.whi));
+        }
+    }
+    if (!changed.empty()) {
+        pt->accel.refits++;  // as the host entry: once the tables have changed
+        if (const int rc = pt->accel.move_finish(changed, n)) return rc;
+        if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
+        if (pt->dev_emit && emissive)
+            if (const int rc = rebuild_emitters(pt)) return rc;
+    }
+    pt->inst_dev_updates++;
+    pt->inst_dev_moved += changed.size();
+    pt->inst_dev_launches = cnt.launches;
+    pt->inst_dev_syncs = cnt.syncs;
+    pt->inst_dev_ms = pt->totals.build_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (skipped_now)
+        g_last_error = std::to_string(skipped_now) + " of " + std::to_string(n) + " instance ids out of range: skipped";
+    return PUPIL_OK;
+}
+
+int pupil_pt_get_instance_transforms(pupil_pt *pt, uint32_t first, uint32_t n, float *to_world, float *to_object) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    const size_t ni = pt->h_insts.size();
+    if (first > ni || n > ni - first) return fail(PUPIL_ERR_INVALID, "instance range out of bounds");
+    for (uint32_t k = 0; k < n; k++) {
+        const DevInstance &d = pt->h_insts[first + k];
+        if (to_world) std::memcpy(to_world + 12 * (size_t)k, d.to_world, sizeof(d.to_world));
+        if (to_object) std::memcpy(to_object + 12 * (size_t)k, d.to_object, sizeof(d.to_object));
+    }
+    return PUPIL_OK;
+}
+
+int pupil_debug_update_counts(pupil_pt *pt, uint32_t *launches, uint32_t *syncs) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (launches) *launches = pt->accel.counts.launches;
+    if (syncs) *syncs = pt->accel.counts.syncs;
+    return PUPIL_OK;
+}
+
+int pupil_pt_instances_device_info(pupil_pt *pt, uint64_t *updates, uint64_t *instances, uint64_t *skipped,
+                                   uint32_t *last_launches, uint32_t *last_syncs, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (updates) *updates = pt->inst_dev_updates;
+    if (instances) *instances = pt->inst_dev_moved;
+    if (skipped) *skipped = pt->inst_dev_skipped;
+    if (last_launches) *last_launches = pt->inst_dev_launches;
+    if (last_syncs) *last_syncs = pt->inst_dev_syncs;
+    if (last_ms) *last_ms = pt->inst_dev_ms;
+    return PUPIL_OK;
 }
 
 // EmitterHelper reset after a transform change (world/world.cpp:45-54): the area

@@ -58,6 +58,22 @@ struct SceneAccel {
     // the vertices of mesh shape `shape`, shown by the instances in `changed`, were replaced;
     // rebuild: PUPIL_VERTS_REBUILD
     int update_shape(uint32_t shape, const std::vector<uint32_t> &changed, bool rebuild);
+    // Instances moved on the device (pupil_pt_update_instances_device), in three steps whose kernel
+    // launches and synchronisations do not depend on how many moved (flattened BVH, two-level world
+    // mode; object mode rebuilds its TLAS through update_instances, correct and no more).
+    // move_begin: what the transform kernel writes besides the instance table -- the id list of the
+    // structure kernels (two-level; null otherwise) and the cleared moved flags (flattened; null
+    // otherwise).  move_boxes (two-level, `count` list entries written): the instances' world
+    // boxes, also to box[stride * k] on the device.  move_finish, once insts holds what the device
+    // computed for `changed` (the ids of the list in range): the structure follows, then publish().
+    int move_begin(uint32_t **list, uint8_t **moved);
+    void move_boxes(uint32_t count, float *box, uint32_t stride);
+    int move_finish(const std::vector<uint32_t> &changed, uint32_t count);
+    // kernel launches and stream / event synchronisations of the structure's own code since the
+    // caller cleared them, counted where they are made, on the paths the device move takes
+    struct Counts {
+        uint32_t launches = 0, syncs = 0;
+    } counts;
     // the material bins of instances changed (insts / d_insts hold the new ones): the bin words of
     // the record slots follow, enqueued on the stream.  No box or link changes: not a refit
     void update_bins();
@@ -85,7 +101,8 @@ struct SceneAccel {
     uint64_t refits = 0;  // accel_refits; ticked by the entry points, not here
 
 private:
-    int update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs);
+    // flagged: d_moved already holds the flags of `changed` (move_begin + the transform kernel)
+    int update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs, bool flagged = false);
     int update_tlas(const std::vector<uint32_t> &changed);
     int flag_instances(const std::vector<uint32_t> *changed, uint32_t nodes);
     Tables t{};

@@ -131,9 +131,12 @@ int SceneAccel::publish() {
         const uint64_t tlas = std::min<uint64_t>(tl.tlas_nodes, n), cap = std::min<uint64_t>(tl.tlas_cap, n);
         launch_node_bound(sc.nodes4, tlas, node_bound, t.stream, true);
         launch_node_bound(sc.nodes4 + cap, n - cap, node_bound, t.stream, false);
+        counts.launches += (tlas ? 1u : 0u) + (n - cap ? 1u : 0u);
     } else {
         launch_node_bound(sc.nodes4, n, node_bound, t.stream, true);
+        counts.launches++;
     }
+    counts.syncs++;
     uint32_t b[3];
     HIP_TRY(hipMemcpyAsync(b, node_bound, sizeof(b), hipMemcpyDeviceToHost, t.stream));
     HIP_TRY(hipStreamSynchronize(t.stream));
@@ -161,11 +164,16 @@ int SceneAccel::flag_instances(const std::vector<uint32_t> *changed, uint32_t no
 // shape's vertices replaced (attrs: their shading records are rewritten too): one refit in
 // place, or a rebuild with the masks applied to the new tree before it replaces the old one
 // (refit = false, PUPIL_FLAT_UPDATE=rebuild, a tree without a level order).
-int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs) {
+int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs, bool flagged) {
     const BvhBuildInput bin{t.num_prims, t.d_prim_inst, t.d_insts, t.d_mats};
     if (refit && !is_rebuild(std::getenv("PUPIL_FLAT_UPDATE"))) {
-        if (const int rc = flag_instances(&changed, bvh.num_nodes4)) return rc;
+        if (!flagged)
+            if (const int rc = flag_instances(&changed, bvh.num_nodes4)) return rc;
         if (refit_bvh4(bin, bvh, d_moved, refit_box, t.stream, &ms) == 0) {
+            // refit_bvh4: the records, one launch per level, one event synchronisation
+            counts.launches += (bvh.num_records ? 1u : 0u) +
+                               (bvh.level_start.size() >= 2 ? (uint32_t)bvh.level_start.size() - 1u : 0u);
+            counts.syncs++;
             // deformed meshes: the shading records follow (publish synchronises the stream)
             if (attrs) launch_refresh_attrs(bin, bvh, d_moved, t.stream);
             return publish();
@@ -201,7 +209,8 @@ int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bo
 // regenerated: world mode refits it like the reference's IAS update, object mode rebuilds it
 // (PUPIL_TL_UPDATE=rebuild: full build in both).
 int SceneAccel::update_tlas(const std::vector<uint32_t> &changed) {
-    const int rc = rebuild_tlas(tl, *t.insts, t.d_insts, changed, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")));
+    const int rc = rebuild_tlas(tl, *t.insts, t.d_insts, changed, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")),
+                                &counts.launches, &counts.syncs);
     return rc != 0 ? builder_error(rc, true, "TLAS rebuild failed") : publish();
 }
 
@@ -209,6 +218,39 @@ int SceneAccel::update_instances(const std::vector<uint32_t> &changed) {
     if (!two_level) return update_flat(changed, true, false);
     const auto t0 = std::chrono::steady_clock::now();
     if (const int rc = update_tlas(changed)) return rc;
+    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+int SceneAccel::move_begin(uint32_t **list, uint8_t **moved) {
+    *list = nullptr, *moved = nullptr;
+    if (two_level) {
+        if (tl.world) *list = tl.d_list;
+        return PUPIL_OK;
+    }
+    if (is_rebuild(std::getenv("PUPIL_FLAT_UPDATE"))) return PUPIL_OK;  // a rebuild reads no flag
+    const size_t n = std::max<size_t>(1, t.insts->size());
+    if (!d_moved) HIP_TRY(hipMalloc((void **)&d_moved, n));
+    if (!refit_box) HIP_TRY(hipMalloc((void **)&refit_box, sizeof(float) * 6 * (size_t)std::max(1u, bvh.num_nodes4)));
+    HIP_TRY(hipMemsetAsync(d_moved, 0, n, t.stream));
+    *moved = d_moved;
+    return PUPIL_OK;
+}
+
+void SceneAccel::move_boxes(uint32_t count, float *box, uint32_t stride) {
+    if (!two_level || !tl.world || count == 0) return;
+    instance_boxes_device(tl, t.d_insts, count, box, stride, t.stream);
+    counts.launches += 2;
+}
+
+int SceneAccel::move_finish(const std::vector<uint32_t> &changed, uint32_t count) {
+    if (!two_level) return update_flat(changed, true, false, d_moved != nullptr && !is_rebuild(std::getenv("PUPIL_FLAT_UPDATE")));
+    if (!tl.world) return update_instances(changed);  // the host's TLAS build, from the mirror
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = move_world_instances(tl, *t.insts, t.d_insts, changed, count, t.stream,
+                                        !is_rebuild(std::getenv("PUPIL_TL_UPDATE")), &counts.launches, &counts.syncs);
+    if (rc != 0) return builder_error(rc, true, "TLAS rebuild failed");
+    if (const int prc = publish()) return prc;
     ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PUPIL_OK;
 }

@@ -350,6 +350,28 @@ struct EnvTablesJob {
     DevEmitter *env;
 };
 void launch_env_tables(const EnvTablesJob &job, hipStream_t s);
+// Instance transforms from device memory (pt_instances.hip): entry k of the list moves instance
+// ids[k] (null: k) to to_world[12k..], with to_object[12k..] or, null, the inverse computed on the
+// device.  An id >= num_instances is skipped and counted in *skipped, a running total.  stage:
+// kMoveStageFloats floats per entry for the host mirror -- to_world, to_object (the real one, also
+// where the device copy of a hidden sphere gets NaN), the two margins, then six floats the box
+// gather fills (two-level).  list (or null): the ids as the structure kernels take them, `fallback`
+// (an id in range that the list holds anyway) in place of a skipped one.  moved (or null): the
+// flattened refit's flags, cleared by the caller.  margins: recompute the two-level box margins.
+constexpr uint32_t kMoveStageFloats = 32;
+constexpr uint32_t kMoveStageBox = 26;
+struct MoveInstancesJob {
+    DevInstance *instances;
+    uint32_t num_instances, n;
+    const uint32_t *ids;
+    const float *to_world, *to_object;
+    uint32_t margins, fallback;
+    float *stage;
+    uint32_t *list;
+    uint8_t *moved;
+    uint32_t *skipped;
+};
+void launch_move_instances(const MoveInstancesJob &job, hipStream_t s);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

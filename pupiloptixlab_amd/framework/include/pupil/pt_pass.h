@@ -63,6 +63,15 @@ public:
     // restart accumulation at the next OnRun.  False: no scene, or the engine refused.
     bool UpdateEnvDevice(const void *rgba_device, uint32_t width, uint32_t height, void *stream) noexcept;
     bool UpdateEnvParams(float scale, const float to_world[9]) noexcept;
+    // Instances moved from device memory (pupil_pt_update_instances_device), applied now, under the
+    // same threading rule: entry k moves instance ids_device[k] (NULL: instance k) to the row-major
+    // 3x4 at to_world_device + 12k floats; to_object_device NULL = the engine inverts on the device.
+    // The arrays are read after the work enqueued so far on `stream` (a hipStream_t).  Visibility
+    // stays; an emissive instance needs SetDeviceEmitters(true).  ComputeMotionVectors after the
+    // next OnRun covers the move, which also restarts accumulation.  False: no scene, or the engine
+    // refused.
+    bool UpdateInstancesDevice(uint32_t n, const uint32_t *ids_device, const void *to_world_device,
+                               const void *to_object_device, void *stream) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in
@@ -117,6 +126,7 @@ private:
     bool m_have_cam = false;
     std::vector<float> m_to_world, m_prev_to_world;  // 12 floats per instance
     bool m_instances_moved = false;                 // by the last OnRun
+    bool m_device_moved = false;                    // UpdateInstancesDevice since the last OnRun
     std::atomic_bool m_keep_prev_verts = false;     // SetKeepPreviousVertices
     bool m_snapshots = false;                       // the engine holds vertex snapshots
     bool m_device_emitters = false;                 // SetDeviceEmitters

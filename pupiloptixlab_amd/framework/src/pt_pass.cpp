@@ -25,7 +25,8 @@ PTPass::~PTPass() noexcept {
 void PTPass::OnRun() noexcept {
     if (!m_engine) return;
     std::memcpy(m_cam[1], m_cam[0], sizeof(m_cam[0]));  // the previous OnRun's view, for ComputeMotionVectors
-    m_instances_moved = false;
+    m_instances_moved = m_device_moved;  // UpdateInstancesDevice since the last OnRun: its "before" stays
+    m_device_moved = false;
     if (m_snapshots) {  // the vertex snapshots of the OnRun before are a frame old
         pupil_pt_clear_vertex_snapshots(m_engine);
         m_snapshots = false;
@@ -78,7 +79,7 @@ void PTPass::OnRun() noexcept {
                     std::memcpy(&to[12 * k], ins.to_object, sizeof(ins.to_object));
                     emissive = emissive || ins.emitter_offset >= 0;
                 }
-                m_prev_to_world = m_to_world;
+                if (!m_instances_moved) m_prev_to_world = m_to_world;
                 for (size_t k = 0; k < moved.size(); k++)
                     if (12 * (size_t)moved[k] + 12 <= m_to_world.size())
                         std::memcpy(&m_to_world[12 * (size_t)moved[k]], &tw[12 * k], 12 * sizeof(float));
@@ -186,7 +187,7 @@ void PTPass::SetScene(world::World *world) noexcept {
     for (uint32_t i = 0; i < sd.num_instances; i++)
         std::memcpy(&m_to_world[12 * (size_t)i], sd.instances[i].to_world, 12 * sizeof(float));
     m_prev_to_world.clear();
-    m_instances_moved = false;
+    m_instances_moved = m_device_moved = false;
     m_have_cam = false;
     m_dirty = true;
     // the engine creates every instance visible: instances hidden before the scene was set
@@ -343,6 +344,22 @@ bool PTPass::UpdateEnvDevice(const void *rgba_device, uint32_t width, uint32_t h
     if (pupil_pt_update_env_device(m_engine, rgba_device, width, height, stream) != PUPIL_OK) {
         Log("%s: env map update failed: %s", name.c_str(), pupil_last_error());
         return false;
+    }
+    m_dirty = true;
+    return true;
+}
+
+bool PTPass::UpdateInstancesDevice(uint32_t n, const uint32_t *ids_device, const void *to_world_device,
+                                   const void *to_object_device, void *stream) noexcept {
+    if (!m_engine) return false;
+    if (pupil_pt_update_instances_device(m_engine, n, ids_device, to_world_device, to_object_device, stream) != PUPIL_OK) {
+        Log("%s: device instance update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    if (n && !m_to_world.empty()) {  // the flow of the next OnRun covers the move: the first "before" stays
+        if (!m_device_moved) m_prev_to_world = m_to_world;
+        m_device_moved = true;
+        pupil_pt_get_instance_transforms(m_engine, 0, (uint32_t)(m_to_world.size() / 12), m_to_world.data(), nullptr);
     }
     m_dirty = true;
     return true;

@@ -200,6 +200,65 @@ class PTPass(Pass):
             check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
         self.dirty = True
 
+    def update_instances_device(self, to_world, ids=None, to_object=None, stream=None):
+        """Instances moved from device tensors with ONE refit (pupil_pt_update_instances_device):
+        entry k of `to_world` (float32, contiguous, 12 per entry: row-major 3x4) moves instance
+        ids[k] (int32 / uint32, distinct; None: instance k).  to_object: the inverses the world
+        would compute, or None = the engine inverts on the device, bit for bit the world's.  The
+        tensors are read in place after the work enqueued so far on `stream` (default: the current
+        stream); no matrix passes through the host on its way in.  Visibility stays; an emissive
+        instance needs device_emitters on (PUPIL_ERR_UNSUPPORTED otherwise: use update_instances).
+        motion_vectors() after the next render covers the move; restarts accumulation."""
+        torch = self._torch
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        if to_world is None:
+            raise abi.PupilError(abi.ERR_INVALID, "null argument")
+        ints = (torch.int32, getattr(torch, "uint32", torch.int32))
+        for t, kinds in ((to_world, (torch.float32,)), (ids, ints), (to_object, (torch.float32,))):
+            if t is None:
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in kinds and t.is_contiguous()):
+                raise ValueError("update_instances_device needs contiguous float32 (matrices) and int32 or uint32 "
+                                 "(ids) device tensors")
+            if t.device.index != self.device_index:  # the kernels read them on the engine's GPU
+                raise ValueError(f"update_instances_device needs tensors on {self.device}, got {t.device}")
+        n = int(ids.numel()) if ids is not None else to_world.numel() // 12
+        if to_world.numel() != 12 * n or (to_object is not None and to_object.numel() != 12 * n):
+            raise ValueError(f"update_instances_device needs 12 floats per entry for {n} entries")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        check(self._lib.pupil_pt_update_instances_device(
+            self._pt, n, C.c_void_p(ids.data_ptr()) if ids is not None and n else None,
+            C.c_void_p(to_world.data_ptr()), C.c_void_p(to_object.data_ptr()) if to_object is not None else None,
+            C.c_void_p(s.cuda_stream)))
+        if self._to_world is not None and n:
+            if not self._moved:  # several updates before one render: the first one's "before" stays
+                self._prev_to_world = self._to_world.copy()
+                self._moved = True
+            self._to_world = self.instance_transforms()[0]
+        self.dirty = True
+
+    def instance_transforms(self):
+        """The engine's host mirror of every instance's (to_world, to_object), (n, 12) float32 each
+        (pupil_pt_get_instance_transforms), whichever update path wrote it."""
+        import numpy as np
+
+        n = 0 if self._to_world is None else len(self._to_world)
+        tw, to = np.zeros((n, 12), np.float32), np.zeros((n, 12), np.float32)
+        check(self._lib.pupil_pt_get_instance_transforms(self._pt, 0, n, tw.ctypes.data_as(abi.f32p),
+                                                         to.ctypes.data_as(abi.f32p)))
+        return tw, to
+
+    def instances_device_info(self) -> dict:
+        """Device instance updates since the scene was set: calls, instances moved, ids skipped as
+        out of range, and the kernel launches, synchronisations and host time of the last call."""
+        u = [C.c_uint64(0) for _ in range(3)]
+        la, sy, ms = C.c_uint32(0), C.c_uint32(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_instances_device_info(self._pt, *[C.byref(x) for x in u], C.byref(la), C.byref(sy),
+                                                       C.byref(ms)))
+        return {"updates": u[0].value, "instances": u[1].value, "skipped": u[2].value, "last_launches": la.value,
+                "last_syncs": sy.value, "last_ms": ms.value}
+
     def _keep_previous(self, shape: int):
         """The vertices `shape` has now become its "previous" vertices for motion_vectors()
         (pupil_pt_snapshot_shape_vertices), unless an update since the last render already kept
