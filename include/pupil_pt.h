@@ -71,6 +71,34 @@ extern "C" {
 #define PUPIL_EMITTER_SPHERE 2u
 #define PUPIL_EMITTER_CONST_ENV 3u
 #define PUPIL_EMITTER_ENV_MAP 4u
+/* Delta emitters (types.h:13-14 reserves Point and DistDir; the reference parses `point`,
+ * scene.cpp:194-202, and stops at AddEmitter's "TODO case Point", world/emitter.cpp:314).  They
+ * reuse pupil_emitter's fields; every field a type does not name is zero.
+ *
+ * Table order.  Delta emitters travel in pupil_scene_desc::area_emitters after every triangle and
+ * sphere emitter: point and spot lights first (the reference's EmitterGroup::points) in the order
+ * they were added, then the directional lights (EmitterGroup::directionals) -- the scan order of
+ * SelectOneEmiiter (render/emitter.h:110-135).  num_area_emitters counts them; no instance's
+ * emitter_offset range reaches them, and no ray can hit one (Eval: pdf 0).
+ *
+ * Weights and probabilities (EmitterHelper::ComputeProbability, world/emitter.cpp:321-337):
+ * weight = 1, as the env has (:300), and select_probability = weight / emitter_num (:334-335) with
+ * emitter_num = true area emitters + delta emitters + (env ? 1 : 0) (:331-332).  The areas'
+ * weight / area_weight_sum * m_areas.size() (:328) uses the true area count only, then / emitter_num
+ * (:333).  Every emissive triangle counts as one emitter: a point light beside a two-triangle lamp
+ * is picked one time in three.
+ *
+ * Sampling (EmitterSampleRecord with is_delta = true): pdf = 1, MIS weight 1 (main.cu:135), the
+ * two xi are drawn and ignored.
+ *   point:       wi = normalize(center - hit), distance = |center - hit|, radiance = color / distance^2
+ *   spot:        the point light times Mitsuba's falloff of a = acos(clamp(dot(-wi, axis), -1, 1)):
+ *                1 for a <= beam, 0 for a >= cutoff, (cutoff - a) / (cutoff - beam) between
+ *                (beam == cutoff: a hard edge)
+ *   directional: wi = -direction, distance = 1e16 (as the constant env), radiance = color */
+#define PUPIL_EMITTER_POINT 5u       /* center = position, color = intensity (per steradian) */
+#define PUPIL_EMITTER_SPOT 6u        /* + nrm[0] = unit axis, light towards the scene; pos[0][0] = cutoff
+                                      * angle, pos[0][1] = beam width (radians, 0 < beam <= cutoff <= pi) */
+#define PUPIL_EMITTER_DIRECTIONAL 7u /* nrm[0] = unit direction of travel, color = irradiance on a facing plane */
 
 #define PUPIL_SHAPE_MESH 0u
 #define PUPIL_SHAPE_SPHERE 1u
@@ -140,12 +168,12 @@ typedef struct pupil_emitter {
     float select_probability;
     float area;
     pupil_texture radiance;
-    float pos[3][3];   /* TriArea: world-space vertices */
-    float nrm[3][3];   /* TriArea: world-space vertex normals */
+    float pos[3][3];   /* TriArea: world-space vertices; Spot: pos[0][0] = cutoff, pos[0][1] = beam (radians) */
+    float nrm[3][3];   /* TriArea: world-space vertex normals; Spot / Directional: nrm[0] = axis / direction */
     float tex[3][2];   /* TriArea: vertex texcoords */
-    float center[3];   /* Sphere centre / env centre */
+    float center[3];   /* Sphere centre / env centre; Point / Spot: position */
     float radius;      /* Sphere radius */
-    float color[3];    /* ConstEnv colour */
+    float color[3];    /* ConstEnv colour; Point / Spot: intensity; Directional: irradiance */
     /* EnvMap: radiance.type == BITMAP; the CDF tables are built by the engine */
     float to_world[9]; /* EnvMap: rows of the 3x3 rotation */
     float to_local[9];
@@ -165,7 +193,8 @@ typedef struct pupil_scene_desc {
     const pupil_shape *shapes;
     const pupil_material *materials;
     const pupil_instance *instances;
-    const pupil_emitter *area_emitters; /* EmitterGroup::areas, select_probability filled */
+    const pupil_emitter *area_emitters; /* EmitterGroup::areas, then points, then directionals
+                                         * (PUPIL_EMITTER_POINT above); select_probability filled */
     const pupil_emitter *env;           /* EmitterGroup::env or NULL */
 } pupil_scene_desc;
 
@@ -482,8 +511,11 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
  * the first snapshot.  PUPIL_ERR_INVALID: pt NULL.  No ABI bump: detect the symbols. */
 int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape);
 int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
-/* replaces the area-emitter table, selection CDF and env emitter (after an emissive instance moved);
- * rewritten in place on the engine's stream when their shapes are unchanged */
+/* replaces the area-emitter table (delta lights included), selection CDF and env emitter (after an
+ * emissive instance moved, or a point, spot or directional light was moved, recoloured, added or
+ * removed); rewritten in place on the engine's stream when their shapes -- the emitter count, each
+ * entry's type, the env -- are unchanged.  PUPIL_ERR_INVALID for a table that is not in the order
+ * areas, point / spot lights, directional lights. */
 int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
 /* Engine-owned area-emitter table.  The engine holds everything the table is derived from
  * (vertices, indices, normals, to_world / to_object, each instance's emitter_offset), so with
@@ -516,7 +548,10 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene);
  * The rebuild rewrites, in place, pos / nrm / area / select_probability of every triangle
  * emitter (center / radius / area / select_probability of a sphere), the selection CDF and its
  * guide table, and nothing else: counts, guide_bits, radiance textures, texcoords and the env
- * emitter (whose select probability depends on the emitter count only) cannot change.  Every
+ * emitter (whose select probability depends on the emitter count only) cannot change.  Delta
+ * lights may be present: the ranges cover the triangle and sphere emitters in front of them, the
+ * scene's delta entries must be the engine's type for type, and the rebuild leaves a delta entry
+ * untouched but for its select_probability (1 / emitter count, as before) and its CDF entry.  Every
  * stage restates the host's operations in the host's order (pt_emitters.hip), so the result is
  * bit-identical to pupil_world_get_desc + pupil_pt_update_emitters for the same vertices and
  * transforms; to_object must be the inverse the world computes.  Precondition, as for the host
@@ -783,8 +818,17 @@ int pupil_debug_select_emitter(pupil_pt *pt, uint32_t n, const float *p, int32_t
 /* the device's area-emitter table, emitters [first, first + n): 24 floats each --
  * select_probability, area, cdf, the type word's bits, pos[3][3], nrm[3][3], 0, 0.
  * PUPIL_ERR_INVALID when the range is out of bounds.  Works with the device-side emitter mode
- * on or off. */
+ * on or off.  For a delta entry (PUPIL_EMITTER_POINT / _SPOT / _DIRECTIONAL) the nine pos floats
+ * are center, color, (cutoff, beam, 0); nrm[0] is the axis or direction; area is 0. */
 int pupil_debug_read_emitters(pupil_pt *pt, uint32_t first, uint32_t n, float *out);
+/* the device's Emitter::SampleDirect (emitter_sample_direct) of table entry `emitter`
+ * (== the table's count, delta emitters included: the env emitter) on n inputs xi of 3 floats
+ * (x, y used), from the shading point pos_nrm = (position xyz, normal xyz).  out: 8 floats per
+ * input, as pupil_debug_env mode 0 -- wi(3), pdf, distance, radiance(3).  The sample is returned
+ * as the function gives it: the integrator's gates (NoL > 0, f * pdf != 0) are not applied.
+ * PUPIL_ERR_INVALID: a NULL argument, an index beyond the env's, the env's without an env. */
+int pupil_debug_emitter_sample(pupil_pt *pt, uint32_t emitter, uint32_t n, const float *xi, const float *pos_nrm,
+                               float *out);
 /* the CDF's guide table: *bits = guide_bits, guide = its 2^bits + 1 entries.  Call with guide =
  * NULL for the count; a count of 0 means the table has none (fewer than two emitters, or
  * PUPIL_EMITTER_SELECT=binary). */
@@ -907,6 +951,26 @@ int pupil_world_add_instance(pupil_world *w, uint32_t shape, uint32_t material, 
                              uint32_t flip_normals, uint32_t flip_tex_coords, uint32_t is_emitter,
                              const pupil_texture *radiance, uint32_t *out_instance);
 int pupil_world_add_const_env(pupil_world *w, const float radiance[3]);
+/* Delta lights (PUPIL_EMITTER_POINT / _SPOT / _DIRECTIONAL above).  Both calls read only e->type
+ * and the fields that type names (center and color; for a spot nrm[0], pos[0][0], pos[0][1]; for a
+ * directional light nrm[0] and color); the world normalises the axis / direction, and
+ * pupil_world_get_desc fills weight (1) and select_probability.
+ * *out_light (may be NULL) and `light` number the delta lights in order of addition, whatever their
+ * types (lights loaded from XML come first, in file order).  In the desc's table light k is entry
+ *   A + (point and spot lights among lights 0 .. k-1)                          for a point or spot,
+ *   A + (all point and spot lights) + (directional lights among 0 .. k-1)      for a directional,
+ * with A the number of triangle and sphere emitters.
+ * pupil_world_set_delta_emitter replaces light `light`; a point may become a spot and back.
+ * PUPIL_ERR_INVALID, with the world unchanged: a NULL argument (out_light excepted); a type that is
+ * not 5, 6 or 7; a zero or non-finite axis or direction; spot angles outside
+ * 0 < beam <= cutoff <= pi (or non-finite); a light index out of range; a type change between
+ * point / spot and directional, which would move the light across that boundary of the table. */
+int pupil_world_add_delta_emitter(pupil_world *w, const pupil_emitter *e, uint32_t *out_light);
+int pupil_world_set_delta_emitter(pupil_world *w, uint32_t light, const pupil_emitter *e);
+/* light `light` as the world holds it (axis normalised, weight 1, select_probability 0: that one
+ * is the desc's to fill), for callers that change one field.  PUPIL_ERR_INVALID: a NULL argument,
+ * a light index out of range. */
+int pupil_world_get_delta_emitter(pupil_world *w, uint32_t light, pupil_emitter *out);
 /* the inverse of a row-major 3x3 by the routine pupil_world_get_desc derives an env emitter's
  * to_local from its to_world with (the 4x4 inverse in double of the matrix without translation):
  * what pupil_pt_update_env_params needs to match a freshly loaded scene bit for bit.

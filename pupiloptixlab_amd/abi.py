@@ -13,6 +13,9 @@ TEX_RGB, TEX_BITMAP, TEX_CHECKERBOARD = 0, 1, 2
 MAT_UNKNOWN, MAT_DIFFUSE, MAT_DIELECTRIC, MAT_ROUGH_DIELECTRIC = 0, 1, 2, 3
 MAT_CONDUCTOR, MAT_ROUGH_CONDUCTOR, MAT_PLASTIC, MAT_ROUGH_PLASTIC = 4, 5, 6, 7
 EMITTER_NONE, EMITTER_TRI_AREA, EMITTER_SPHERE, EMITTER_CONST_ENV, EMITTER_ENV_MAP = 0, 1, 2, 3, 4
+# delta lights: they follow the triangle and sphere emitters in SceneDesc.area_emitters, point and
+# spot first, then directional (include/pupil_pt.h, PUPIL_EMITTER_POINT)
+EMITTER_POINT, EMITTER_SPOT, EMITTER_DIRECTIONAL = 5, 6, 7
 SHAPE_MESH, SHAPE_SPHERE = 0, 1
 
 PUPIL_OK = OK = 0
@@ -197,6 +200,7 @@ SIGNATURES = {
     "pupil_image_save": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, f32p, C.c_uint32]),
     "pupil_debug_select_emitter": (C.c_int, [C.c_void_p, C.c_uint32, f32p, C.POINTER(C.c_int32)]),
     "pupil_debug_env": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, C.c_uint32, f32p]),
+    "pupil_debug_emitter_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p, f32p, f32p]),
     "pupil_debug_tex_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p]),
     "pupil_image_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f32p]),
     "pupil_world_create": (C.c_int, [C.POINTER(C.c_void_p)]),
@@ -209,6 +213,9 @@ SIGNATURES = {
     "pupil_world_add_instance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
                                            C.c_uint32, C.c_uint32, C.POINTER(Texture), u32p]),
     "pupil_world_add_const_env": (C.c_int, [C.c_void_p, f32p]),
+    "pupil_world_add_delta_emitter": (C.c_int, [C.c_void_p, C.POINTER(Emitter), u32p]),
+    "pupil_world_set_delta_emitter": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Emitter)]),
+    "pupil_world_get_delta_emitter": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Emitter)]),
     "pupil_world_set_instance_transform": (C.c_int, [C.c_void_p, C.c_uint32, f32p]),
     "pupil_world_set_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),

@@ -168,6 +168,11 @@ struct pupil_pt {
     DevEmitter *d_areas = nullptr, *d_env = nullptr;
     float *d_cdf = nullptr;
     uint32_t *d_guide = nullptr;
+    // the type of every entry of the emitter table (sc.num_areas of them): the triangle and sphere
+    // emitters [0, num_true_areas), which the instances' emitter ranges cover, then the delta lights
+    // -- point and spot, then directional -- which no primitive carries and no ray hits
+    std::vector<uint32_t> emit_types;
+    uint32_t num_true_areas = 0;
     pupil_emitter env_src{};  // the env emitter the tables were built from (same_env)
     bool env_src_valid = false;
     // The env map from device memory (pupil_pt_update_env_device / _update_env_params).  h_env: the
@@ -422,6 +427,28 @@ int convert_emitter(pupil_pt *pt, const pupil_emitter &e, DevEmitter &d) {
 // CDF and its guide table (2^bits >= emitter count buckets, at most 2^20, guide[k] = first
 // i with cdf[i] >= k / 2^bits; empty for PUPIL_EMITTER_SELECT=binary, the plain binary
 // search A/B, or fewer than two emitters).  Bitmap radiance textures are uploaded here.
+// The table's shape: each entry's type, and the number of triangle and sphere emitters in front.
+// The table must be in SelectOneEmiiter's scan order (render/emitter.h:110-135): areas, points
+// (point and spot lights), directionals.
+int emitter_table_shape(const pupil_scene_desc *scene, std::vector<uint32_t> &types, uint32_t &true_areas) {
+    types.resize(scene->num_area_emitters);
+    true_areas = 0;
+    uint32_t stage = 0;  // 0 areas, 1 points, 2 directionals
+    for (uint32_t e = 0; e < scene->num_area_emitters; e++) {
+        const uint32_t t = scene->area_emitters[e].type;
+        uint32_t s;
+        if (t == PUPIL_EMITTER_TRI_AREA || t == PUPIL_EMITTER_SPHERE) s = 0;
+        else if (t == PUPIL_EMITTER_POINT || t == PUPIL_EMITTER_SPOT) s = 1;
+        else if (t == PUPIL_EMITTER_DIRECTIONAL) s = 2;
+        else return fail(PUPIL_ERR_INVALID, "emitter table entry of an unknown or env type");
+        if (s < stage) return fail(PUPIL_ERR_INVALID, "emitter table out of order: areas, point / spot, directional");
+        stage = s;
+        true_areas += s == 0 ? 1u : 0u;
+        types[e] = t;
+    }
+    return PUPIL_OK;
+}
+
 int emitter_tables(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<DevEmitter> &areas, std::vector<float> &cdf,
                    std::vector<uint32_t> &guide, uint32_t &bits) {
     areas.assign(scene->num_area_emitters, DevEmitter{});
@@ -464,6 +491,9 @@ int upload_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     std::vector<float> cdf;
     std::vector<uint32_t> g;
     uint32_t bits = 0;
+    std::vector<uint32_t> types;
+    uint32_t true_areas = 0;
+    if (const int rc = emitter_table_shape(scene, types, true_areas)) return rc;
     if (const int rc = emitter_tables(pt, scene, areas, cdf, g, bits)) return rc;
     DevEmitter *d_areas = nullptr, *d_env = nullptr;
     float *d_cdf = nullptr;
@@ -497,6 +527,8 @@ int upload_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     pt->sc.areas = d_areas;
     pt->sc.area_cdf = d_cdf;
     pt->sc.num_areas = scene->num_area_emitters;
+    pt->emit_types.swap(types);
+    pt->num_true_areas = true_areas;
     pt->sc.has_env = d_env ? 1u : 0u;
     pt->sc.env = d_env;
     return PUPIL_OK;
@@ -877,6 +909,14 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
     std::vector<DevInstance> &insts = pt->h_insts;
     insts.resize(scene->num_instances);
     std::vector<uint32_t> prim_inst;
+    // an instance's emitter range lies within the triangle and sphere emitters: the delta lights
+    // behind them belong to no primitive
+    uint32_t true_areas = 0;
+    if (scene->area_emitters)
+        for (uint32_t e = 0; e < scene->num_area_emitters; e++) {
+            const uint32_t t = scene->area_emitters[e].type;
+            true_areas += t >= PUPIL_EMITTER_POINT && t <= PUPIL_EMITTER_DIRECTIONAL ? 0u : 1u;
+        }
     for (uint32_t i = 0; i < scene->num_instances; i++) {
         const pupil_instance &src = scene->instances[i];
         if (src.shape >= scene->num_shapes) return fail(PUPIL_ERR_INVALID, "instance shape out of range");
@@ -899,7 +939,7 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
         d.texcoords = pt->shapes[src.shape].tex;
         d.indices = pt->shapes[src.shape].idx;
         const uint32_t nprim = sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
-        if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + nprim > scene->num_area_emitters)
+        if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + nprim > true_areas)
             return fail(PUPIL_ERR_INVALID, "emitter offset out of range");
         prim_inst.insert(prim_inst.end(), nprim, i);
     }
@@ -1034,7 +1074,10 @@ int alloc_workspace(pupil_pt *pt) {
 // emitter (a terminal miss adds radiance), the traversal reads object-space records (two-level
 // object mode) or the emissive primitives number more than the cap (emissive meshes).  An
 // emitter of zero radiance stays in the set: its hit still multiplies the path's throughput by
-// that zero (inf * 0), which only the shade itself restates.
+// that zero (inf * 0), which only the shade itself restates.  The delta lights of the emitter
+// table play no part: the count below is of primitives, taken from the instances, and a point,
+// spot or directional light is none -- no ray hits it, so it adds nothing to a terminal ray's
+// shade.  A scene lit by delta lights alone therefore has no set (and traces every ray).
 int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
     DeviceScene &sc = pt->sc;
     sc.cull_set = pt->d_cull + 1;
@@ -1076,10 +1119,20 @@ int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
 // emit_inst (per emitter) and inst_weight (per instance); changes nothing of the engine.
 int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std::vector<uint32_t> &emit_inst,
                           std::vector<float> &inst_weight) {
-    const uint32_t ni = (uint32_t)pt->h_insts.size(), ne = pt->sc.num_areas;
+    // ne: the triangle and sphere emitters, which the ranges must cover; the delta lights behind
+    // them (the rebuild leaves them as they are) must be the engine's, type for type
+    const uint32_t ni = (uint32_t)pt->h_insts.size(), ne = pt->num_true_areas;
     if (scene->num_instances != ni) return fail(PUPIL_ERR_INVALID, "the scene's instance count is not the engine's");
-    if (scene->num_area_emitters != ne) return fail(PUPIL_ERR_INVALID, "the scene's area emitter count is not the engine's");
-    if ((ni && !scene->instances) || (ne && !scene->area_emitters)) return fail(PUPIL_ERR_INVALID, "missing scene array");
+    if (scene->num_area_emitters != pt->sc.num_areas)
+        return fail(PUPIL_ERR_INVALID, "the scene's area emitter count is not the engine's");
+    if ((ni && !scene->instances) || (pt->sc.num_areas && !scene->area_emitters))
+        return fail(PUPIL_ERR_INVALID, "missing scene array");
+    for (uint32_t e = 0; e < pt->sc.num_areas; e++) {
+        const uint32_t t = scene->area_emitters[e].type;
+        const bool delta = t >= PUPIL_EMITTER_POINT && t <= PUPIL_EMITTER_DIRECTIONAL;
+        if (delta != (e >= ne) || (delta && t != pt->emit_types[e]))
+            return fail(PUPIL_ERR_INVALID, "the scene's delta lights are not the engine's");
+    }
     emit_inst.assign(ne, 0u);
     inst_weight.assign(ni, 0.f);
     uint32_t next = 0;  // emitter ranges follow each other in instance order (World::Build)
@@ -1105,6 +1158,7 @@ int device_emitter_setup(pupil_pt *pt, const pupil_scene_desc *scene) {
     std::vector<uint32_t> emit_inst;
     std::vector<float> inst_weight;
     if (const int rc = device_emitter_tables(pt, scene, emit_inst, inst_weight)) return rc;
+    // sized for the whole table: the select scratch and the CDF chain span the delta lights too
     const uint32_t ne = pt->sc.num_areas;
     if (!pt->d_emit_inst || pt->dev_emit_count != ne) {
         for (void *p : {(void *)pt->d_emit_inst, (void *)pt->d_emit_weight, (void *)pt->d_emit_select}) pt->release(p);
@@ -1116,7 +1170,8 @@ int device_emitter_setup(pupil_pt *pt, const pupil_scene_desc *scene) {
     }
     if (!pt->d_inst_weight && (pt->alloc(&pt->d_inst_weight, inst_weight.size()) || pt->alloc(&pt->d_emit_sum, 1)))
         return fail(PUPIL_ERR_OOM, "emitter bookkeeping allocation failed");
-    if (ne) HIP_TRY(hipMemcpy(pt->d_emit_inst, emit_inst.data(), sizeof(uint32_t) * ne, hipMemcpyHostToDevice));
+    if (!emit_inst.empty())  // one entry per triangle or sphere emitter
+        HIP_TRY(hipMemcpy(pt->d_emit_inst, emit_inst.data(), sizeof(uint32_t) * emit_inst.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(pt->d_inst_weight, inst_weight.data(), sizeof(float) * inst_weight.size(), hipMemcpyHostToDevice));
     return PUPIL_OK;
 }
@@ -1130,7 +1185,8 @@ int rebuild_emitters(pupil_pt *pt) {
     job.cdf = pt->d_cdf;
     job.guide = pt->d_guide;
     job.guide_bits = pt->sc.guide_bits;
-    job.count = pt->sc.num_areas;
+    job.count = pt->num_true_areas;
+    job.total = pt->sc.num_areas;
     job.emitter_num = pt->sc.num_areas + (pt->sc.has_env ? 1u : 0u);
     job.instances = pt->d_insts;
     job.emit_inst = pt->d_emit_inst;
@@ -1537,7 +1593,7 @@ int pupil_pt_instances_device_info(pupil_pt *pt, uint64_t *updates, uint64_t *in
 
 // EmitterHelper reset after a transform change (world/world.cpp:45-54): the area
 // emitter table, selection CDF and env emitter are replaced by the scene's.  When the
-// tables keep their shapes (same emitter count, no bitmap radiance to upload, the same
+// tables keep their shapes (same emitter count and types, no bitmap radiance to upload, the same
 // env) they are rewritten in place on the engine's stream after the renders enqueued so
 // far; otherwise new tables are uploaded and the old ones freed.
 int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
@@ -1546,7 +1602,12 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
     pt->pipe.invalidate();
-    bool in_place = pt->d_areas && scene->num_area_emitters == pt->sc.num_areas && same_env(pt, scene);
+    // the table's shape: its counts and, entry by entry, its types (a light added, removed or turned
+    // from point to directional changes it; a light moved, recoloured or re-aimed does not)
+    std::vector<uint32_t> types;
+    uint32_t true_areas = 0;
+    if (const int rc = emitter_table_shape(scene, types, true_areas)) return rc;
+    bool in_place = pt->d_areas && types == pt->emit_types && same_env(pt, scene);
     for (uint32_t e = 0; in_place && e < scene->num_area_emitters; e++)
         in_place = scene->area_emitters[e].radiance.type != PUPIL_TEX_BITMAP;
     if (in_place) {
@@ -2627,6 +2688,11 @@ int pupil_debug_read_emitters(pupil_pt *pt, uint32_t first, uint32_t n, float *o
             o[4 + 3 * v] = d.pos[v].x, o[5 + 3 * v] = d.pos[v].y, o[6 + 3 * v] = d.pos[v].z;
             o[13 + 3 * v] = d.nrm[v].x, o[14 + 3 * v] = d.nrm[v].y, o[15 + 3 * v] = d.nrm[v].z;
         }
+        if (d.type >= PUPIL_EMITTER_POINT) {  // a delta light: center, color, (cutoff, beam, 0)
+            o[4] = d.center.x, o[5] = d.center.y, o[6] = d.center.z;
+            o[7] = d.color.x, o[8] = d.color.y, o[9] = d.color.z;
+            o[10] = d.pos[0].x, o[11] = d.pos[0].y, o[12] = 0.f;
+        }
         o[22] = o[23] = 0.f;
     }
     return PUPIL_OK;
@@ -2683,6 +2749,22 @@ int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const floa
                 return fail(PUPIL_ERR_INVALID, "xi outside [0, 1]");
     return debug_probe(pt, n, xi_or_dir, 3, out, 8, [&](const float *din, float *dout) {
         launch_debug_env(pt->sc, din, pos_nrm, mode, dout, n, pt->own_stream);
+    });
+}
+
+int pupil_debug_emitter_sample(pupil_pt *pt, uint32_t emitter, uint32_t n, const float *xi, const float *pos_nrm,
+                               float *out) {
+    if (!pt || !xi || !pos_nrm || !out) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (emitter > pt->sc.num_areas) return fail(PUPIL_ERR_INVALID, "emitter index beyond the env's");
+    const bool env = emitter == pt->sc.num_areas;
+    if (env && (!pt->sc.has_env || !pt->d_env)) return fail(PUPIL_ERR_INVALID, "the scene has no env emitter");
+    if (n == 0) return PUPIL_OK;
+    for (uint32_t i = 0; i < n; i++)  // the CDF searches take random numbers (pupil_debug_env)
+        if (!(xi[3 * i] >= 0.f && xi[3 * i] <= 1.f && xi[3 * i + 1] >= 0.f && xi[3 * i + 1] <= 1.f))
+            return fail(PUPIL_ERR_INVALID, "xi outside [0, 1]");
+    const DevEmitter *e = env ? pt->d_env : pt->d_areas + emitter;
+    return debug_probe(pt, n, xi, 3, out, 8, [&](const float *din, float *dout) {
+        launch_debug_emitter_sample(e, din, pos_nrm, dout, n, pt->own_stream);
     });
 }
 

@@ -110,7 +110,21 @@ struct SceneEmitter {
     Texture envmap;
     float scale = 1.f;
     util::Transform transform{};
+    // delta lights (PUPIL_EMITTER_POINT / _SPOT / _DIRECTIONAL): `radiance` is the intensity or
+    // irradiance, `axis` unit length, the angles in radians
+    util::Float3 position{};
+    util::Float3 axis{};
+    float cutoff = 0.f, beam = 0.f;
 };
+inline bool IsDelta(uint32_t type) { return type >= PUPIL_EMITTER_POINT && type <= PUPIL_EMITTER_DIRECTIONAL; }
+// v / |v|; false for a zero or non-finite vector
+inline bool NormalizeAxis(util::Float3 &v) {
+    const float len = std::sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
+    if (!(len > 0.f) || !std::isfinite(len)) return false;
+    v = {v.x / len, v.y / len, v.z / len};
+    return true;
+}
+constexpr float kDegToRad = 3.14159265358979323846f / 180.f;
 
 // ---- built-in shapes (shape.cpp:20-66 geometry: unit rectangle/cube)
 std::shared_ptr<Mesh> MakeRectangle() {
@@ -623,6 +637,45 @@ public:
                 sensor.transform.matrix.at(r, 2) *= -1.f;
             }
     }
+    // point (scene.cpp:194-202: `position`, `intensity`), and mitsuba's spot and directional.  A
+    // to_world gives the position as the image of the origin and the axis as the image of local
+    // +Z, normalised; a lookat has mitsuba's handedness already (LoadTransform3D) and no further
+    // flip applies (the sensor's is its own, shapes take none either).
+    bool LoadDeltaEmitter(const xml::Object *o, SceneEmitter &e) {
+        util::Transform t;
+        const xml::Object *to = o->GetUniqueSubObject("transform");
+        LoadTransform(to, t);
+        const float *m = t.matrix.e;
+        if (o->type == "directional") {
+            e.type = PUPIL_EMITTER_DIRECTIONAL;
+            LoadFloat3(o->GetProperty("irradiance"), e.radiance, {1, 1, 1});
+            e.axis = {m[2], m[6], m[10]};
+            Load3Float(o->GetProperty("direction"), e.axis, e.axis);
+        } else {
+            e.type = o->type == "spot" ? PUPIL_EMITTER_SPOT : PUPIL_EMITTER_POINT;
+            LoadFloat3(o->GetProperty("intensity"), e.radiance, {1, 1, 1});
+            e.position = {m[3], m[7], m[11]};
+            if (e.type == PUPIL_EMITTER_POINT) Load3Float(o->GetProperty("position"), e.position, e.position);
+            e.axis = {m[2], m[6], m[10]};
+        }
+        if (e.type != PUPIL_EMITTER_POINT && !NormalizeAxis(e.axis)) {
+            warn("emitter [" + o->type + "] has no direction; skipped");
+            return false;
+        }
+        if (e.type == PUPIL_EMITTER_POINT) e.axis = {};
+        if (e.type == PUPIL_EMITTER_SPOT) {
+            float cutoff_deg, beam_deg;
+            LoadFloat(o, "cutoff_angle", cutoff_deg, 20.f);
+            LoadFloat(o, "beam_width", beam_deg, cutoff_deg * 0.75f);
+            e.cutoff = cutoff_deg * kDegToRad;
+            e.beam = beam_deg * kDegToRad;
+            if (!(e.beam > 0.f && e.beam <= e.cutoff && e.cutoff <= 3.14159265358979323846f)) {
+                warn("spot emitter angles out of range (0 < beam_width <= cutoff_angle <= 180); skipped");
+                return false;
+            }
+        }
+        return true;
+    }
     bool LoadFromXML(const std::string &file, std::string &err) {
         root = std::filesystem::path(file).parent_path();
         xml::Parser parser;
@@ -672,6 +725,8 @@ public:
                     }
                     e.envmap.filter = 1;
                     LoadTransform(o->GetUniqueSubObject("transform"), e.transform);
+                } else if (o->type == "point" || o->type == "spot" || o->type == "directional") {
+                    if (!LoadDeltaEmitter(o, e)) continue;
                 } else {
                     if (o->type != "area") warn("unknown emitter type [" + o->type + "]");
                     continue;
@@ -750,6 +805,7 @@ public:
     std::vector<pupil_emitter> d_areas;
     pupil_emitter d_env{};
     bool has_env = false;
+    size_t num_true_areas = 0;  // triangle and sphere emitters: d_areas holds the delta lights after them
 
     // World::LoadScene(Scene*) + EmitterHelper + CameraHelper
     int Build(pupil_scene_desc &desc) {
@@ -825,6 +881,13 @@ public:
                 has_env = true;
             }
         }
+        // the reference's m_points, then m_directionals (SelectOneEmiiter's scan order,
+        // render/emitter.h:121-134), each in order of addition
+        num_true_areas = d_areas.size();
+        for (int pass = 0; pass < 2; pass++)
+            for (auto &e : sc.emitters)
+                if (resource::IsDelta(e.type) && (e.type == PUPIL_EMITTER_DIRECTIONAL) == (pass == 1))
+                    d_areas.push_back(DeltaEmitter(e));
         ComputeProbability();
         // camera (CameraHelper::Reset + GetCudaMemory)
         std::memset(&desc, 0, sizeof(desc));
@@ -901,14 +964,31 @@ public:
         }
     }
 
-    // EmitterHelper::ComputeProbability (emitter.cpp:321-337)
+    static pupil_emitter DeltaEmitter(const resource::SceneEmitter &s) {
+        pupil_emitter e;
+        std::memset(&e, 0, sizeof(e));
+        e.type = s.type;
+        e.weight = 1.f;  // as the env (emitter.cpp:300)
+        e.color[0] = s.radiance.x, e.color[1] = s.radiance.y, e.color[2] = s.radiance.z;
+        if (s.type != PUPIL_EMITTER_DIRECTIONAL)
+            e.center[0] = s.position.x, e.center[1] = s.position.y, e.center[2] = s.position.z;
+        if (s.type != PUPIL_EMITTER_POINT) e.nrm[0][0] = s.axis.x, e.nrm[0][1] = s.axis.y, e.nrm[0][2] = s.axis.z;
+        if (s.type == PUPIL_EMITTER_SPOT) e.pos[0][0] = s.cutoff, e.pos[0][1] = s.beam;
+        return e;
+    }
+
+    // EmitterHelper::ComputeProbability (emitter.cpp:321-337).  d_areas = m_areas (the first
+    // num_true_areas entries), then m_points, then m_directionals
     void ComputeProbability() {
+        const size_t areas = num_true_areas;
         float area_weight_sum = 0.f;
-        for (auto &e : d_areas) area_weight_sum += e.weight;
-        if (!d_areas.empty())
-            for (auto &e : d_areas) e.select_probability = e.weight / area_weight_sum * d_areas.size();
-        const size_t emitter_num = (has_env ? 1 : 0) + d_areas.size();
-        for (auto &e : d_areas) e.select_probability = e.select_probability / emitter_num;
+        for (size_t i = 0; i < areas; i++) area_weight_sum += d_areas[i].weight;
+        for (size_t i = 0; i < areas; i++)
+            d_areas[i].select_probability = d_areas[i].weight / area_weight_sum * areas;
+        const size_t emitter_num = (has_env ? 1 : 0) + d_areas.size();  // :331-332
+        for (size_t i = 0; i < areas; i++) d_areas[i].select_probability = d_areas[i].select_probability / emitter_num;
+        for (size_t i = areas; i < d_areas.size(); i++)  // :334-335
+            d_areas[i].select_probability = d_areas[i].weight / emitter_num;
         if (has_env) d_env.select_probability = d_env.weight / emitter_num;
     }
 };
@@ -1113,6 +1193,64 @@ int pupil_world_add_const_env(pupil_world *w, const float radiance[3]) {
     e.radiance = {radiance[0], radiance[1], radiance[2]};
     w->w.scene.emitters.push_back(e);
     return PUPIL_OK;
+}
+
+// validates *e and converts it (pupil_world_add_delta_emitter / _set_delta_emitter)
+static int delta_from_desc(const pupil_emitter *e, Pupil::resource::SceneEmitter &out) {
+    using Pupil::werr;
+    if (!Pupil::resource::IsDelta(e->type)) return werr(PUPIL_ERR_INVALID, "not a point, spot or directional emitter");
+    out = Pupil::resource::SceneEmitter{};
+    out.type = e->type;
+    out.radiance = {e->color[0], e->color[1], e->color[2]};
+    if (e->type != PUPIL_EMITTER_DIRECTIONAL) out.position = {e->center[0], e->center[1], e->center[2]};
+    if (e->type != PUPIL_EMITTER_POINT) {
+        out.axis = {e->nrm[0][0], e->nrm[0][1], e->nrm[0][2]};
+        if (!Pupil::resource::NormalizeAxis(out.axis)) return werr(PUPIL_ERR_INVALID, "zero or non-finite light direction");
+    }
+    if (e->type == PUPIL_EMITTER_SPOT) {
+        out.cutoff = e->pos[0][0];
+        out.beam = e->pos[0][1];
+        if (!(out.beam > 0.f && out.beam <= out.cutoff && out.cutoff <= 3.14159265358979323846f))
+            return werr(PUPIL_ERR_INVALID, "spot angles must satisfy 0 < beam <= cutoff <= pi");
+    }
+    return PUPIL_OK;
+}
+
+int pupil_world_add_delta_emitter(pupil_world *w, const pupil_emitter *e, uint32_t *out_light) {
+    if (!w || !e) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    Pupil::resource::SceneEmitter s;
+    if (const int rc = delta_from_desc(e, s)) return rc;
+    uint32_t light = 0;
+    for (const auto &x : w->w.scene.emitters) light += Pupil::resource::IsDelta(x.type) ? 1u : 0u;
+    w->w.scene.emitters.push_back(s);
+    if (out_light) *out_light = light;
+    return PUPIL_OK;
+}
+
+int pupil_world_set_delta_emitter(pupil_world *w, uint32_t light, const pupil_emitter *e) {
+    if (!w || !e) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    Pupil::resource::SceneEmitter s;
+    if (const int rc = delta_from_desc(e, s)) return rc;
+    uint32_t k = 0;  // light k = the k-th delta emitter of the scene, in order of addition
+    for (auto &x : w->w.scene.emitters) {
+        if (!Pupil::resource::IsDelta(x.type) || k++ != light) continue;
+        if ((x.type == PUPIL_EMITTER_DIRECTIONAL) != (s.type == PUPIL_EMITTER_DIRECTIONAL))
+            return Pupil::werr(PUPIL_ERR_INVALID, "a light cannot change between point / spot and directional");
+        x = s;
+        return PUPIL_OK;
+    }
+    return Pupil::werr(PUPIL_ERR_INVALID, "light out of range");
+}
+
+int pupil_world_get_delta_emitter(pupil_world *w, uint32_t light, pupil_emitter *out) {
+    if (!w || !out) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    uint32_t k = 0;
+    for (const auto &x : w->w.scene.emitters) {
+        if (!Pupil::resource::IsDelta(x.type) || k++ != light) continue;
+        *out = Pupil::world::World::DeltaEmitter(x);
+        return PUPIL_OK;
+    }
+    return Pupil::werr(PUPIL_ERR_INVALID, "light out of range");
 }
 
 int pupil_world_invert3x3(const float m[9], float out[9]) {

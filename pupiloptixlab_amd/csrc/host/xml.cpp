@@ -222,7 +222,9 @@ Tag tag_of(const std::string &n) {
         {"string", Tag::string},   {"float", Tag::float_},         {"rgb", Tag::rgb},
         {"point", Tag::point},     {"matrix", Tag::matrix},        {"scale", Tag::scale},
         {"rotate", Tag::rotate},   {"translate", Tag::translate},  {"boolean", Tag::boolean},
-        {"ref", Tag::ref}};
+        {"ref", Tag::ref},
+        // mitsuba's <vector name="direction" .../> of a directional emitter: read as a point is
+        {"vector", Tag::point}};
     auto it = m.find(n);
     return it == m.end() ? Tag::unknown : it->second;
 }

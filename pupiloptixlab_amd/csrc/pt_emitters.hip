@@ -15,6 +15,10 @@
 // Stages 2 and 4 are one wave: its 64 lanes stage kChainChunk values in the LDS with coalesced
 // loads (and, for the CDF, store the chunk's results the same way), lane 0 reads them back four
 // per LDS load and adds.  Nothing else of a DevEmitter is written (type, radiance, tex, the env).
+// The delta lights (point, spot, directional) follow the area emitters in the table and have no
+// geometry to rebuild: stages 1 and 2 run over the area emitters alone (`count` in stage 3 is the
+// true area count), stage 3 rewrites a delta light's select_probability = 1 / emitter_num and
+// stages 4 and 5 span the whole table, as the host's CDF does.
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
@@ -127,9 +131,14 @@ __global__ __launch_bounds__(64) void k_emit_chain(const float *in, uint32_t n, 
 // size_t values are)
 __global__ __launch_bounds__(kEmitBlock) void k_emit_select(EmitterJob job) {
     const uint32_t e = blockIdx.x * kEmitBlock + threadIdx.x;
-    if (e >= job.count) return;
-    float p = job.weight[e] / job.sum[0] * (float)job.count;
-    p = p / (float)job.emitter_num;
+    if (e >= job.total) return;
+    float p;
+    if (e < job.count) {
+        p = job.weight[e] / job.sum[0] * (float)job.count;
+        p = p / (float)job.emitter_num;
+    } else {
+        p = 1.f / (float)job.emitter_num;  // a delta light: weight 1 (emitter.cpp:334-335)
+    }
     job.areas[e].select_probability = p;
     job.select[e] = p;
 }
@@ -140,7 +149,7 @@ __global__ __launch_bounds__(kEmitBlock) void k_emit_guide(EmitterJob job) {
     const uint32_t m = 1u << job.guide_bits;
     if (k > m) return;
     const float t = (float)k / (float)m;
-    uint32_t lo = 0, hi = job.count;  // first i in [0, count] with cdf[i] >= t (count = none)
+    uint32_t lo = 0, hi = job.total;  // first i in [0, total] with cdf[i] >= t (total = none)
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2u;
         if (job.cdf[mid] < t) lo = mid + 1u;
@@ -168,10 +177,11 @@ __global__ __launch_bounds__(kEmitBlock) void k_cull_scan(const float4 *recs, ui
 void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s) {
     if (job.count == 0) return;
     const dim3 grid((job.count + kEmitBlock - 1) / kEmitBlock);
+    const dim3 grid_all((job.total + kEmitBlock - 1) / kEmitBlock);
     hipLaunchKernelGGL(k_emit_geometry, grid, dim3(kEmitBlock), 0, s, job);
     hipLaunchKernelGGL(k_emit_chain<false>, dim3(1), dim3(64), 0, s, (const float *)job.weight, job.count, job.sum);
-    hipLaunchKernelGGL(k_emit_select, grid, dim3(kEmitBlock), 0, s, job);
-    hipLaunchKernelGGL(k_emit_chain<true>, dim3(1), dim3(64), 0, s, (const float *)job.select, job.count, job.cdf);
+    hipLaunchKernelGGL(k_emit_select, grid_all, dim3(kEmitBlock), 0, s, job);
+    hipLaunchKernelGGL(k_emit_chain<true>, dim3(1), dim3(64), 0, s, (const float *)job.select, job.total, job.cdf);
     if (job.guide) {
         const uint32_t entries = (1u << job.guide_bits) + 1u;
         hipLaunchKernelGGL(k_emit_guide, dim3((entries + kEmitBlock - 1) / kEmitBlock), dim3(kEmitBlock), 0, s, job);

@@ -292,12 +292,13 @@ struct EmitterJob {
     float *cdf;
     uint32_t *guide;       // null = the table has none
     uint32_t guide_bits;
-    uint32_t count;        // area emitters
-    uint32_t emitter_num;  // + 1 with an env emitter
+    uint32_t count;        // triangle and sphere emitters: table entries [0, count)
+    uint32_t total;        // + the delta lights, entries [count, total): cdf, select and the guide span these
+    uint32_t emitter_num;  // total + 1 with an env emitter
     const DevInstance *instances;
     const uint32_t *emit_inst;  // per emitter: its instance
     const float *inst_weight;   // per instance: GetWeight of its radiance (0 where not emissive)
-    float *weight, *select;     // scratch, one float per emitter
+    float *weight, *select;     // scratch, one float per table entry
     float *sum;                 // scratch, one float
 };
 void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s);
@@ -379,6 +380,10 @@ void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32
 // direction) on n device inputs of 3 floats; pos_nrm: 6 host floats; out: 8 floats per input
 void launch_debug_env(const DeviceScene &sc, const float *in, const float *pos_nrm, uint32_t mode, float *out, uint32_t n,
                       hipStream_t s);
+// emitter_sample_direct of the device emitter *e with xi = in.xy on n device inputs of 3 floats;
+// pos_nrm: 6 host floats; out: 8 floats per input (wi, pdf, distance, radiance)
+void launch_debug_emitter_sample(const DevEmitter *e, const float *in, const float *pos_nrm, float *out, uint32_t n,
+                                 hipStream_t s);
 // tex_sample of materials[material].tex[slot] on n device uv pairs; out: 3 floats per input
 void launch_debug_tex(const DeviceScene &sc, uint32_t material, uint32_t slot, const float *uv, float *out, uint32_t n,
                       hipStream_t s);

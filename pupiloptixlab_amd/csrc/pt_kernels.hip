@@ -242,6 +242,28 @@ __global__ void k_debug_env(DeviceScene sc, const float *in, vec3 pos, vec3 nrm,
     }
 }
 
+// emitter_sample_direct of *e from (pos, nrm) with xi = in.xy.  One thread per input.
+__global__ void k_debug_emitter_sample(const DevEmitter *e, const float *in, vec3 pos, vec3 nrm, float *out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    LocalGeo g;
+    g.position = pos;
+    g.normal = nrm;
+    g.texcoord = v2(0.f, 0.f);
+    const EmitterSample r = emitter_sample_direct(*e, g, v2(in[3 * i], in[3 * i + 1]));
+    float *o = out + 8 * (size_t)i;
+    o[0] = r.wi.x, o[1] = r.wi.y, o[2] = r.wi.z;
+    o[3] = r.pdf;
+    o[4] = r.distance;
+    o[5] = r.radiance.x, o[6] = r.radiance.y, o[7] = r.radiance.z;
+}
+
+void launch_debug_emitter_sample(const DevEmitter *e, const float *in, const float *pos_nrm, float *out, uint32_t n,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL(k_debug_emitter_sample, dim3((n + 255) / 256), dim3(256), 0, s, e, in,
+                       v3(pos_nrm[0], pos_nrm[1], pos_nrm[2]), v3(pos_nrm[3], pos_nrm[4], pos_nrm[5]), out, n);
+}
+
 __global__ void k_debug_tex(const DevMaterial *mat, uint32_t slot, const float *uv, float *out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -330,7 +330,7 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
             if (!is_zero(er.f * es.pdf)) {
                 const float NoL = dot(geo.normal, es.wi);
                 if (NoL > 0.f) {
-                    const float mis = mis_weight(es.pdf, er.pdf);
+                    const float mis = es.is_delta ? 1.f : mis_weight(es.pdf, er.pdf);  // main.cu:135
                     const float pdf_l = es.pdf * sel_prob;
                     const vec3 C = T * es.radiance * er.f * NoL * mis / pdf_l;
                     sh_tmax = es.distance - 0.001f;

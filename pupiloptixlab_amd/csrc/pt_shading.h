@@ -570,12 +570,14 @@ struct LocalGeo {
 };
 
 // EmitterSampleRecord (render/emitter/types.h:17-26); is_delta is never set
-// for area / sphere emitters in the reference (uninitialised) -> false here.
+// for area / sphere emitters in the reference (uninitialised) -> false here, and true
+// for the point, spot and directional lights.
 struct EmitterSample {
     vec3 radiance;
     vec3 wi;
     float distance;
     float pdf;
+    bool is_delta;
 };
 
 PT_D vec3 emitter_radiance(const DevEmitter &e, vec2 tex) {  // Emitter::GetRadiance (emitter.h:54-71)
@@ -586,12 +588,38 @@ PT_D vec3 emitter_radiance(const DevEmitter &e, vec2 tex) {  // Emitter::GetRadi
 PT_D void env_map_eval(const DevEmitter &e, vec3 dir_world, vec3 &radiance, float &pdf);
 
 // Emitter::SampleDirect (emitter.h:73-88, emitter/{area,sphere,env}.h)
+// The delta lights (pupil_pt.h, PUPIL_EMITTER_POINT): pdf 1, xi unused.  A spot is the point
+// light times mitsuba's falloff of the angle between -wi and the axis (pos[0] = cutoff, beam).
+PT_D void emitter_sample_delta(const DevEmitter &e, const LocalGeo &hit, EmitterSample &s) {
+    s.is_delta = true;
+    s.pdf = 1.f;
+    if (e.type == PUPIL_EMITTER_DIRECTIONAL) {
+        s.wi = -e.nrm[0];
+        s.distance = kMaxDistance;
+        s.radiance = e.color;
+        return;
+    }
+    const vec3 d = e.center - hit.position;
+    s.wi = normalize(d);
+    s.distance = length(d);
+    s.radiance = e.color / (s.distance * s.distance);
+    if (e.type == PUPIL_EMITTER_SPOT) {
+        const float cutoff = e.pos[0].x, beam = e.pos[0].y;
+        const float a = dm_acos(fminf(fmaxf(dot(-s.wi, e.nrm[0]), -1.f), 1.f));
+        float falloff = 1.f;
+        if (a >= cutoff) falloff = 0.f;
+        else if (a > beam) falloff = (cutoff - a) / (cutoff - beam);
+        s.radiance = s.radiance * falloff;
+    }
+}
+
 PT_D EmitterSample emitter_sample_direct(const DevEmitter &e, const LocalGeo &hit, vec2 xi) {
     EmitterSample s;
     s.pdf = 0.f;
     s.distance = 0.f;
     s.radiance = v3(0.f);
     s.wi = v3(0.f, 0.f, 1.f);
+    s.is_delta = false;
     if (e.type == PUPIL_EMITTER_TRI_AREA) {  // area.h:17-34
         const vec3 t = uniform_sample_triangle(xi.x, xi.y);
         const vec3 position = e.pos[0] * t.x + e.pos[1] * t.y + e.pos[2] * t.z;
@@ -647,6 +675,13 @@ PT_D EmitterSample emitter_sample_direct(const DevEmitter &e, const LocalGeo &hi
         s.radiance = tex_sample(e.radiance, tex) * e.scale;
         s.pdf = luminance(s.radiance) * e.row_weight[row] * e.normalization / fmaxf(1e-4f, fabs_(st));
         if (s.pdf < 0.f) s.pdf = 0.f;
+    } else if (e.type >= PUPIL_EMITTER_POINT) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // keeps the light's loads inside the branch: hoisted above the type test they stay live
+        // through the other branches, and the diffuse shade kernels (at their VGPR cap) spill
+        asm volatile("" ::: "memory");
+#endif
+        emitter_sample_delta(e, hit, s);
     }
     return s;
 }

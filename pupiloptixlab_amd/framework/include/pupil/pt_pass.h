@@ -52,6 +52,11 @@ public:
     // on `stream`.  Both restart accumulation at the next OnRun, as an instance update does.
     // False: no scene, or the engine refused (the log has pupil_last_error).
     bool UpdateMaterials(const std::vector<uint32_t> &ids) noexcept;
+    // Point, spot and directional lights added or changed on the scene's world (World::AddPointLight,
+    // SetLight, ...): hands Desc()'s emitter table to the engine (pupil_pt_update_emitters; in place
+    // when no light was added or changed its type), under the same threading rule.  Restarts
+    // accumulation at the next OnRun.  False: no scene, or the engine refused.
+    bool UpdateLights() noexcept;
     bool UpdateTextureDevice(uint32_t material, uint32_t slot, const void *rgba_device, uint32_t width, uint32_t height,
                              hipStream_t stream) noexcept;
     // The env map in place (pupil_pt_update_env_device / _update_env_params), applied now, under the

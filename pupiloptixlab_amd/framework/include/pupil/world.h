@@ -84,6 +84,18 @@ public:
     // order) and refreshes Desc().  The reference has no event for a material edit and fires
     // none: PTPass::UpdateMaterials hands the material to the engine.
     bool SetMaterial(uint32_t material, const pupil_material &m) noexcept;
+    // Delta lights (pupil_world_add_delta_emitter / _set_delta_emitter; PUPIL_EMITTER_POINT in
+    // pupil_pt.h has the table order, the selection rule and the sampling).  The adders return the
+    // light's number (lights count in order of addition, those of the XML file first) or -1;
+    // directions need not be unit length, angles are in degrees (beam_deg < 0: 3/4 of the
+    // cutoff, mitsuba's default).  SetLight replaces light `light` by *e as the C entry reads it
+    // (angles in radians).  All refresh Desc() and fire no event: PTPass::UpdateLights hands the
+    // table to the engine.
+    int AddPointLight(const float position[3], const float intensity[3]) noexcept;
+    int AddSpotLight(const float position[3], const float direction[3], const float intensity[3],
+                     float cutoff_deg = 20.f, float beam_deg = -1.f) noexcept;
+    int AddDirectionalLight(const float direction[3], const float irradiance[3]) noexcept;
+    bool SetLight(uint32_t light, const pupil_emitter &e) noexcept;
 
     pupil_world *handle() noexcept { return m_world; }
     // Flattened scene for pupil_pt_create (valid until the world changes); a thread
@@ -92,6 +104,7 @@ public:
     std::mutex &Mutex() noexcept { return m_mutex; }
 
 private:
+    int AddLight(const pupil_emitter &e) noexcept;
     pupil_world *m_world = nullptr;
     pupil_scene_desc m_desc{};
     std::mutex m_mutex;

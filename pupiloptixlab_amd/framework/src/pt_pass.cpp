@@ -306,6 +306,17 @@ bool PTPass::SetDeviceEmitters(bool on) noexcept {
     return true;
 }
 
+bool PTPass::UpdateLights() noexcept {
+    if (!m_engine || !m_world) return false;
+    std::scoped_lock lock(m_world->Mutex());
+    if (pupil_pt_update_emitters(m_engine, &m_world->Desc()) != PUPIL_OK) {
+        Log("%s: light update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    m_dirty = true;
+    return true;
+}
+
 bool PTPass::UpdateMaterials(const std::vector<uint32_t> &ids) noexcept {
     if (!m_engine || !m_world) return false;
     if (ids.empty()) return true;

@@ -122,6 +122,62 @@ bool World::SetMaterial(uint32_t material, const pupil_material &m) noexcept {
     return true;
 }
 
+namespace {
+pupil_emitter DeltaLight(uint32_t type, const float *position, const float *direction, const float color[3]) {
+    pupil_emitter e;
+    std::memset(&e, 0, sizeof(e));
+    e.type = type;
+    for (int k = 0; k < 3; k++) {
+        e.color[k] = color[k];
+        if (position) e.center[k] = position[k];
+        if (direction) e.nrm[0][k] = direction[k];
+    }
+    return e;
+}
+}  // namespace
+
+int World::AddLight(const pupil_emitter &e) noexcept {
+    std::scoped_lock lock(m_mutex);
+    uint32_t light = 0;
+    if (!m_world || pupil_world_add_delta_emitter(m_world, &e, &light) != PUPIL_OK) {
+        Log("light not added: %s", pupil_last_error());
+        return -1;
+    }
+    // a world without a shape yet has no desc: Finalize() fills it once there is one
+    (void)pupil_world_get_desc(m_world, &m_desc);
+    return (int)light;
+}
+
+int World::AddPointLight(const float position[3], const float intensity[3]) noexcept {
+    return AddLight(DeltaLight(PUPIL_EMITTER_POINT, position, nullptr, intensity));
+}
+
+int World::AddSpotLight(const float position[3], const float direction[3], const float intensity[3], float cutoff_deg,
+                        float beam_deg) noexcept {
+    pupil_emitter e = DeltaLight(PUPIL_EMITTER_SPOT, position, direction, intensity);
+    const float deg = 3.14159265358979323846f / 180.f;
+    e.pos[0][0] = cutoff_deg * deg;
+    e.pos[0][1] = (beam_deg < 0.f ? cutoff_deg * 0.75f : beam_deg) * deg;
+    return AddLight(e);
+}
+
+int World::AddDirectionalLight(const float direction[3], const float irradiance[3]) noexcept {
+    return AddLight(DeltaLight(PUPIL_EMITTER_DIRECTIONAL, nullptr, direction, irradiance));
+}
+
+bool World::SetLight(uint32_t light, const pupil_emitter &e) noexcept {
+    std::scoped_lock lock(m_mutex);
+    if (!m_world || pupil_world_set_delta_emitter(m_world, light, &e) != PUPIL_OK) {
+        Log("light update failed: %s", pupil_last_error());
+        return false;
+    }
+    if (pupil_world_get_desc(m_world, &m_desc) != PUPIL_OK) {
+        Log("scene description failed: %s", pupil_last_error());
+        return false;
+    }
+    return true;
+}
+
 // the caller holds Mutex() where another thread may edit the world
 uint32_t World::InstanceVisibility(uint32_t instance) noexcept {
     uint32_t mask = 1u;

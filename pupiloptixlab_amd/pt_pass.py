@@ -487,6 +487,40 @@ class PTPass(Pass):
         check(self._lib.pupil_pt_refresh_emitters(self._pt))
         self.dirty = True
 
+    def update_lights(self, world=None):
+        """Point, spot and directional lights added or changed on `world` (default: the World the
+        scene came from) since the engine last saw its emitter table: World.add_*_light,
+        World.set_light.  Hands the whole table to the engine (pupil_pt_update_emitters), which
+        rewrites it in place when no light was added and none changed its type; restarts
+        accumulation."""
+        world = world if world is not None else self._world
+        if world is None:
+            raise abi.PupilError(abi.ERR_INVALID, "update_lights needs a scene set from a World")
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        desc = world.desc()
+        check(self._lib.pupil_pt_update_emitters(self._pt, C.byref(desc)))
+        self.dirty = True
+
+    def emitter_sample(self, emitter: int, xi, position, normal):
+        """The device's Emitter::SampleDirect of table entry `emitter` (the table's count: the env)
+        from one shading point (pupil_debug_emitter_sample): xi (n, 2) in [0, 1].  Returns wi
+        (n, 3), pdf (n,), distance (n,), radiance (n, 3)."""
+        import numpy as np
+
+        xi = np.asarray(xi, np.float32).reshape(-1, 2)
+        n = xi.shape[0]
+        inp = np.zeros((max(1, n), 3), np.float32)
+        inp[:n, :2] = xi
+        pn = np.ascontiguousarray(np.concatenate([np.asarray(position, np.float32).reshape(3),
+                                                  np.asarray(normal, np.float32).reshape(3)]))
+        out = np.zeros((max(1, n), 8), np.float32)
+        check(self._lib.pupil_debug_emitter_sample(self._pt, int(emitter), n, inp.ctypes.data_as(abi.f32p),
+                                                   pn.ctypes.data_as(abi.f32p), out.ctypes.data_as(abi.f32p)))
+        out = out[:n]
+        return {"wi": out[:, 0:3].copy(), "pdf": out[:, 3].copy(), "distance": out[:, 4].copy(),
+                "radiance": out[:, 5:8].copy()}
+
     def device_emitters_info(self) -> dict:
         en, n, ms = C.c_uint32(0), C.c_uint64(0), C.c_double(0.0)
         check(self._lib.pupil_pt_device_emitters_info(self._pt, C.byref(en), C.byref(n), C.byref(ms)))
@@ -495,7 +529,9 @@ class PTPass(Pass):
     def emitter_table(self):
         """The engine's area-emitter table as numpy arrays (pupil_debug_read_emitters /
         _read_emitter_guide): select_probability, area, cdf (n,), type (n,) uint32, pos and nrm
-        (n, 3, 3), guide_bits, and guide ((2^bits + 1,) uint32, or None when the table has none)."""
+        (n, 3, 3), guide_bits, and guide ((2^bits + 1,) uint32, or None when the table has none).
+        The delta lights follow the area emitters; for one of them pos is (center, color,
+        (cutoff, beam, 0)), nrm[0] the axis or direction and area 0."""
         import numpy as np
 
         cnt = C.c_uint32(0)

@@ -28,6 +28,16 @@ def _ptr(arr, ctype=C.c_float):
     return arr.ctypes.data_as(C.POINTER(ctype)) if arr is not None else None
 
 
+def _rgb3(v):
+    v = np.atleast_1d(np.asarray(v, dtype=np.float32))
+    return np.repeat(v, 3) if v.size == 1 else v
+
+
+def _radians(deg) -> float:
+    """Degrees to radians in float32, as the XML loader converts cutoff_angle and beam_width."""
+    return float(np.float32(deg) * (np.float32(np.pi) / np.float32(180.0)))
+
+
 def identity4():
     return np.eye(4, dtype=np.float32)
 
@@ -255,6 +265,80 @@ class World:
     def add_const_env(self, radiance):
         r = _f32(radiance, 3)
         check(self._lib.pupil_world_add_const_env(self._h, _ptr(r)))
+
+    # ---- delta lights (PUPIL_EMITTER_POINT / _SPOT / _DIRECTIONAL in include/pupil_pt.h)
+    def _add_light(self, e: abi.Emitter) -> int:
+        out = C.c_uint32()
+        check(self._lib.pupil_world_add_delta_emitter(self._h, C.byref(e), C.byref(out)))
+        self._desc = None
+        return out.value
+
+    def add_point_light(self, position, intensity) -> int:
+        """A point light of `intensity` (rgb, per steradian) at `position`.  Returns the light's
+        number for set_light(): lights count in order of addition, whatever their types."""
+        e = abi.Emitter()
+        e.type = abi.EMITTER_POINT
+        e.center[:] = tuple(_f32(position, 3))
+        e.color[:] = tuple(_f32(_rgb3(intensity), 3))
+        return self._add_light(e)
+
+    def add_spot_light(self, position, direction, intensity, cutoff_deg=20.0, beam_deg=None) -> int:
+        """A spot light shining along `direction` (normalised by the world): the point light times
+        mitsuba's falloff -- full inside beam_deg (default 3/4 of the cutoff) off the axis, zero
+        beyond cutoff_deg, linear in the angle between."""
+        e = abi.Emitter()
+        e.type = abi.EMITTER_SPOT
+        e.center[:] = tuple(_f32(position, 3))
+        e.nrm[0][:] = tuple(_f32(direction, 3))
+        e.color[:] = tuple(_f32(_rgb3(intensity), 3))
+        e.pos[0][0] = _radians(cutoff_deg)
+        e.pos[0][1] = _radians(0.75 * cutoff_deg if beam_deg is None else beam_deg)
+        return self._add_light(e)
+
+    def add_directional_light(self, direction, irradiance) -> int:
+        """A directional light travelling along `direction`, `irradiance` (rgb) on a plane that
+        faces it."""
+        e = abi.Emitter()
+        e.type = abi.EMITTER_DIRECTIONAL
+        e.nrm[0][:] = tuple(_f32(direction, 3))
+        e.color[:] = tuple(_f32(_rgb3(irradiance), 3))
+        return self._add_light(e)
+
+    def light(self, light: int) -> abi.Emitter:
+        """Light `light` as the world holds it (pupil_world_get_delta_emitter)."""
+        e = abi.Emitter()
+        check(self._lib.pupil_world_get_delta_emitter(self._h, int(light), C.byref(e)))
+        return e
+
+    def set_light(self, light: int, **fields):
+        """Change fields of light `light`: position, direction, intensity (or irradiance: the same
+        field), cutoff_deg, beam_deg, and type (abi.EMITTER_POINT <-> EMITTER_SPOT only; a light
+        cannot cross between point / spot and directional).  Unnamed fields stay.  The next desc()
+        carries the light; PTPass.update_lights hands it to the engine."""
+        e = self.light(light)
+        unknown = set(fields) - {"position", "direction", "intensity", "irradiance", "cutoff_deg", "beam_deg", "type"}
+        if unknown:
+            raise ValueError(f"unknown light field(s): {', '.join(sorted(unknown))}")
+        if "type" in fields:
+            e.type = int(fields["type"])
+        if "position" in fields:
+            e.center[:] = tuple(_f32(fields["position"], 3))
+        if "direction" in fields:
+            e.nrm[0][:] = tuple(_f32(fields["direction"], 3))
+        for name in ("intensity", "irradiance"):
+            if name in fields:
+                e.color[:] = tuple(_f32(_rgb3(fields[name]), 3))
+        if "cutoff_deg" in fields:
+            e.pos[0][0] = _radians(fields["cutoff_deg"])
+            if "beam_deg" not in fields and e.pos[0][1] == 0.0:  # a point turned spot: mitsuba's default
+                e.pos[0][1] = _radians(0.75 * fields["cutoff_deg"])
+        if "beam_deg" in fields:
+            e.pos[0][1] = _radians(fields["beam_deg"])
+        if e.type == abi.EMITTER_POINT:  # a point names neither axis nor angles
+            e.nrm[0][:] = (0.0, 0.0, 0.0)
+            e.pos[0][:] = (0.0, 0.0, 0.0)
+        check(self._lib.pupil_world_set_delta_emitter(self._h, int(light), C.byref(e)))
+        self._desc = None
 
     def desc(self) -> abi.SceneDesc:
         """Flattened scene (pointers owned by the world; valid until it changes)."""
