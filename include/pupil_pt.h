@@ -866,6 +866,28 @@ int pupil_debug_fill_tlas_reserve(pupil_pt *pt, float value);
  * nothing to move.  Either may be NULL. */
 int pupil_debug_bvh_reinsert(int device, uint32_t n, const float *boxes, uint32_t rounds, double *cost,
                              uint32_t *kept, uint32_t *rejected);
+/* the wavefront stages' stable partition of the path ids 0 .. n-1 by a key byte, launched as the
+ * engine launches it, on scratch sized for `capacity` >= n paths (at most 2^28) that is filled
+ * with the word 0xA5A5A5A5 beforehand.  All pointers are host memory.
+ * mode 0 (exclusive): nbins in 1..9, bin = key >> shift_or_tag, the key 0xFF is in no bin; out
+ * has n ids.  mode 1 (flags): nbins = 2, bit b of the key puts the path in bin b when key >> 2 ==
+ * shift_or_tag; out has 2n ids.  bin_mask: 0 = every bin.  The ids of bin b are
+ * out[starts[b] .. starts[b] + counts[b]); the entries of out after *total keep the fill word.
+ * counts, starts: nbins each; total (or NULL): one; log (or NULL): nbins, the counts again.
+ * cum_in (or NULL): nbins running totals the counts are added to -- cum_out (or NULL) receives
+ * the sums and snap (or NULL: the partition gets no snapshot pointer) the totals as they were;
+ * cum_out and snap need cum_in.
+ * info (or NULL): the rounds and blocks of the tile geometry used (blocks = 0 for n = 0), the
+ * histogram entries allocated for the capacity, and 1 when the scratch was written nowhere it
+ * should not be: 64 guard words after the histogram and after the id list, the histogram past
+ * nbins * blocks entries and the id list past n (2n) ids all still hold the fill word.
+ * PUPIL_ERR_INVALID, before the device is touched: keys NULL with n > 0; out, counts or starts
+ * NULL; nbins outside 1..9; mode > 1; mode 1 with nbins != 2; n > capacity; capacity > 2^28;
+ * cum_out or snap without cum_in. */
+int pupil_debug_partition(int device, uint32_t n, uint32_t capacity, const uint8_t *keys, uint32_t nbins,
+                          uint32_t mode, uint32_t shift_or_tag, uint32_t bin_mask, const uint64_t *cum_in,
+                          uint32_t *out, uint32_t *counts, uint32_t *starts, uint32_t *total, uint32_t *log,
+                          uint64_t *cum_out, uint64_t *snap, uint32_t *info);
 
 /* ---- image output (util::BitmapTexture::Save, framework/util/texture.cpp:12-85,152-160) ----
  * rgba: width*height float4, row 0 = image bottom (the "final result" order).

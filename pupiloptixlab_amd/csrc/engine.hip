@@ -20,6 +20,7 @@
 
 #include "host/emitter_weight.h"
 #include "host/pipe_schedule.h"
+#include "host/scoped_buffer.h"
 #include "pt_accel.h"
 
 namespace {
@@ -62,6 +63,14 @@ vec3 pixel_average(const pupil_texture &t) {
     }
     return texture_const_average(t.type, t.c0, t.c1);
 }
+
+// device scratch of one call, freed on every return path (pupil_debug_partition)
+struct HipScratchAlloc {
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+template <typename T>
+using ScratchBuf = ScopedBuffer<T, HipScratchAlloc>;
 
 // material bin of a material type (0 is the miss bin, 8 holds every unknown type)
 uint32_t material_bin(uint32_t type) { return type >= 1u && type <= 7u ? type : 8u; }
@@ -2842,6 +2851,73 @@ int pupil_debug_bvh_reinsert(int device, uint32_t n, const float *boxes, uint32_
     for (uint32_t r = 0; r <= rounds; r++) cost[r] = log.costs[std::min<size_t>(r, log.costs.size() - 1)];
     if (kept) *kept = (uint32_t)log.kept;
     if (rejected) *rejected = (uint32_t)log.rejected;
+    return PUPIL_OK;
+}
+
+int pupil_debug_partition(int device, uint32_t n, uint32_t capacity, const uint8_t *keys, uint32_t nbins,
+                          uint32_t mode, uint32_t shift_or_tag, uint32_t bin_mask, const uint64_t *cum_in,
+                          uint32_t *out, uint32_t *counts, uint32_t *starts, uint32_t *total, uint32_t *log,
+                          uint64_t *cum_out, uint64_t *snap, uint32_t *info) {
+    if ((!keys && n > 0) || !out || !counts || !starts) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (nbins < 1u || nbins > (uint32_t)kPartMaxBins) return fail(PUPIL_ERR_INVALID, "nbins must be in 1..9");
+    if (mode > 1u) return fail(PUPIL_ERR_INVALID, "mode must be 0 (exclusive) or 1 (flags)");
+    if (mode == 1u && nbins != 2u) return fail(PUPIL_ERR_INVALID, "the flags mode has two bins");
+    if (n > capacity) return fail(PUPIL_ERR_INVALID, "n exceeds the capacity");
+    if (capacity > (1u << 28)) return fail(PUPIL_ERR_INVALID, "the capacity exceeds 2^28 paths");
+    if (!cum_in && (cum_out || snap)) return fail(PUPIL_ERR_INVALID, "cum_out and snap need cum_in");
+    HIP_TRY(hipSetDevice(device));
+    constexpr uint32_t kFill = 0xA5A5A5A5u, kGuard = 64;
+    const size_t per = mode == 1u ? 2 : 1;  // ids per path the list can hold
+    const size_t hist_n = partition_hist_entries(capacity), out_n = per * capacity;
+    uint32_t rounds = 0, blocks = 0;
+    partition_geometry(n, &rounds, &blocks);
+    if ((size_t)nbins * blocks > hist_n) return fail(PUPIL_ERR_INVALID, "the histogram would not fit its scratch");
+    // counts, starts, log (kPartMaxBins each) and the total share one small buffer
+    constexpr uint32_t kCounts = 0, kStarts = kPartMaxBins, kLog = 2 * kPartMaxBins, kTotal = 3 * kPartMaxBins;
+    constexpr uint32_t kSmall = 3 * kPartMaxBins + 1;
+    ScratchBuf<uint8_t> d_keys;
+    ScratchBuf<uint32_t> d_hist, d_out, d_small;
+    ScratchBuf<unsigned long long> d_cum;  // nbins totals, then nbins snapshots
+    HIP_TRY(d_keys.alloc(n));
+    HIP_TRY(d_hist.alloc(hist_n + kGuard));
+    HIP_TRY(d_out.alloc(out_n + kGuard));
+    HIP_TRY(d_small.alloc(kSmall));
+    HIP_TRY(d_cum.alloc(2 * kPartMaxBins));
+    // the engine never clears this scratch between launches: nothing may depend on zeros
+    HIP_TRY(hipMemsetD32((hipDeviceptr_t)d_hist.get(), (int)kFill, hist_n + kGuard));
+    HIP_TRY(hipMemsetD32((hipDeviceptr_t)d_out.get(), (int)kFill, out_n + kGuard));
+    HIP_TRY(hipMemsetD32((hipDeviceptr_t)d_small.get(), (int)kFill, kSmall));
+    HIP_TRY(hipMemsetD32((hipDeviceptr_t)d_cum.get(), (int)kFill, 2 * 2 * kPartMaxBins));
+    if (n) HIP_TRY(hipMemcpy(d_keys.get(), keys, n, hipMemcpyHostToDevice));
+    if (cum_in) HIP_TRY(hipMemcpy(d_cum.get(), cum_in, sizeof(uint64_t) * nbins, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    launch_partition(d_keys.get(), n, nbins, mode == 1u ? kPartFlags : kPartExclusive, shift_or_tag, d_out.get(),
+                     d_hist.get(), d_small.get() + kCounts, d_small.get() + kStarts, d_small.get() + kTotal,
+                     d_small.get() + kLog, nullptr, cum_in ? d_cum.get() : nullptr,
+                     cum_in && snap ? d_cum.get() + kPartMaxBins : nullptr, bin_mask);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> h_hist(hist_n + kGuard), h_out(out_n + kGuard);
+    uint32_t h_small[kSmall];
+    HIP_TRY(hipMemcpy(h_hist.data(), d_hist.get(), sizeof(uint32_t) * h_hist.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_out.data(), d_out.get(), sizeof(uint32_t) * h_out.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_small, d_small.get(), sizeof(h_small), hipMemcpyDeviceToHost));
+    if (cum_out) HIP_TRY(hipMemcpy(cum_out, d_cum.get(), sizeof(uint64_t) * nbins, hipMemcpyDeviceToHost));
+    if (snap) HIP_TRY(hipMemcpy(snap, d_cum.get() + kPartMaxBins, sizeof(uint64_t) * nbins, hipMemcpyDeviceToHost));
+    std::copy(h_out.begin(), h_out.begin() + per * n, out);
+    std::copy(h_small + kCounts, h_small + kCounts + nbins, counts);
+    std::copy(h_small + kStarts, h_small + kStarts + nbins, starts);
+    if (log) std::copy(h_small + kLog, h_small + kLog + nbins, log);
+    if (total) *total = h_small[kTotal];
+    if (info) {
+        const auto untouched = [](const std::vector<uint32_t> &v, size_t from) {
+            return std::all_of(v.begin() + from, v.end(), [](uint32_t w) { return w == kFill; });
+        };
+        info[0] = rounds;
+        info[1] = blocks;
+        info[2] = (uint32_t)hist_n;
+        info[3] = untouched(h_hist, (size_t)nbins * blocks) && untouched(h_out, per * n) ? 1u : 0u;
+    }
     return PUPIL_OK;
 }
 

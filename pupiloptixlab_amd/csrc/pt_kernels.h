@@ -390,11 +390,17 @@ void launch_debug_tex(const DeviceScene &sc, uint32_t material, uint32_t slot, c
 
 // stable partition of path ids 0..n-1 by a key byte (queue_partition.hip)
 uint32_t partition_hist_entries(uint32_t n);
+// the tile geometry launch_partition uses for n paths: rounds of 64 paths per wave and the
+// number of blocks (0 for n = 0: the launch is a few memsets)
+void partition_geometry(uint32_t n, uint32_t *rounds, uint32_t *blocks);
 // log_out (or null): the nbins counts; cum_out (or null): the counts are added to these
 // nbins running 64-bit totals (rays traced since the engine was created); snap_out (or
-// null): receives the totals as they were before this partition added to them; bin_mask (or 0 =
-// every bin below nbins): the bins a key can name -- the others are reported empty without being
-// ranked (the material partition of a scene with few materials)
+// null): receives the totals as they were before this partition added to them -- it requires
+// cum_out and is left unwritten without it; bin_mask (or 0 = every bin below nbins; bits at or
+// above nbins are ignored): the bins a key can name -- the others are reported empty without
+// being ranked (the material partition of a scene with few materials).  A key that names a
+// masked-out bin or a bin at or above nbins is dropped: its path is in no list.
+// (tests/test_queue_partition.py pins both.)
 void launch_partition(const uint8_t *keys, uint32_t n, uint32_t nbins, PartMode mode, uint32_t shift, uint32_t *out,
                       uint32_t *hist, uint32_t *counts_out, uint32_t *starts_out, uint32_t *total_out, uint32_t *log_out,
                       hipStream_t s, unsigned long long *cum_out = nullptr, unsigned long long *snap_out = nullptr,

@@ -18,6 +18,9 @@
 // Modes (PartMode, pt_kernels.h): exclusive (bin = key >> shift, 0xFF none),
 // flags (bit b puts the path in bin b when the key's bounce tag, bits 2..7,
 // equals `shift`; a path can be in several bins).
+//
+// Tests: tests/test_queue_partition.py (every id list against an exact stable-partition
+// reference, through pupil_debug_partition), tests/test_queue_partition_host.py.
 #include <algorithm>
 #include <cstdlib>
 
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(1024) void k_part_scan(uint32_t *hist, uint32_t nbl
         starts_out[t] = start;
         counts_out[t] = next - start;
         if (log_out) log_out[t] = next - start;
-        if (snap_out) snap_out[t] = cum_out[t];  // the totals before this partition
+        if (snap_out && cum_out) snap_out[t] = cum_out[t];  // the totals before this partition
         if (cum_out) cum_out[t] += next - start;  // one block, stream-ordered: no atomics needed
     }
     if (t == 0 && total_out) *total_out = carry;
@@ -230,6 +233,11 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(const uint8_t *keys
 // that grows with n: the scratch sized for the capacity serves every smaller batch
 uint32_t partition_hist_entries(uint32_t n) {
     return kPartMaxBins * std::max(kPartTargetBlocks, (n + 256u * kPartMaxRounds - 1) / (256u * kPartMaxRounds));
+}
+
+void partition_geometry(uint32_t n, uint32_t *rounds, uint32_t *blocks) {
+    *rounds = part_rounds(n);
+    *blocks = part_blocks(n);
 }
 
 void launch_partition(const uint8_t *keys, uint32_t n, uint32_t nbins, PartMode mode, uint32_t shift, uint32_t *out,
