@@ -833,6 +833,11 @@ int pupil_debug_emitter_sample(pupil_pt *pt, uint32_t emitter, uint32_t n, const
  * NULL for the count; a count of 0 means the table has none (fewer than two emitters, or
  * PUPIL_EMITTER_SELECT=binary). */
 int pupil_debug_read_emitter_guide(pupil_pt *pt, uint32_t *bits, uint32_t *guide, uint32_t *inout_count);
+/* the shade kernels keep copies of the scene's small tables in each block's LDS: caps = the entry
+ * caps of the instance, material, area-emitter (delta lights included) and cull-set copies, and
+ * *fit (pt may be NULL: then only the caps) has bit k set when table k of the engine's scene is
+ * within its cap now; a table over its cap is read from global memory.  Either pointer may be NULL. */
+int pupil_debug_shade_tables(pupil_pt *pt, uint32_t caps[4], uint32_t *fit);
 /* the device's env emitter on n inputs of 3 floats, from the shading point pos_nrm =
  * (position xyz, normal xyz); out: 8 floats per input.
  * mode 0: Emitter::SampleDirect (render/emitter/env.h:23-49, 70-79) with xi = (in.x, in.y),

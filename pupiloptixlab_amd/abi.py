@@ -175,6 +175,7 @@ SIGNATURES = {
     "pupil_debug_read_material": (C.c_int, [C.c_void_p, C.c_uint32, u32p, f32p]),
     "pupil_debug_read_emitters": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, f32p]),
     "pupil_debug_read_emitter_guide": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
+    "pupil_debug_shade_tables": (C.c_int, [C.c_void_p, u32p, u32p]),
     "pupil_debug_fill_tlas_reserve": (C.c_int, [C.c_void_p, C.c_float]),
     "pupil_pt_render": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Launch), C.c_void_p]),
     "pupil_pt_stats": (C.c_int, [C.c_void_p, C.POINTER(Counters)]),

@@ -986,6 +986,8 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
     sc.inst_guide_shift = guide_shift;
     sc.instances = pt->d_insts;
     sc.materials = pt->d_mats;
+    sc.num_instances = (uint32_t)insts.size();
+    sc.num_materials = (uint32_t)mats.size();
     return PUPIL_OK;
 }
 
@@ -1046,6 +1048,9 @@ void read_knobs(pupil_pt *pt) {
     // most paths of one chunk of pupil_pt_radiance_rays, which bounds its scratch (at least a wave)
     if (const char *g = std::getenv("PUPIL_RADIANCE_CHUNK"))
         pt->rad_chunk = (size_t)std::min(2147483647.0, std::max(64.0, std::atof(g)));
+    sc.shade_max_blocks = kShadeMaxBlocks;
+    if (const char *g = std::getenv("PUPIL_SHADE_MAX_BLOCKS"))
+        sc.shade_max_blocks = (uint32_t)std::min(1 << 20, std::max(64, std::atoi(g)));
     sc.trace_node_min = 8;  // node phase ends below 8 active lanes (7 waves: 8 and 12 beat 4 by 1.5 %; 2 is slower)
     if (const char *r = std::getenv("PUPIL_NODE_MIN")) sc.trace_node_min = (uint32_t)std::min(64, std::max(1, std::atoi(r)));
 }
@@ -2703,6 +2708,15 @@ int pupil_debug_read_emitters(pupil_pt *pt, uint32_t first, uint32_t n, float *o
             o[10] = d.pos[0].x, o[11] = d.pos[0].y, o[12] = 0.f;
         }
         o[22] = o[23] = 0.f;
+    }
+    return PUPIL_OK;
+}
+
+int pupil_debug_shade_tables(pupil_pt *pt, uint32_t caps[4], uint32_t *fit) {
+    if (caps) shade_table_caps(caps);
+    if (fit) {
+        if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+        *fit = shade_tables_fit(pt->sc);
     }
     return PUPIL_OK;
 }

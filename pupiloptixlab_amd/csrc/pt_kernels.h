@@ -23,6 +23,7 @@ constexpr int kRing = 16;       // persistent BVH4 kernels: per-lane LDS ring en
 // overwrites a live entry.
 constexpr int kTraceStackEntries = kRing + kStackOvf;
 constexpr int kShadeBlock = 256;
+constexpr uint32_t kShadeMaxBlocks = 16384;  // largest shade grid (pt_kernels.hip shade_blocks)
 constexpr uint32_t kMaxDepth = 128;  // PTPass inspector range (pt_pass.cpp:225-237)
 constexpr uint32_t kNumQueues = 9;  // 0 = miss, 1..7 = EMatType, 8 = unknown material
 constexpr uint32_t kMissIndex = 0xFFFFFFFFu;
@@ -197,6 +198,11 @@ enum ShadeList : int { kShadeBins = 0, kShadeAll = 1, kShadeNext = 2, kShadeNext
 void launch_shade(const DeviceScene &sc, const FrameParams &fp, const PathState &ps, const Queues &q, uint32_t tag,
                   hipStream_t s, ShadeList list, uint32_t range_base, uint32_t range_n, uint32_t max_count,
                   bool fresh_range = false, uint32_t fresh_seed0 = 0);
+// The shade kernels' block-resident scene tables (pt_shade.h BlockTables).  shade_table_caps: the
+// entry caps of the instance, material, area-emitter and cull-set copies, in that order;
+// shade_tables_fit: bit k set = table k of `sc` is within its cap and is read from the LDS copy
+void shade_table_caps(uint32_t caps[4]);
+uint32_t shade_tables_fit(const DeviceScene &sc);
 // one persistent launch over the next + shadow lists of a bounce (BVH4 persistent path only)
 // ahead_count > 0 (render-ahead, BVH4 kernels only): the launch also traces the camera
 // rays of the next render.  `ps` is then the base of both buffer halves: this render's

@@ -49,6 +49,62 @@ __global__ __launch_bounds__(kShadeBlock) void k_generate(DeviceScene sc, FrameP
 }
 
 // ------------------------------------------------------------------ shade
+// Block-resident scene tables (pt_shade.h BlockTables): every shade block copies the scene's small
+// tables into its LDS before it shades, so the dependent gathers of a path's shade (instance ->
+// material -> emitter guide -> CDF -> emitter, and the cull set's records) are LDS reads instead
+// of trips through the L1 behind the path-state misses.  TAB = 1: the host found every table
+// within its cap, all pointers are LDS; TAB = 2: `fit` (bit 0 instances, 1 materials, 2 area
+// emitters with CDF, guide and env, 3 cull set) names the tables that are, the others stay in
+// global memory.  The copies are made on every launch from the engine's tables, which the update
+// calls keep current.
+__device__ __forceinline__ void stage_copy(uint32_t *dst, const void *src, uint32_t bytes) {
+    const uint32_t n16 = bytes / 16u;
+    for (uint32_t i = threadIdx.x; i < n16; i += kShadeBlock)
+        reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
+    for (uint32_t i = 4u * n16 + threadIdx.x; i < bytes / 4u; i += kShadeBlock)
+        dst[i] = reinterpret_cast<const uint32_t *>(src)[i];
+}
+
+template <int TAB>
+__device__ __forceinline__ BlockTables stage_tables(const DeviceScene &sc, uint32_t fit, uint32_t *s) {
+    const bool f_inst = TAB == 1 || (fit & 1u), f_mat = TAB == 1 || (fit & 2u), f_area = TAB == 1 || (fit & 4u),
+               f_cull = TAB == 1 || (fit & 8u);
+    uint32_t *s_inst = s + kTabOffInst / 4u, *s_mat = s + kTabOffMat / 4u, *s_area = s + kTabOffArea / 4u,
+             *s_cdf = s + kTabOffCdf / 4u, *s_guide = s + kTabOffGuide / 4u, *s_crec = s + kTabOffCullRec / 4u,
+             *s_cobj = s + kTabOffCullObj / 4u;
+    uint32_t *s_env = s_area + kTabAreas * (uint32_t)(sizeof(DevEmitter) / 4u);
+    if (f_inst) stage_copy(s_inst, sc.instances, sc.num_instances * (uint32_t)sizeof(DevInstance));
+    if (f_mat) stage_copy(s_mat, sc.materials, sc.num_materials * (uint32_t)sizeof(DevMaterial));
+    if (f_area) {
+        stage_copy(s_area, sc.areas, sc.num_areas * (uint32_t)sizeof(DevEmitter));
+        stage_copy(s_cdf, sc.area_cdf, sc.num_areas * 4u);
+        if (sc.area_guide) stage_copy(s_guide, sc.area_guide, ((1u << sc.guide_bits) + 1u) * 4u);
+        if (sc.has_env) stage_copy(s_env, sc.env, (uint32_t)sizeof(DevEmitter));
+    }
+    if (f_cull && threadIdx.x < sc.cull_n) {
+        const uint32_t k = threadIdx.x, i = sc.cull_set[k];
+        const float4 a = sc.prims[kRecF4 * i + 0];
+        reinterpret_cast<float4 *>(s_crec)[3 * k + 0] = a;
+        const float4 b = sc.prims[kRecF4 * i + 1];
+        reinterpret_cast<float4 *>(s_crec)[3 * k + 1] = b;
+        reinterpret_cast<float4 *>(s_crec)[3 * k + 2] = sc.prims[kRecF4 * i + 2];
+        if (__float_as_uint(a.w) & kPrimSphereBit) {
+            const float *t = sc.instances[__float_as_uint(b.w)].to_object;
+            for (int j = 0; j < 12; j++) reinterpret_cast<float *>(s_cobj)[12 * k + j] = t[j];
+        }
+    }
+    __syncthreads();
+    return BlockTables{f_inst ? reinterpret_cast<const DevInstance *>(s_inst) : sc.instances,
+                       f_mat ? reinterpret_cast<const DevMaterial *>(s_mat) : sc.materials,
+                       f_area ? reinterpret_cast<const DevEmitter *>(s_area) : sc.areas,
+                       f_area ? reinterpret_cast<const DevEmitter *>(s_env) : sc.env,
+                       f_area ? reinterpret_cast<const float *>(s_cdf) : sc.area_cdf,
+                       f_area ? reinterpret_cast<const uint32_t *>(s_guide) : sc.area_guide,
+                       f_cull ? reinterpret_cast<const float4 *>(s_crec) : nullptr,
+                       reinterpret_cast<const float *>(s_cobj),
+                       sc};
+}
+
 // All shading of a bounce in one launch (4 waves per SIMD: <= 128 VGPRs).  The material bins lie back to back in
 // q.bins (bin 0 = miss, 1..7 = EMatType, 8 = unknown type), each in increasing
 // path order, so a wave sees one material except at the 8 bin boundaries; the
@@ -61,19 +117,28 @@ __global__ __launch_bounds__(kShadeBlock) void k_generate(DeviceScene sc, FrameP
 // Only the miss / hit split diverges inside a wave, which costs less than the three
 // partition launches.  Each path's bounce comes from its own state, so the paths of
 // several frames in flight (pipelined renders, engine.hip) share one launch.
-template <int LIST>
+// TAB: stage_tables.  126-128 VGPRs, no scratch but 12 B in <next, mixed tables>, 30432 B of LDS per
+// block (four blocks per CU at 4 waves per SIMD).
+template <int LIST, int TAB>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_shade_all(DeviceScene sc, FrameParams fp, PathState ps, Queues q,
                                                            uint32_t tag, uint32_t range_base, uint32_t range_n,
-                                                           uint32_t fresh_range, uint32_t fresh_seed0) {
+                                                           uint32_t fresh_range, uint32_t fresh_seed0, uint32_t fit) {
+    __shared__ uint4 s_tab[kTabBytes / 16u];
     const uint32_t n_list = LIST == kShadeNext || LIST == kShadeNextRange ? q.counts[kCntNext] : 0u;
     const uint32_t count = LIST == kShadeBins ? q.counts[kScratch]  // all traced paths (total of the bin partition)
                                               : n_list + (LIST == kShadeAll || LIST == kShadeNextRange ? range_n : 0u);
     uint32_t start[kPartMaxBins];
 #pragma unroll
     for (int b = 0; b < kPartMaxBins; b++) start[b] = LIST == kShadeBins ? q.counts[kStartBins + b] : 0u;
+    if (blockIdx.x * blockDim.x >= count) return;  // the whole block: no path, no copies
+    const BlockTables tb = stage_tables<TAB>(sc, fit, reinterpret_cast<uint32_t *>(s_tab));
     const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-        const uint32_t p = LIST == kShadeBins ? q.bins[i] : (i < n_list ? q.nxsh[i] : range_base + (i - n_list));
+    auto path_of = [&](uint32_t k) {
+        return LIST == kShadeBins ? q.bins[k] : (k < n_list ? q.nxsh[k] : range_base + (k - n_list));
+    };
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < count; i += stride) {
+        const uint32_t p = path_of(i);
         // bin of list position i: the last bin starting at or before i (an empty
         // bin starts where the next one does, so it is never the last such bin)
         uint32_t bin = 0;
@@ -91,19 +156,19 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(4))
         const uint32_t fresh_p = p - range_base;
         uint32_t flags = 0;
         switch (bin) {
-        case 0: shade_miss(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
-        case PUPIL_MAT_DIFFUSE: flags = shade_hit<PUPIL_MAT_DIFFUSE>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
-        case PUPIL_MAT_DIELECTRIC: flags = shade_hit<PUPIL_MAT_DIELECTRIC>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        case 0: shade_miss(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        case PUPIL_MAT_DIFFUSE: flags = shade_hit<PUPIL_MAT_DIFFUSE>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        case PUPIL_MAT_DIELECTRIC: flags = shade_hit<PUPIL_MAT_DIELECTRIC>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
         case PUPIL_MAT_ROUGH_DIELECTRIC:
-            flags = shade_hit<PUPIL_MAT_ROUGH_DIELECTRIC>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0);
+            flags = shade_hit<PUPIL_MAT_ROUGH_DIELECTRIC>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0);
             break;
-        case PUPIL_MAT_CONDUCTOR: flags = shade_hit<PUPIL_MAT_CONDUCTOR>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        case PUPIL_MAT_CONDUCTOR: flags = shade_hit<PUPIL_MAT_CONDUCTOR>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
         case PUPIL_MAT_ROUGH_CONDUCTOR:
-            flags = shade_hit<PUPIL_MAT_ROUGH_CONDUCTOR>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0);
+            flags = shade_hit<PUPIL_MAT_ROUGH_CONDUCTOR>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0);
             break;
-        case PUPIL_MAT_PLASTIC: flags = shade_hit<PUPIL_MAT_PLASTIC>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
-        case PUPIL_MAT_ROUGH_PLASTIC: flags = shade_hit<PUPIL_MAT_ROUGH_PLASTIC>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
-        default: flags = shade_hit<0u>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        case PUPIL_MAT_PLASTIC: flags = shade_hit<PUPIL_MAT_PLASTIC>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        case PUPIL_MAT_ROUGH_PLASTIC: flags = shade_hit<PUPIL_MAT_ROUGH_PLASTIC>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
+        default: flags = shade_hit<0u>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0); break;
         }
         if (fp.nee_count) {  // collect_stats only: the reference's shadow-ray count, one atomic per wave
             const unsigned long long m = __ballot((flags & 4u) != 0u);
@@ -118,26 +183,35 @@ __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(4))
 
 // Single-material scenes (DeviceScene::single_bin, list modes): the same launch with only the
 // miss path and material MAT compiled, so the register budget is that material's, not the
-// largest of the seven BSDFs' (126 VGPRs, 4 waves per SIMD): diffuse needs 101-105 and runs at
-// 5 waves (96 VGPRs, 7-10 spills; config 4 -2.8 % per step, profiles/r04_shade_one_ab.txt);
-// the other BSDFs spill 15-43 registers at 5 waves and stay at 4 (A/B: PUPIL_SHADE_ONE=0).
+// largest of the seven BSDFs' (126-128 VGPRs, 4 waves per SIMD): diffuse runs at 5 waves (96
+// VGPRs; config 4 -2.8 % per step, profiles/r04_shade_one_ab.txt); the other BSDFs spill 15-43
+// registers at 5 waves and stay at 4 (A/B: PUPIL_SHADE_ONE=0).  With the tables in LDS (TAB = 1)
+// the three diffuse instances hold 8 / 12 / 0 B of scratch per lane (range / next / next + range;
+// 28 / 40 / 28 B with the tables in global memory), the others 117-128 VGPRs and none; every
+// instance has 30432 B of LDS per block, five blocks per CU at 5 waves (pt_shade.h has the
+// budget; profiles/shade_tables_ab.txt section 5 the full register table).
 constexpr int shade_one_waves(uint32_t mat) { return mat == PUPIL_MAT_DIFFUSE ? 5 : 4; }
-template <int LIST, uint32_t MAT>
+template <int LIST, uint32_t MAT, int TAB>
 __global__ __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(shade_one_waves(MAT)))) void k_shade_one(
     DeviceScene sc, FrameParams fp, PathState ps, Queues q, uint32_t tag, uint32_t range_base, uint32_t range_n,
-    uint32_t fresh_range, uint32_t fresh_seed0) {
+    uint32_t fresh_range, uint32_t fresh_seed0, uint32_t fit) {
     static_assert(LIST != kShadeBins, "single-material shading walks a list");
+    __shared__ uint4 s_tab[kTabBytes / 16u];
     const uint32_t n_list = LIST == kShadeNext || LIST == kShadeNextRange ? q.counts[kCntNext] : 0u;
     const uint32_t count = n_list + (LIST == kShadeAll || LIST == kShadeNextRange ? range_n : 0u);
+    if (blockIdx.x * blockDim.x >= count) return;  // the whole block: no path, no copies
+    const BlockTables tb = stage_tables<TAB>(sc, fit, reinterpret_cast<uint32_t *>(s_tab));
     const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-        const uint32_t p = i < n_list ? q.nxsh[i] : range_base + (i - n_list);
+    auto path_of = [&](uint32_t k) { return k < n_list ? q.nxsh[k] : range_base + (k - n_list); };
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i < count; i += stride) {
+        const uint32_t p = path_of(i);
         const bool miss = __float_as_uint(ld_ps(ps.hit + p).w) == kMissIndex;
         const bool fresh = fresh_range && i >= n_list;
         const uint32_t fresh_p = p - range_base;
         uint32_t flags = 0;
-        if (miss) shade_miss(sc, fp, ps, p, fresh, fresh_p, fresh_seed0);
-        else flags = shade_hit<MAT>(sc, fp, ps, p, fresh, fresh_p, fresh_seed0);
+        if (miss) shade_miss(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0);
+        else flags = shade_hit<MAT>(sc, tb, fp, ps, p, fresh, fresh_p, fresh_seed0);
         if (fp.nee_count) {
             const unsigned long long m = __ballot((flags & 4u) != 0u);
             if (m && __lane_id() == __ffsll((unsigned long long)__builtin_amdgcn_read_exec()) - 1)
@@ -298,30 +372,59 @@ void launch_generate(const DeviceScene &sc, const FrameParams &fp, const PathSta
 }
 
 
-// Shade launch size: one thread per path of the batch (fp.num_paths bounds the
-// traced count, which only the device knows), so the hardware dispatcher
-// balances the waves instead of a grid-stride loop over a fixed grid (A/B at
-// config 4: 3.75 vs 4.05 ms of shading per frame with 2048 blocks = twice the
-// resident waves).  PUPIL_SHADE_BLOCKS overrides it (A/B knob).
-static uint32_t shade_blocks(uint32_t num_paths) {
+// Shade launch size: one thread per path of the batch (fp.num_paths bounds the traced count, which
+// only the device knows) up to DeviceScene::shade_max_blocks blocks (kShadeMaxBlocks unless the
+// engine's PUPIL_SHADE_MAX_BLOCKS says otherwise); a larger batch is walked by that many blocks in
+// a grid-stride loop.  Each block pays for its table copies once (stage_tables), so blocks that
+// shade several paths per thread amortise them, while 16384 blocks -- 64 per CU, about 13 times the
+// resident ones -- still leave the balancing to the hardware dispatcher (a grid of 2048 blocks was
+// 8 % slower than one thread per path before the copies existed; profiles/shade_tables_ab.txt has
+// the sweep).  PUPIL_SHADE_BLOCKS forces the grid size as before (A/B knob).
+static uint32_t shade_blocks(uint32_t num_paths, uint32_t max_blocks) {
     static const int forced = [] {
         const char *e = std::getenv("PUPIL_SHADE_BLOCKS");
         return e ? std::min(1 << 20, std::max(64, std::atoi(e))) : 0;
     }();
     if (forced) return (uint32_t)forced;
-    return std::max(64u, std::min(1u << 20, (num_paths + kShadeBlock - 1) / kShadeBlock));
+    const uint32_t cap = max_blocks ? max_blocks : kShadeMaxBlocks;
+    return std::max(64u, std::min(cap, (num_paths + kShadeBlock - 1) / kShadeBlock));
+}
+
+// Which of the small tables a shade block copies into its LDS (stage_tables' `fit` bits): those
+// within their caps.  PUPIL_SHADE_TABLES masks the bits (A/B knob; 0 = every table stays global).
+void shade_table_caps(uint32_t caps[4]) {
+    caps[0] = kTabInstances, caps[1] = kTabMaterials, caps[2] = kTabAreas, caps[3] = kTabCull;
+}
+uint32_t shade_tables_fit(const DeviceScene &sc) {
+    static const uint32_t mask = [] {
+        const char *e = std::getenv("PUPIL_SHADE_TABLES");
+        return e ? (uint32_t)std::atoi(e) & 15u : 15u;
+    }();
+    const bool areas = sc.num_areas <= kTabAreas && (!sc.area_guide || (1u << sc.guide_bits) <= kTabAreas);
+    return ((sc.num_instances <= kTabInstances ? 1u : 0u) | (sc.num_materials <= kTabMaterials ? 2u : 0u) |
+            (areas ? 4u : 0u) | (sc.cull_n <= kTabCull ? 8u : 0u)) & mask;
 }
 
 // max_count: host bound on the paths the launch may list (the device knows the count)
 void launch_shade(const DeviceScene &sc, const FrameParams &fp, const PathState &ps, const Queues &q, uint32_t tag,
                   hipStream_t s, ShadeList list, uint32_t range_base, uint32_t range_n, uint32_t max_count,
                   bool fresh_range, uint32_t fresh_seed0) {
-    const dim3 g(shade_blocks(max_count)), b(kShadeBlock);
+    const dim3 g(shade_blocks(max_count, sc.shade_max_blocks)), b(kShadeBlock);
     const uint32_t fr = fresh_range && list != kShadeBins ? 1u : 0u;
-#define SHADE(L) \
-    hipLaunchKernelGGL(k_shade_all<L>, g, b, 0, s, sc, fp, ps, q, tag, range_base, range_n, fr, fresh_seed0)
-#define SHADE1(L, M) \
-    hipLaunchKernelGGL((k_shade_one<L, M>), g, b, 0, s, sc, fp, ps, q, tag, range_base, range_n, fr, fresh_seed0)
+    const uint32_t fit = shade_tables_fit(sc);
+#define SHADE(L)                                                                                                       \
+    if (fit == 15u)                                                                                                    \
+        hipLaunchKernelGGL((k_shade_all<L, 1>), g, b, 0, s, sc, fp, ps, q, tag, range_base, range_n, fr, fresh_seed0,  \
+                           fit);                                                                                       \
+    else                                                                                                               \
+        hipLaunchKernelGGL((k_shade_all<L, 2>), g, b, 0, s, sc, fp, ps, q, tag, range_base, range_n, fr, fresh_seed0, fit)
+#define SHADE1(L, M)                                                                                                   \
+    if (fit == 15u)                                                                                                    \
+        hipLaunchKernelGGL((k_shade_one<L, M, 1>), g, b, 0, s, sc, fp, ps, q, tag, range_base, range_n, fr,            \
+                           fresh_seed0, fit);                                                                          \
+    else                                                                                                               \
+        hipLaunchKernelGGL((k_shade_one<L, M, 2>), g, b, 0, s, sc, fp, ps, q, tag, range_base, range_n, fr,            \
+                           fresh_seed0, fit)
 #define SHADE1_ALL(L)                                                       \
     switch (sc.single_bin) {                                                \
     case PUPIL_MAT_DIFFUSE: SHADE1(L, PUPIL_MAT_DIFFUSE); break;             \

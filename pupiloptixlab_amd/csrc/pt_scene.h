@@ -191,6 +191,7 @@ struct DeviceScene {
     const uint32_t *inst_first;
     const uint32_t *inst_guide;
     uint32_t inst_guide_shift;
+    uint32_t num_instances;  // entries of `instances` (in what was padding: the struct keeps its size)
     const DevInstance *instances;
     const DevMaterial *materials;
     const DevEmitter *areas;
@@ -202,6 +203,7 @@ struct DeviceScene {
     uint32_t guide_bits;
     uint32_t num_areas;
     uint32_t has_env;
+    uint32_t num_materials;  // entries of `materials` (in what was padding)
     const DevEmitter *env;
     // Terminal-ray cull set (engine.hip derive_cull_set): the record slots in `prims` of every
     // emissive primitive, in increasing order, when there are at most kCullSetMax of them, the
@@ -210,6 +212,9 @@ struct DeviceScene {
     const uint32_t *cull_set;
     uint32_t cull_n;
     Camera camera;
+    // shade launches above this many blocks of kShadeBlock paths stride over their list
+    // (pt_kernels.hip shade_blocks; the engine's PUPIL_SHADE_MAX_BLOCKS knob; in the tail padding)
+    uint32_t shade_max_blocks;
 };
 
 }  // namespace pupil

@@ -66,6 +66,85 @@ __device__ __forceinline__ uint32_t fresh_rng_of(const FrameParams &fp, uint32_t
     return rng;
 }
 
+// ------------------------------------------------------------------ the small scene tables
+// What the shade reads of the scene's small tables -- instances, materials, the area emitters
+// with their CDF and guide, the env emitter and the terminal-ray cull set's records -- goes
+// through one accessor type (the TB parameter of the functions below).  GlobalTables reads
+// DeviceScene's pointers; BlockTables (pt_kernels.hip) reads the copies a shade block made in
+// its LDS at its start.  Only where an operand comes from differs: the float operations and
+// their order are the same.
+struct GlobalTables {
+    const DeviceScene &sc;
+    __device__ __forceinline__ const DevInstance &instance(uint32_t i) const { return sc.instances[i]; }
+    __device__ __forceinline__ const DevMaterial &material(uint32_t i) const { return sc.materials[i]; }
+    __device__ __forceinline__ const DevEmitter &area(uint32_t i) const { return sc.areas[i]; }
+    __device__ __forceinline__ const DevEmitter *env() const { return sc.env; }
+    __device__ __forceinline__ float area_cdf(uint32_t i) const { return sc.area_cdf[i]; }
+    __device__ __forceinline__ uint32_t area_guide(uint32_t k) const { return sc.area_guide[k]; }
+    // entry k of the cull set: its record's three vertex words, and (a sphere) its instance's to_object
+    __device__ __forceinline__ void cull_record(uint32_t k, float4 &a, float4 &b, float4 &c) const {
+        const uint32_t i = sc.cull_set[k];
+        a = sc.prims[kRecF4 * i + 0];
+        b = sc.prims[kRecF4 * i + 1];
+        c = sc.prims[kRecF4 * i + 2];
+    }
+    __device__ __forceinline__ const float *cull_to_object(uint32_t k, float4 b) const {
+        return sc.instances[__float_as_uint(b.w)].to_object;
+    }
+};
+
+// Entry caps of the block-resident copies (a table over its cap stays in global memory, decided
+// per table at launch) and their layout in a block's LDS, in bytes, every part 16-B aligned:
+//   instances 44 x 224 = 9856 | materials 40 x 352 = 14080 | area emitters (16 + the env) x 328 =
+//   5576 -> 5584 | CDF 16 x 4 = 64 | guide 17 x 4 = 68 -> 80 | cull records 8 x 48 = 384 | cull
+//   to_object 8 x 48 = 384: 30432 B, allocated as 30720 (512-B granules).
+// A CU holds 160 KB = 163840 B: 5 waves per SIMD at kShadeBlock = 256 are 5 blocks (153600 B), 4
+// waves are 4 blocks, so the copies never lower the occupancy amdgpu_waves_per_eu asks for.
+// (Config 5 has 40 instances and 40 materials; the engine's default cull set holds at most 8.)
+constexpr uint32_t kTabInstances = 44, kTabMaterials = 40, kTabAreas = 16, kTabCull = 8;
+constexpr uint32_t kTabOffInst = 0;
+constexpr uint32_t kTabOffMat = kTabOffInst + kTabInstances * (uint32_t)sizeof(DevInstance);
+constexpr uint32_t kTabOffArea = kTabOffMat + kTabMaterials * (uint32_t)sizeof(DevMaterial);
+constexpr uint32_t kTabOffCdf = (kTabOffArea + (kTabAreas + 1u) * (uint32_t)sizeof(DevEmitter) + 15u) & ~15u;
+constexpr uint32_t kTabOffGuide = kTabOffCdf + kTabAreas * 4u;
+constexpr uint32_t kTabOffCullRec = (kTabOffGuide + (kTabAreas + 1u) * 4u + 15u) & ~15u;
+constexpr uint32_t kTabOffCullObj = kTabOffCullRec + kTabCull * 48u;
+constexpr uint32_t kTabBytes = kTabOffCullObj + kTabCull * 48u;
+static_assert(sizeof(DevInstance) % 16 == 0 && sizeof(DevMaterial) % 16 == 0 && sizeof(DevEmitter) % 4 == 0, "copy units");
+static_assert(5u * ((kTabBytes + 511u) & ~511u) <= 160u * 1024u, "five shade blocks per CU");
+
+// The tables as a shade block reads them: each pointer is the block's LDS copy or, for a table
+// over its cap, DeviceScene's own (a wave-uniform choice made once per block).
+struct BlockTables {
+    const DevInstance *instances;
+    const DevMaterial *materials;
+    const DevEmitter *areas;
+    const DevEmitter *env_;
+    const float *cdf;
+    const uint32_t *guide;
+    const float4 *cull_rec;  // LDS: 3 float4 per set entry; null = read through sc.cull_set
+    const float *cull_obj;   // LDS: 12 floats per set entry (written for spheres only)
+    const DeviceScene &sc;
+    __device__ __forceinline__ const DevInstance &instance(uint32_t i) const { return instances[i]; }
+    __device__ __forceinline__ const DevMaterial &material(uint32_t i) const { return materials[i]; }
+    __device__ __forceinline__ const DevEmitter &area(uint32_t i) const { return areas[i]; }
+    __device__ __forceinline__ const DevEmitter *env() const { return env_; }
+    __device__ __forceinline__ float area_cdf(uint32_t i) const { return cdf[i]; }
+    __device__ __forceinline__ uint32_t area_guide(uint32_t k) const { return guide[k]; }
+    __device__ __forceinline__ void cull_record(uint32_t k, float4 &a, float4 &b, float4 &c) const {
+        if (cull_rec) {
+            a = cull_rec[3 * k + 0];
+            b = cull_rec[3 * k + 1];
+            c = cull_rec[3 * k + 2];
+        } else {
+            GlobalTables{sc}.cull_record(k, a, b, c);
+        }
+    }
+    __device__ __forceinline__ const float *cull_to_object(uint32_t k, float4 b) const {
+        return cull_rec ? cull_obj + 12 * k : instances[__float_as_uint(b.w)].to_object;
+    }
+};
+
 struct HitGeo {
     LocalGeo g;
     int emitter;
@@ -77,8 +156,9 @@ struct HitGeo {
 // shading record (bvh_build.hip k_attrs: object-space vertices, normals, uvs).
 // ro_rec: the ray origin record, read only for a sphere hit (the triangle position is
 // interpolated from the vertices)
-__device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, float4 h, const float4 *ro_rec, bool fresh,
-                                             vec3 rd, vec2 stale_uv) {
+template <class TB>
+__device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, const TB &tb, float4 h, const float4 *ro_rec,
+                                             bool fresh, vec3 rd, vec2 stale_uv) {
     HitGeo out;
     const uint32_t idx = __float_as_uint(h.w);
     // flat: idx = record in traversal order, which names the instance; two-level:
@@ -90,7 +170,7 @@ __device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, float4 h, c
     if (sc.two_level) {
         gprim = idx;
         inst_id = inst_of_prim(sc, idx);
-        const DevInstance &ti = sc.instances[inst_id];
+        const DevInstance &ti = tb.instance(inst_id);
         sphere = ti.kind == PUPIL_SHAPE_SPHERE;
         rec = sc.attrs + (size_t)kAttrStride * (sphere ? 0u : ti.attr_base + (idx - ti.prim_offset));
         for (int k = 0; k < 7; k++) ra[k] = rec[k];
@@ -110,7 +190,7 @@ __device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, float4 h, c
         sphere = (ref & kPrimSphereBit) != 0u;
         inst_id = __float_as_uint(ra[1].w);
     }
-    const DevInstance &in = sc.instances[inst_id];
+    const DevInstance &in = tb.instance(inst_id);
     out.inst = inst_id;
     LocalGeo &g = out.g;
     g.texcoord = stale_uv;
@@ -159,6 +239,10 @@ __device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, float4 h, c
     out.emitter = in.emitter_offset >= 0 ? in.emitter_offset + (int)local : -1;
     return out;
 }
+__device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, float4 h, const float4 *ro_rec, bool fresh,
+                                             vec3 rd, vec2 stale_uv) {
+    return reconstruct(sc, GlobalTables{sc}, h, ro_rec, fresh, rd, stale_uv);
+}
 
 // EmitterGroup::SelectOneEmiiter (render/emitter.h:110-135) as a binary search
 // over the sequentially accumulated CDF: picks the same emitter as the scan.
@@ -167,25 +251,30 @@ __device__ __forceinline__ HitGeo reconstruct(const DeviceScene &sc, float4 h, c
 // order), else the env emitter, else the last area emitter.  The guide table narrows
 // the search to the bucket of p (expected O(1) for any emitter count); the binary
 // search over that range returns exactly the linear scan's index.
-__device__ __forceinline__ const DevEmitter *select_emitter(const DeviceScene &sc, float p, float &sel_prob) {
+template <class TB>
+__device__ __forceinline__ const DevEmitter *select_emitter(const DeviceScene &sc, const TB &tb, float p,
+                                                            float &sel_prob) {
     uint32_t lo = 0, hi = sc.num_areas;
     if (sc.area_guide) {
         const uint32_t m = 1u << sc.guide_bits;
         const uint32_t k = min((uint32_t)(p * (float)m), m - 1u);  // exact: m is a power of two <= 2^24
-        lo = sc.area_guide[k];
-        hi = sc.area_guide[k + 1];
+        lo = tb.area_guide(k);
+        hi = tb.area_guide(k + 1);
     }
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (p <= sc.area_cdf[mid]) hi = mid;
+        if (p <= tb.area_cdf(mid)) hi = mid;
         else lo = mid + 1;
     }
     const DevEmitter *e = nullptr;
-    if (lo < sc.num_areas) e = &sc.areas[lo];
-    else if (sc.has_env) e = sc.env;
-    else if (sc.num_areas > 0) e = &sc.areas[sc.num_areas - 1];
+    if (lo < sc.num_areas) e = &tb.area(lo);
+    else if (sc.has_env) e = tb.env();
+    else if (sc.num_areas > 0) e = &tb.area(sc.num_areas - 1);
     sel_prob = e ? e->select_probability : 0.f;
     return e;
+}
+__device__ __forceinline__ const DevEmitter *select_emitter(const DeviceScene &sc, float p, float &sel_prob) {
+    return select_emitter(sc, GlobalTables{sc}, p, sel_prob);
 }
 
 // One path that hit a surface of material MAT (0 = unknown type): emission and
@@ -215,18 +304,16 @@ __device__ __forceinline__ bool last_sample(const FrameParams &fp, uint32_t p, u
 // own (intersect_leaf_dyn: ray_pre, intersect_triangle / intersect_unit_sphere) on its own records,
 // from the o and d the shade would store for it, so "rejected here" implies "rejected there" bit
 // for bit; a ray that passes is traced as ever.  The loop is wave-uniform.
-__device__ __forceinline__ bool terminal_ray_culled(const DeviceScene &sc, vec3 o, vec3 d) {
+template <class TB>
+__device__ __forceinline__ bool terminal_ray_culled(const DeviceScene &sc, const TB &tb, vec3 o, vec3 d) {
     const RayPre r = ray_pre(o, d);
     bool hit = false;
     for (uint32_t k = 0; k < sc.cull_n; k++) {
-        const uint32_t i = sc.cull_set[k];
-        const float4 a = sc.prims[kRecF4 * i + 0];
-        const float4 b = sc.prims[kRecF4 * i + 1];
-        const float4 c = sc.prims[kRecF4 * i + 2];
+        float4 a, b, c;
+        tb.cull_record(k, a, b, c);
         float t, b1, b2;
         if (__float_as_uint(a.w) & kPrimSphereBit)
-            hit = hit || intersect_unit_sphere(sc.instances[__float_as_uint(b.w)].to_object, r.o, d, 0.001f,
-                                               kMaxDistance, t);
+            hit = hit || intersect_unit_sphere(tb.cull_to_object(k, b), r.o, d, 0.001f, kMaxDistance, t);
         else
             hit = hit || intersect_triangle(r, v3(a.x, a.y, a.z), v3(b.x, b.y, b.z), v3(c.x, c.y, c.z), 0.001f,
                                             kMaxDistance, t, b1, b2);
@@ -236,9 +323,10 @@ __device__ __forceinline__ bool terminal_ray_culled(const DeviceScene &sc, vec3 
 
 // fresh: a path of the frame generated for this launch (bounce 0, throughput 1, radiance 0,
 // RNG `fresh_rng`; k_generate stored only its camera ray)
-template <uint32_t MAT>
-__device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const FrameParams &fp, const PathState &ps,
-                                              uint32_t p, bool fresh, uint32_t fresh_p, uint32_t fresh_seed0) {
+template <uint32_t MAT, class TB>
+__device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const TB &tb, const FrameParams &fp,
+                                              const PathState &ps, uint32_t p, bool fresh, uint32_t fresh_p,
+                                              uint32_t fresh_seed0) {
     bool push_next = false, push_shadow = false, culled = false;
     const float4 h = ld_ps(ps.hit + p);
     const vec3 ray_d = f3(ld_ps(ps.ray_d + p));
@@ -256,9 +344,9 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
     vec3 L_add = v3(0.f);
     const vec2 stale_uv = v2(__uint_as_float(misc.z), __uint_as_float(misc.w));
 
-    HitGeo hg = reconstruct(sc, h, ps.ray_o + p, fresh, ray_d, stale_uv);
-    const DevInstance &in = sc.instances[hg.inst];
-    const DevMaterial &mat = sc.materials[in.material];
+    HitGeo hg = reconstruct(sc, tb, h, ps.ray_o + p, fresh, ray_d, stale_uv);
+    const DevInstance &in = tb.instance(hg.inst);
+    const DevMaterial &mat = tb.material(in.material);
     if (mat.twosided && dot(-ray_d, hg.g.normal) < 0.f) hg.g.normal = -hg.g.normal;  // geometry.h:316-320
     const LocalGeo &geo = hg.g;
     LocalBsdf bsdf = local_bsdf(mat, geo.texcoord);
@@ -268,7 +356,7 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
     bool L_changed = fresh;  // rad is rewritten only when this hit adds emission (or was never stored)
     if (bounce == 0) {
         if (hg.emitter >= 0) {  // main.cu:88-92
-            L_add = emitter_radiance(sc.areas[hg.emitter], geo.texcoord);
+            L_add = emitter_radiance(tb.area(hg.emitter), geo.texcoord);
             L_changed = true;
         }
         const float test = rng_next(rng);                                                    // main.cu:101
@@ -290,7 +378,7 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
             if (fp.test) fp.test[fo + out] = test;
         }
     } else if (hg.emitter >= 0) {  // main.cu:171-182
-        const DevEmitter &e = sc.areas[hg.emitter];
+        const DevEmitter &e = tb.area(hg.emitter);
         vec3 Le;
         float pdf_e;
         emitter_eval_area(e, geo, f3(ld_ps(ps.ray_o + p)), Le, pdf_e);
@@ -315,7 +403,7 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
     if (alive) {
         // direct light sampling (main.cu:114-141)
         float sel_prob;
-        const DevEmitter *e = select_emitter(sc, rng_next(rng), sel_prob);
+        const DevEmitter *e = select_emitter(sc, tb, rng_next(rng), sel_prob);
         const float x0 = rng_next(rng);
         const float x1 = rng_next(rng);
         const vec3 wo = to_local(-ray_d, geo.normal);
@@ -358,7 +446,7 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
             // Terminal-ray cull: the ray's shade is the path's last (its depth check fails: bounce + 2
             // >= max_depth).  A ray the test resolves was cast and is counted, but it is not listed
             // and its path state is not stored.
-            if (fp.cull_cum && bounce + 2u >= fp.max_depth && terminal_ray_culled(sc, geo.position, nd)) {
+            if (fp.cull_cum && bounce + 2u >= fp.max_depth && terminal_ray_culled(sc, tb, geo.position, nd)) {
                 culled = true;
             } else {
                 st_ps(ps.ray_d + p, f4(nd, 0.f));
@@ -384,6 +472,12 @@ __device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const Frame
     return (push_next ? 1u : 0u) | (push_shadow ? 2u : 0u) | (nee ? 4u : 0u) | (culled ? 8u : 0u);
 }
 
+template <uint32_t MAT>
+__device__ __forceinline__ uint32_t shade_hit(const DeviceScene &sc, const FrameParams &fp, const PathState &ps,
+                                              uint32_t p, bool fresh, uint32_t fresh_p, uint32_t fresh_seed0) {
+    return shade_hit<MAT>(sc, GlobalTables{sc}, fp, ps, p, fresh, fresh_p, fresh_seed0);
+}
+
 // The culled rays of a wave's shades (bit 3 of shade_hit's flags; 0 on the lanes that shaded
 // nothing) into the running total: one atomic per wave, on its block's shard.
 __device__ __forceinline__ void count_culled(const FrameParams &fp, uint32_t flags) {
@@ -395,8 +489,10 @@ __device__ __forceinline__ void count_culled(const FrameParams &fp, uint32_t fla
 
 // Paths whose ray left the scene (__miss__default, main.cu:196-212, and the
 // env handling at main.cu:87-99 / 165-169).
-__device__ __forceinline__ void shade_miss(const DeviceScene &sc, const FrameParams &fp, const PathState &ps,
-                                           uint32_t p, bool fresh, uint32_t fresh_p, uint32_t fresh_seed0) {
+template <class TB>
+__device__ __forceinline__ void shade_miss(const DeviceScene &sc, const TB &tb, const FrameParams &fp,
+                                           const PathState &ps, uint32_t p, bool fresh, uint32_t fresh_p,
+                                           uint32_t fresh_seed0) {
     const uint32_t fresh_rng = fresh ? fresh_rng_of(fp, fresh_p, fresh_seed0) : 0u;
     const uint4 misc = fresh ? make_uint4(fresh_rng, 0u, 0u, 0u) : ld_ps(ps.misc + p);
     if ((misc.y & 0xFFFFFFu) == 0u) {
@@ -407,7 +503,7 @@ __device__ __forceinline__ void shade_miss(const DeviceScene &sc, const FramePar
             vec3 Le;
             float pdf;
             const vec3 ro = fresh ? camera_origin(sc.camera) : f3(ld_ps(ps.ray_o + p));  // fresh: not stored
-            env_eval(*sc.env, ro, f3(ld_ps(ps.ray_d + p)), Le, pdf);
+            env_eval(*tb.env(), ro, f3(ld_ps(ps.ray_d + p)), Le, pdf);
             L = L + Le;  // main.cu:185, no MIS on the camera ray
         }
         const float test = rng_next(rng);
@@ -424,12 +520,16 @@ __device__ __forceinline__ void shade_miss(const DeviceScene &sc, const FramePar
         const float4 thr4 = ld_ps(ps.thr + p);
         vec3 Le;
         float env_pdf;
-        env_eval(*sc.env, f3(ld_ps(ps.ray_o + p)), f3(ld_ps(ps.ray_d + p)), Le, env_pdf);
+        env_eval(*tb.env(), f3(ld_ps(ps.ray_o + p)), f3(ld_ps(ps.ray_d + p)), Le, env_pdf);
         const float mis = mis_weight(thr4.w, env_pdf);  // main.cu:166-167
         const vec3 env_rad = Le * (f3(thr4) * mis);
         float4 rad4 = ld_ps(ps.rad + p);
         st_ps(ps.rad + p, f4(f3(rad4) + env_rad, 0.f));  // main.cu:185
     }
+}
+__device__ __forceinline__ void shade_miss(const DeviceScene &sc, const FrameParams &fp, const PathState &ps,
+                                           uint32_t p, bool fresh, uint32_t fresh_p, uint32_t fresh_seed0) {
+    shade_miss(sc, GlobalTables{sc}, fp, ps, p, fresh, fresh_p, fresh_seed0);
 }
 
 }  // namespace
