@@ -511,6 +511,44 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
  * the first snapshot.  PUPIL_ERR_INVALID: pt NULL.  No ABI bump: detect the symbols. */
 int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape);
 int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
+/* New topology for mesh shape `shape`, in place: *mesh is a PUPIL_SHAPE_MESH with its own
+ * num_vertices, num_faces, positions, indices and optional normals / texcoords, each present or
+ * absent whatever the old mesh had.  The arrays are copied into arrays the engine owns.  Every
+ * instance of the shape shows the new mesh (a hidden one when it is shown again), and the next
+ * render, ray query, radiance call and flow pass equal, bit for bit, those of an engine created on
+ * the same scene description.  Everything that hangs off the primitive count follows: the
+ * instances' prim_offset and array pointers, the primitive -> instance table and its lookup
+ * tables (filled on the device, pt_replace.hip), the cull set, the query scratch; the whole
+ * acceleration structure is rebuilt with the builders of pupil_pt_create, as PUPIL_VERTS_REBUILD
+ * does (there is no rebuild of one BLAS inside the two-level arrays).  accel_refits + 1; bvh_prims,
+ * bvh_nodes and bvh_depth follow; build_ms = the call's time.  The shape's vertex snapshot is
+ * dropped: the next flow pass treats it as having none.
+ *   flags: 0, or PUPIL_VERTS_DEVICE = all the pointers of *mesh are device pointers, read in
+ *   place after the work enqueued so far on hip_stream (a hipStream_t, NULL = the null stream) by
+ *   an event; no vertex or index passes through the host (the index check is a reduction on the
+ *   device, 4 bytes come back).  hip_stream is ignored without it.
+ * Ordered after every render enqueued so far; frames in flight are dropped; returns once the
+ * structure is published.
+ * A failed call leaves the engine as it was (the next render equals the render before the call):
+ * everything is validated, allocated and built aside -- new shape arrays, tables, instance table
+ * and structure -- and swapped in together once the structure is complete.
+ * PUPIL_ERR_INVALID: NULL pt / mesh / positions / indices, shape out of range or a
+ * PUPIL_SHAPE_SPHERE, mesh->kind not PUPIL_SHAPE_MESH, num_faces or num_vertices 0, unknown flags,
+ * an index >= num_vertices.  PUPIL_ERR_UNSUPPORTED: an instance of the shape is emissive
+ * (emitter_offset >= 0) -- its emitter count would change and with it every later instance's
+ * emitter_offset; emissive replacement is not supported -- or a limit of the builders (2^31
+ * primitives, 2^27 flattened primitives, the 28-bit leaf links, the node limit, the traversal
+ * stacks).  PUPIL_ERR_OOM: the new arrays could not be allocated.
+ * pupil_pt_replace_info: successful calls since create and the host clock around the last one;
+ * either out pointer may be NULL.  No ABI bump: detect the symbols. */
+int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape *mesh, uint32_t flags,
+                                void *hip_stream);
+int pupil_pt_replace_info(pupil_pt *pt, uint64_t *replacements, double *last_ms);
+/* (tests) the primitive -> instance tables as the device holds them: the primitive count, the
+ * guide's shift and its entries ((num_prims - 1 >> shift) + 2), and, each unless NULL, prim_inst
+ * (num_prims words), inst_first (num_instances + 1) and inst_guide (guide_entries). */
+int pupil_debug_read_prim_tables(pupil_pt *pt, uint32_t *num_prims, uint32_t *guide_shift, uint32_t *guide_entries,
+                                 uint32_t *prim_inst, uint32_t *inst_first, uint32_t *inst_guide);
 /* replaces the area-emitter table (delta lights included), selection CDF and env emitter (after an
  * emissive instance moved, or a point, spot or directional light was moved, recoloured, added or
  * removed); rewritten in place on the engine's stream when their shapes -- the emitter count, each
@@ -1021,6 +1059,14 @@ int pupil_world_get_instance_visibility(pupil_world *w, uint32_t instance, uint3
  * area emitters (world-space triangles, areas, select probabilities) that
  * pupil_pt_update_emitters takes after pupil_pt_update_shape_vertices. */
 int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *positions, const float *normals);
+/* the world-side half of pupil_pt_replace_shape_mesh: mesh shape `shape` gets new counts and
+ * arrays (copied; normals / texcoords may be NULL), its instances keep material, transform and
+ * flags, and pupil_world_get_desc afterwards describes the scene a fresh engine is created from.
+ * PUPIL_ERR_INVALID: NULL arguments, a count of 0, shape out of range or not a mesh, an index
+ * >= num_vertices; PUPIL_ERR_UNSUPPORTED: an emissive instance shows the shape. */
+int pupil_world_set_mesh(pupil_world *w, uint32_t shape, uint32_t num_vertices, uint32_t num_faces,
+                         const float *positions, const float *normals, const float *texcoords,
+                         const uint32_t *indices);
 /* A material replaced on the host side: `material` is an index into pupil_scene_desc.materials
  * (the world flattens one material per instance, in instance order, so it is the material of
  * desc instance `material`); the next pupil_world_get_desc carries *m there, and

@@ -159,6 +159,9 @@ SIGNATURES = {
                                                   C.c_void_p]),
     "pupil_pt_snapshot_shape_vertices": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pupil_pt_clear_vertex_snapshots": (C.c_int, [C.c_void_p]),
+    "pupil_pt_replace_shape_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Shape), C.c_uint32, C.c_void_p]),
+    "pupil_pt_replace_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_debug_read_prim_tables": (C.c_int, [C.c_void_p, u32p, u32p, u32p, u32p, u32p, u32p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_pt_enable_device_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_pt_refresh_emitters": (C.c_int, [C.c_void_p]),
@@ -224,6 +227,7 @@ SIGNATURES = {
     "pupil_world_set_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
     "pupil_world_set_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
+    "pupil_world_set_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p, f32p, u32p]),
     "pupil_world_set_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
     "pupil_world_get_desc": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_world_destroy": (None, [C.c_void_p]),

@@ -20,6 +20,7 @@
 
 #include "host/emitter_weight.h"
 #include "host/pipe_schedule.h"
+#include "host/prim_tables.h"
 #include "host/scoped_buffer.h"
 #include "pt_accel.h"
 
@@ -270,6 +271,10 @@ struct pupil_pt {
     uint64_t inst_dev_updates = 0, inst_dev_moved = 0, inst_dev_skipped = 0;
     uint32_t inst_dev_launches = 0, inst_dev_syncs = 0;
     double inst_dev_ms = 0.0;
+    // meshes replaced in place (pupil_pt_replace_shape_mesh): the successful calls and the host
+    // clock around the last one
+    uint64_t replacements = 0;
+    double replace_ms = 0.0;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -959,8 +964,7 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
     std::vector<uint32_t> inst_first(insts.size() + 1);
     for (size_t i = 0; i < insts.size(); i++) inst_first[i] = insts[i].prim_offset;
     inst_first[insts.size()] = (uint32_t)prim_inst.size();
-    uint32_t guide_shift = 0;
-    while ((prim_inst.size() >> guide_shift) > 8192u) guide_shift++;
+    const uint32_t guide_shift = prim_guide_shift(prim_inst.size());
     std::vector<uint32_t> inst_guide;
     if (!prim_inst.empty()) {
         const size_t nb = ((prim_inst.size() - 1) >> guide_shift) + 1;
@@ -1447,6 +1451,177 @@ int pupil_pt_clear_vertex_snapshots(pupil_pt *pt) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
     for (ShapeDev &sd : pt->shapes) sd.prev_valid = false;
     pt->snapshots = 0;  // the flow pass reads no table; the next snapshot uploads a new one
+    return PUPIL_OK;
+}
+
+// New topology for one mesh shape (header: the contract).  Three phases.  Aside: the new shape
+// arrays, the primitive -> instance tables and a second instance table are allocated and filled
+// on the engine's stream (pt_replace.hip) while everything the engine reads stays as it is; the
+// host computes only the instances' prefix sums (host/prim_tables.h).  Build: SceneAccel::
+// replace_shape rebuilds the whole structure over the new tables and swaps it in, or leaves the
+// old one.  Swap: the engine's pointers, counts and mirrors follow, whatever was sized or indexed
+// by the old primitive count is dropped (the query slot map, the shape's vertex snapshot, the cull
+// set's scan), and the old arrays are freed -- the stream has passed every render that read them.
+int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape *mesh, uint32_t flags, void *hip_stream) {
+    if (!pt || !mesh || !mesh->positions || !mesh->indices) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (flags & ~PUPIL_VERTS_DEVICE) return fail(PUPIL_ERR_INVALID, "unknown flags");
+    if (shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "shape index out of range");
+    ShapeDev &sd = pt->shapes[shape];
+    if (sd.kind != PUPIL_SHAPE_MESH || mesh->kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
+    if (mesh->num_faces == 0 || mesh->num_vertices == 0) return fail(PUPIL_ERR_INVALID, "mesh without faces or vertices");
+    const bool device = (flags & PUPIL_VERTS_DEVICE) != 0u;
+    const size_t nv = mesh->num_vertices, nf = mesh->num_faces;
+    const uint32_t ni = (uint32_t)pt->h_insts.size();
+    std::vector<uint32_t> counts(ni);
+    bool used = false;
+    for (uint32_t i = 0; i < ni; i++) {
+        const DevInstance &d = pt->h_insts[i];
+        const bool shows = d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape;
+        if (shows && d.emitter_offset >= 0)
+            return fail(PUPIL_ERR_UNSUPPORTED, "an instance of the shape is emissive: its emitter range would change");
+        used = used || shows;
+        counts[i] = shows ? mesh->num_faces : d.kind == PUPIL_SHAPE_MESH ? pt->shapes[pt->accel.inst_shape[i]].num_faces : 1u;
+    }
+    PrimTables tab;
+    if (!prim_tables(counts.data(), ni, &tab)) return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives");
+    if (!pt->accel.two_level && tab.num_prims >= (1u << 27))
+        return fail(PUPIL_ERR_UNSUPPORTED, "flattened BVH limited to 2^27 primitives");
+    if (!device)
+        for (size_t i = 0; i < 3 * nf; i++)
+            if (mesh->indices[i] >= mesh->num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    pt->accel.counts = SceneAccel::Counts{};
+    hipStream_t s = pt->own_stream;
+    // ---- aside: nothing below is read by the engine until the swap
+    ScratchBuf<float> pos, nrm, tex;
+    ScratchBuf<uint32_t> idx, prim_inst, inst_first, inst_guide, idx_max;
+    ScratchBuf<DevInstance> insts;
+    if (pos.alloc(3 * nv) || (mesh->normals && nrm.alloc(3 * nv)) || (mesh->texcoords && tex.alloc(2 * nv)) ||
+        idx.alloc(3 * nf) || prim_inst.alloc(tab.num_prims) || inst_first.alloc(tab.inst_first.size()) ||
+        inst_guide.alloc(tab.guide_entries) || idx_max.alloc(1) || insts.alloc(ni)) {
+        (void)hipGetLastError();
+        return fail(PUPIL_ERR_OOM, "mesh replacement: allocation failed");
+    }
+    // a failure after the first enqueue: the stream passes what it holds before the buffers go
+    auto bail = [&](int rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    };
+#define REPLACE_TRY(expr)                                                                          \
+    do {                                                                                           \
+        const hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess)                                                                      \
+            return bail(fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,            \
+                             std::string(#expr) + ": " + hipGetErrorString(_e)));                  \
+    } while (0)
+    if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
+        REPLACE_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
+        REPLACE_TRY(hipStreamWaitEvent(s, pt->ev_verts, 0));
+    }
+    const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    REPLACE_TRY(hipMemcpyAsync(idx.get(), mesh->indices, sizeof(uint32_t) * 3 * nf, kind, s));
+    if (device) {  // the index check of the host path, as a reduction: 4 bytes come back
+        uint32_t largest = 0;
+        REPLACE_TRY(hipMemsetAsync(idx_max.get(), 0, sizeof(uint32_t), s));
+        launch_index_max(idx.get(), 3 * nf, idx_max.get(), s);
+        REPLACE_TRY(hipGetLastError());
+        REPLACE_TRY(hipMemcpyAsync(&largest, idx_max.get(), sizeof(largest), hipMemcpyDeviceToHost, s));
+        REPLACE_TRY(hipStreamSynchronize(s));
+        pt->accel.counts.launches++, pt->accel.counts.syncs++;
+        if (largest >= mesh->num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
+    }
+    REPLACE_TRY(hipMemcpyAsync(pos.get(), mesh->positions, sizeof(float) * 3 * nv, kind, s));
+    if (mesh->normals) REPLACE_TRY(hipMemcpyAsync(nrm.get(), mesh->normals, sizeof(float) * 3 * nv, kind, s));
+    if (mesh->texcoords) REPLACE_TRY(hipMemcpyAsync(tex.get(), mesh->texcoords, sizeof(float) * 2 * nv, kind, s));
+    REPLACE_TRY(hipMemcpyAsync(inst_first.get(), tab.inst_first.data(), sizeof(uint32_t) * tab.inst_first.size(),
+                               hipMemcpyHostToDevice, s));
+    launch_prim_tables(inst_first.get(), ni, tab.num_prims, tab.guide_shift, tab.guide_entries, prim_inst.get(),
+                       inst_guide.get(), s);
+    // the second instance table: the engine's own, then the prim offsets and the shape's pointers
+    REPLACE_TRY(hipMemcpyAsync(insts.get(), pt->d_insts, sizeof(DevInstance) * ni, hipMemcpyDeviceToDevice, s));
+    const ReplaceMeshJob job{insts.get(), ni, inst_first.get(), sd.pos, pos.get(), nrm.get(), tex.get(), idx.get()};
+    launch_patch_instances(job, s);
+    REPLACE_TRY(hipGetLastError());
+    pt->accel.counts.launches += 2;
+    std::vector<DevInstance> mirror = pt->h_insts;  // the same patch on the host mirror
+    for (uint32_t i = 0; i < ni; i++) {
+        DevInstance &d = mirror[i];
+        d.prim_offset = tab.inst_first[i];
+        if (d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape) {
+            d.positions = pos.get();
+            d.normals = nrm.get();
+            d.texcoords = tex.get();
+            d.indices = idx.get();
+        }
+    }
+    // ---- build: after the renders enqueued so far (the builders share the engine's stream with
+    // nothing of theirs, but the swap below frees what they read)
+    REPLACE_TRY(order_after_renders(pt));
+    ShapeDev fresh = sd;
+    fresh.num_vertices = mesh->num_vertices;
+    fresh.num_faces = mesh->num_faces;
+    fresh.pos = pos.get(), fresh.nrm = nrm.get(), fresh.tex = tex.get(), fresh.idx = idx.get();
+    fresh.prev = nullptr, fresh.prev_valid = false;
+    if (const int rc = pt->accel.replace_shape(shape, fresh, used, tab.num_prims, prim_inst.get(), insts.get(), mirror))
+        return bail(rc);
+#undef REPLACE_TRY
+    // ---- swap: the structure is published and the stream idle
+    pt->pipe.invalidate();  // frames in flight were traced against the old geometry
+    for (void *p : {(void *)sd.pos, (void *)sd.nrm, (void *)sd.tex, (void *)sd.idx, (void *)sd.prev, (void *)pt->d_prim_inst,
+                    (void *)pt->sc.inst_first, (void *)pt->sc.inst_guide, (void *)pt->d_insts, (void *)pt->query_slot})
+        pt->release(p);
+    for (void *p : {(void *)pos.get(), (void *)nrm.get(), (void *)tex.get(), (void *)idx.get(), (void *)prim_inst.get(),
+                    (void *)inst_first.get(), (void *)inst_guide.get(), (void *)insts.get()})
+        if (p) pt->allocs.push_back(p);
+    if (sd.prev_valid) {  // the snapshot held the old vertex count: the flow pass sees none
+        pt->snapshots--;
+        pt->flow_verts_stale = true;
+    }
+    sd = fresh;
+    (void)pos.release(), (void)nrm.release(), (void)tex.release(), (void)idx.release();
+    pt->query_slot = nullptr;  // sized by the primitive count; the next query that needs it allocates
+    pt->d_prim_inst = prim_inst.release();
+    pt->d_insts = insts.release();
+    pt->num_prims = tab.num_prims;
+    DeviceScene &sc = pt->sc;
+    sc.num_prims = tab.num_prims;
+    sc.prim_inst = pt->d_prim_inst;
+    sc.inst_first = inst_first.release();
+    sc.inst_guide = inst_guide.release();
+    sc.inst_guide_shift = tab.guide_shift;
+    sc.instances = pt->d_insts;
+    pt->totals.bvh_prims = pt->num_prims;
+    pt->accel.refits++;
+    if (const int rc = derive_cull_set(pt)) return rc;  // the rebuild moved the records
+    pt->replacements++;
+    pt->replace_ms = pt->totals.build_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+int pupil_debug_read_prim_tables(pupil_pt *pt, uint32_t *num_prims, uint32_t *guide_shift, uint32_t *guide_entries,
+                                 uint32_t *prim_inst, uint32_t *inst_first, uint32_t *inst_guide) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    const DeviceScene &sc = pt->sc;
+    const uint32_t entries = sc.num_prims ? ((sc.num_prims - 1u) >> sc.inst_guide_shift) + 2u : 2u;
+    if (num_prims) *num_prims = sc.num_prims;
+    if (guide_shift) *guide_shift = sc.inst_guide_shift;
+    if (guide_entries) *guide_entries = entries;
+    HIP_TRY(hipSetDevice(pt->device));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (prim_inst && sc.num_prims)
+        HIP_TRY(hipMemcpy(prim_inst, sc.prim_inst, sizeof(uint32_t) * sc.num_prims, hipMemcpyDeviceToHost));
+    if (inst_first)
+        HIP_TRY(hipMemcpy(inst_first, sc.inst_first, sizeof(uint32_t) * ((size_t)sc.num_instances + 1), hipMemcpyDeviceToHost));
+    if (inst_guide) HIP_TRY(hipMemcpy(inst_guide, sc.inst_guide, sizeof(uint32_t) * entries, hipMemcpyDeviceToHost));
+    return PUPIL_OK;
+}
+
+int pupil_pt_replace_info(pupil_pt *pt, uint64_t *replacements, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (replacements) *replacements = pt->replacements;
+    if (last_ms) *last_ms = pt->replace_ms;
     return PUPIL_OK;
 }
 

@@ -1163,6 +1163,30 @@ int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *p
     return PUPIL_OK;
 }
 
+int pupil_world_set_mesh(pupil_world *w, uint32_t shape, uint32_t nv, uint32_t nf, const float *positions,
+                         const float *normals, const float *texcoords, const uint32_t *indices) {
+    if (!w || !positions || !indices || nv == 0 || nf == 0) return Pupil::werr(PUPIL_ERR_INVALID, "bad mesh");
+    if (shape >= w->w.scene.shapes.size()) return Pupil::werr(PUPIL_ERR_INVALID, "shape out of range");
+    Pupil::resource::Shape &s = w->w.scene.shapes[shape];
+    if (s.kind != PUPIL_SHAPE_MESH || !s.mesh) return Pupil::werr(PUPIL_ERR_INVALID, "shape is not a mesh");
+    // an emissive instance's emitter range is its face count, and every later instance's
+    // emitter_offset follows it: pupil_pt_replace_shape_mesh refuses the same shapes
+    for (const auto &ins : w->w.scene.instances)
+        if (ins.shape == (int)shape && ins.is_emitter)
+            return Pupil::werr(PUPIL_ERR_UNSUPPORTED, "an emissive instance shows the shape");
+    for (size_t i = 0; i < 3 * (size_t)nf; i++)
+        if (indices[i] >= nv) return Pupil::werr(PUPIL_ERR_INVALID, "mesh index out of range");
+    // a new mesh object: one another shape shares keeps its own, and the instances (material,
+    // transform, flags) name the shape, not the mesh
+    auto m = std::make_shared<Pupil::resource::Mesh>();
+    m->positions.assign(positions, positions + 3 * (size_t)nv);
+    if (normals) m->normals.assign(normals, normals + 3 * (size_t)nv);
+    if (texcoords) m->texcoords.assign(texcoords, texcoords + 2 * (size_t)nv);
+    m->indices.assign(indices, indices + 3 * (size_t)nf);
+    s.mesh = m;
+    return PUPIL_OK;
+}
+
 int pupil_world_set_material(pupil_world *w, uint32_t material, const pupil_material *m) {
     if (!w || !m) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
     if (material >= desc_instance_count(w)) return Pupil::werr(PUPIL_ERR_INVALID, "material out of range");

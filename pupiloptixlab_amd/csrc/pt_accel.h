@@ -58,6 +58,16 @@ struct SceneAccel {
     // the vertices of mesh shape `shape`, shown by the instances in `changed`, were replaced;
     // rebuild: PUPIL_VERTS_REBUILD
     int update_shape(uint32_t shape, const std::vector<uint32_t> &changed, bool rebuild);
+    // Mesh shape `shape` got new topology (pupil_pt_replace_shape_mesh).  The engine has built
+    // aside, on the stream: `mesh`, the shape's new arrays and counts; the primitive -> instance
+    // table d_prim_inst of num_prims primitives; a second instance table d_insts with the new prim
+    // offsets and array pointers, and `insts`, the host mirror patched the same way.  The
+    // structure takes them as its tables and, when an instance shows the shape (`used`), is
+    // rebuilt over them as by update_shape(rebuild) and published.  On failure the old tables and
+    // the old structure stay and nothing of *insts' owner has changed; on success `insts` holds
+    // the previous mirror.
+    int replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, uint32_t num_prims, const uint32_t *d_prim_inst,
+                      DevInstance *d_insts, std::vector<DevInstance> &insts);
     // Instances moved on the device (pupil_pt_update_instances_device), in three steps whose kernel
     // launches and synchronisations do not depend on how many moved (flattened BVH, two-level world
     // mode; object mode rebuilds its TLAS through update_instances, correct and no more).

@@ -309,4 +309,37 @@ int SceneAccel::update_shape(uint32_t shape, const std::vector<uint32_t> &change
     return publish();
 }
 
+int SceneAccel::replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, uint32_t num_prims,
+                              const uint32_t *d_prim_inst, DevInstance *d_insts, std::vector<DevInstance> &insts) {
+    const Tables old_tables = t;
+    t.num_prims = num_prims;
+    t.d_prim_inst = d_prim_inst;
+    t.d_insts = d_insts;
+    t.insts->swap(insts);
+    if (!used) {  // no instance shows the shape: no structure holds it (the two-level build skips it too)
+        HIP_TRY(hipStreamSynchronize(t.stream));
+        return PUPIL_OK;
+    }
+    TwoLevelShape old_shape{};
+    if (two_level) {
+        TwoLevelShape &ts = tl_shapes[shape];
+        old_shape = ts;
+        ts.num_faces = mesh.num_faces;
+        ts.num_vertices = mesh.num_vertices;
+        ts.positions = mesh.pos;
+        ts.normals = mesh.nrm;
+        ts.texcoords = mesh.tex;
+        ts.indices = mesh.idx;  // vmax: update_shape reduces it from the new array
+    }
+    // both rebuilds build aside and swap on success: flat over t's tables, two-level over
+    // tl_shapes and a copy of *t.insts, uploaded to t.d_insts -- the second table
+    const int rc = update_shape(shape, {}, true);
+    if (rc != PUPIL_OK) {
+        t.insts->swap(insts);
+        t = old_tables;
+        if (two_level) tl_shapes[shape] = old_shape;
+    }
+    return rc;
+}
+
 }  // namespace pupil

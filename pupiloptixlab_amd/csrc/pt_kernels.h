@@ -379,6 +379,24 @@ struct MoveInstancesJob {
     uint32_t *skipped;
 };
 void launch_move_instances(const MoveInstancesJob &job, hipStream_t s);
+// A mesh replaced in place (pt_replace.hip, pupil_pt_replace_shape_mesh).
+// launch_index_max: atomicMax of the n indices into *out, which the caller has cleared.
+// launch_prim_tables: prim_inst (num_prims entries) and inst_guide (guide_entries entries) from
+// inst_first (num_instances + 1 entries), all device arrays (host/prim_tables.h: the geometry).
+// launch_patch_instances: instances[i].prim_offset = inst_first[i], and the mesh instances whose
+// positions are old_positions get the four new array pointers.
+void launch_index_max(const uint32_t *idx, size_t n, uint32_t *out, hipStream_t s);
+void launch_prim_tables(const uint32_t *inst_first, uint32_t num_instances, uint32_t num_prims, uint32_t shift,
+                        uint32_t guide_entries, uint32_t *prim_inst, uint32_t *inst_guide, hipStream_t s);
+struct ReplaceMeshJob {
+    DevInstance *instances;
+    uint32_t num_instances;
+    const uint32_t *inst_first;
+    const float *old_positions;
+    const float *positions, *normals, *texcoords;
+    const uint32_t *indices;
+};
+void launch_patch_instances(const ReplaceMeshJob &job, hipStream_t s);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

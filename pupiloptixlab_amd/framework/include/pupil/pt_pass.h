@@ -77,6 +77,15 @@ public:
     // refused.
     bool UpdateInstancesDevice(uint32_t n, const uint32_t *ids_device, const void *to_world_device,
                                const void *to_object_device, void *stream) noexcept;
+    // A mesh of new topology in place (pupil_pt_replace_shape_mesh), applied now, under the same
+    // threading rule: mesh shape `shape` gets the counts and arrays of `mesh` (host pointers, or,
+    // with `device`, device pointers read after the work enqueued so far on `stream`, a
+    // hipStream_t).  The whole acceleration structure is rebuilt; a pending UpdateShape of the
+    // shape is dropped (the world's vertices it would hand over have the old count until
+    // pupil_world_set_mesh brings the world in step) and so is the shape's vertex snapshot.
+    // Restarts accumulation at the next OnRun.  False: no scene, or the engine refused -- a sphere,
+    // a shape an emissive instance shows, an index out of range -- and then nothing has changed.
+    bool ReplaceShapeMesh(uint32_t shape, const pupil_shape &mesh, bool device = false, void *stream = nullptr) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in

@@ -376,6 +376,21 @@ bool PTPass::UpdateInstancesDevice(uint32_t n, const uint32_t *ids_device, const
     return true;
 }
 
+bool PTPass::ReplaceShapeMesh(uint32_t shape, const pupil_shape &mesh, bool device, void *stream) noexcept {
+    if (!m_engine) return false;
+    if (pupil_pt_replace_shape_mesh(m_engine, shape, &mesh, device ? (uint32_t)PUPIL_VERTS_DEVICE : 0u, stream) !=
+        PUPIL_OK) {
+        Log("%s: mesh replacement failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    {
+        std::scoped_lock lock(m_pending_mutex);
+        m_pending_shapes.erase(std::remove(m_pending_shapes.begin(), m_pending_shapes.end(), shape), m_pending_shapes.end());
+    }
+    m_dirty = true;
+    return true;
+}
+
 bool PTPass::UpdateEnvParams(float scale, const float to_world[9]) noexcept {
     if (!m_engine || !to_world) return false;
     float to_local[9];

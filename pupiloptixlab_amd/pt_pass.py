@@ -329,6 +329,93 @@ class PTPass(Pass):
             C.c_void_p(normals.data_ptr()) if normals is not None else None, flags, C.c_void_p(s.cuda_stream)))
         self.dirty = True
 
+    # ---- a mesh of new topology in place (pupil_pt_replace_shape_mesh)
+    def _replace(self, shape: int, nv: int, nf: int, ptrs, flags: int, stream):
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        mesh = abi.Shape()
+        mesh.kind = abi.SHAPE_MESH
+        mesh.num_vertices, mesh.num_faces = nv, nf
+        mesh.positions = C.cast(ptrs[0], abi.f32p)
+        mesh.normals = C.cast(ptrs[1], abi.f32p)
+        mesh.texcoords = C.cast(ptrs[2], abi.f32p)
+        mesh.indices = C.cast(ptrs[3], abi.u32p)
+        check(self._lib.pupil_pt_replace_shape_mesh(self._pt, int(shape) & 0xFFFFFFFF, C.byref(mesh), flags, stream))
+        if 0 <= int(shape) < len(self._shape_verts):
+            self._shape_verts[int(shape)] = nv
+        self._kept.discard(int(shape))  # the engine dropped the shape's vertex snapshot
+        self.dirty = True
+
+    def replace_shape(self, shape: int, positions, faces, normals=None, texcoords=None):
+        """Mesh shape `shape` replaced by a mesh of new topology, from host arrays: positions
+        (nv, 3) float32, faces (nf, 3) uint32, optional normals (nv, 3) and texcoords (nv, 2), each
+        present or not whatever the old mesh had.  Every instance of the shape shows the new mesh
+        and the engine equals one created on the updated scene (World.set_mesh keeps the world in
+        step).  The whole acceleration structure is rebuilt; the shape's vertex snapshot is
+        dropped; restarts accumulation.  Refused, with the engine untouched: spheres, shapes an
+        emissive instance shows (PUPIL_ERR_UNSUPPORTED), an index >= nv."""
+        import numpy as np
+
+        p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1))
+        f = np.ascontiguousarray(np.asarray(faces, np.uint32).reshape(-1))
+        n = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1)) if normals is not None else None
+        t = np.ascontiguousarray(np.asarray(texcoords, np.float32).reshape(-1)) if texcoords is not None else None
+        nv, nf = p.size // 3, f.size // 3
+        if p.size != 3 * nv or f.size != 3 * nf or (n is not None and n.size != 3 * nv) or \
+                (t is not None and t.size != 2 * nv):
+            raise ValueError(f"arrays do not describe a mesh of {nv} vertices and {nf} faces")
+        ptrs = [C.c_void_p(a.ctypes.data) if a is not None else None for a in (p, n, t, f)]
+        self._replace(shape, nv, nf, ptrs, 0, None)
+
+    def replace_shape_device(self, shape: int, positions, faces, normals=None, texcoords=None, stream=None):
+        """The same from device tensors on the pass's device, all contiguous: positions / normals
+        float32 with 3 per vertex, texcoords float32 with 2 per vertex, faces int32 or uint32 with
+        3 per face.  They are read in place after the work enqueued so far on `stream` (default:
+        the current stream) and copied into arrays the engine owns; no vertex or index passes
+        through the host (the index check is a reduction on the device)."""
+        torch = self._torch
+        if positions is None or faces is None:
+            raise abi.PupilError(abi.ERR_INVALID, "null argument")
+        ints = (torch.int32, getattr(torch, "uint32", torch.int32))
+        for t, kinds in ((positions, (torch.float32,)), (faces, ints), (normals, (torch.float32,)),
+                         (texcoords, (torch.float32,))):
+            if t is None:
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in kinds and t.is_contiguous()):
+                raise ValueError("replace_shape_device needs contiguous float32 (vertices) and int32 or uint32 "
+                                 "(faces) device tensors")
+            if t.device.index != self.device_index:  # the copies run device to device on the engine's GPU
+                raise ValueError(f"replace_shape_device needs tensors on {self.device}, got {t.device}")
+        nv, nf = positions.numel() // 3, faces.numel() // 3
+        if positions.numel() != 3 * nv or faces.numel() != 3 * nf or \
+                (normals is not None and normals.numel() != 3 * nv) or \
+                (texcoords is not None and texcoords.numel() != 2 * nv):
+            raise ValueError(f"tensors do not describe a mesh of {nv} vertices and {nf} faces")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        ptrs = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (positions, normals, texcoords, faces)]
+        self._replace(shape, nv, nf, ptrs, abi.VERTS_DEVICE, C.c_void_p(s.cuda_stream))
+
+    def prim_tables(self) -> dict:
+        """(tests) The device's primitive -> instance tables (pupil_debug_read_prim_tables)."""
+        import numpy as np
+
+        c = [C.c_uint32(0) for _ in range(3)]
+        check(self._lib.pupil_debug_read_prim_tables(self._pt, *[C.byref(x) for x in c], None, None, None))
+        prim_inst = np.zeros(max(1, c[0].value), np.uint32)
+        inst_first = np.zeros(len(self._to_world) + 1, np.uint32)
+        inst_guide = np.zeros(c[2].value, np.uint32)
+        check(self._lib.pupil_debug_read_prim_tables(self._pt, None, None, None, prim_inst.ctypes.data_as(abi.u32p),
+                                                     inst_first.ctypes.data_as(abi.u32p),
+                                                     inst_guide.ctypes.data_as(abi.u32p)))
+        return {"num_prims": c[0].value, "guide_shift": c[1].value, "prim_inst": prim_inst[:c[0].value],
+                "inst_first": inst_first, "inst_guide": inst_guide}
+
+    def replace_info(self) -> dict:
+        """Meshes replaced since the scene was set and the host time of the last call."""
+        n, ms = C.c_uint64(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_replace_info(self._pt, C.byref(n), C.byref(ms)))
+        return {"replacements": n.value, "last_ms": ms.value}
+
     # ---- materials and textures in place (pupil_pt_update_materials / _update_texture_device)
     def update_material(self, world, material: int):
         """Material `material` as `world` holds it now (World.set_material) goes into the engine;
