@@ -544,6 +544,13 @@ int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
 int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape *mesh, uint32_t flags,
                                 void *hip_stream);
 int pupil_pt_replace_info(pupil_pt *pt, uint64_t *replacements, double *last_ms);
+/* Shadow rays of the last render with PUPIL_STATS_COUNTERS (zeros otherwise), beside
+ * pupil_pt_counters: those that found an occluder and the node visits they took; the others took
+ * node_visits - extend_node_visits minus these.  overlap_order: 1 when the engine's any-hit rays
+ * (shadow rays, PUPIL_QUERY_ANY_HIT queries) descend the child with the longest overlap first, 0
+ * when PUPIL_SHADOW_ORDER=0 at create keeps them near to far; results do not depend on it.  Any
+ * out pointer may be NULL.  No ABI bump: detect the symbol. */
+int pupil_pt_shadow_info(pupil_pt *pt, uint64_t *occluded_rays, uint64_t *occluded_visits, uint32_t *overlap_order);
 /* (tests) the primitive -> instance tables as the device holds them: the primitive count, the
  * guide's shift and its entries ((num_prims - 1 >> shift) + 2), and, each unless NULL, prim_inst
  * (num_prims words), inst_first (num_instances + 1) and inst_guide (guide_entries). */

@@ -161,6 +161,7 @@ SIGNATURES = {
     "pupil_pt_clear_vertex_snapshots": (C.c_int, [C.c_void_p]),
     "pupil_pt_replace_shape_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Shape), C.c_uint32, C.c_void_p]),
     "pupil_pt_replace_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_pt_shadow_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p]),
     "pupil_debug_read_prim_tables": (C.c_int, [C.c_void_p, u32p, u32p, u32p, u32p, u32p, u32p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_pt_enable_device_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),

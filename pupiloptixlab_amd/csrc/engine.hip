@@ -143,6 +143,9 @@ struct pupil_pt {
     bool cull_counted = false;
     uint32_t cull_scanned = 0;  // entries of d_cull the last scan left, sorted (0: no scan holds for the records as they are)
     bool cull_last = false;  // the last counted work was a render (a ray query culls nothing)
+    // any-hit rays (shadow rays, any-hit queries) sort a node's children by overlap instead of by
+    // distance (pt_traverse.h visit4); PUPIL_SHADOW_ORDER=0: near to far, as before (A/B)
+    uint32_t any_overlap = 1;
     uint64_t primary_cum = 0;                      // host running total of camera rays
     uint32_t last_paths = 0, last_iters = 0;
     uint64_t last_primary = 0;
@@ -783,9 +786,10 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
             cx.ev0(1);
             cx.tail_slot();
             if (t.inject)  // + the new group's camera rays, dequeued first in every chunk (pixel-major)
-                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, t.nfp, 0u, t.base, interleave, nl);
+                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, t.nfp, 0u, t.base, interleave, nl,
+                                   pt->any_overlap);
             else
-                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s);
+                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, 0u, 0u, 0u, 0u, 0u, pt->any_overlap);
             cx.ev1();
         } else {
             cx.ev0(0);
@@ -1032,6 +1036,7 @@ void read_knobs(pupil_pt *pt) {
     derive_bins(pt);
     if (const char *fr = std::getenv("PUPIL_FRESH_SHADE")) pt->fresh_shade = std::atoi(fr) != 0;
     if (const char *tc = std::getenv("PUPIL_TERMINAL_CULL")) pt->cull_on = std::atoi(tc) != 0;
+    if (const char *g = std::getenv("PUPIL_SHADOW_ORDER")) pt->any_overlap = std::atoi(g) != 0 ? 1u : 0u;
     if (const char *tk = std::getenv("PUPIL_TERMINAL_CULL_K"))
         pt->cull_k = (uint32_t)std::min((int)kCullSetMax, std::max(1, std::atoi(tk)));
     if (const char *a = std::getenv("PUPIL_AHEAD")) pt->knobs.ahead_mode = std::min(2, std::max(0, std::atoi(a)));
@@ -2319,6 +2324,18 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     return PUPIL_OK;
 }
 
+int pupil_pt_shadow_info(pupil_pt *pt, uint64_t *occluded_rays, uint64_t *occluded_visits, uint32_t *overlap_order) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(pt->device));
+    if (pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
+    unsigned long long tc[32] = {};
+    if (pt->last_stats) HIP_TRY(hipMemcpy(tc, pt->trace_counters, sizeof(tc), hipMemcpyDeviceToHost));
+    if (occluded_visits) *occluded_visits = tc[24];
+    if (occluded_rays) *occluded_rays = tc[25];
+    if (overlap_order) *overlap_order = pt->any_overlap;
+    return PUPIL_OK;
+}
+
 void pupil_pt_destroy(pupil_pt *pt) { delete pt; }
 
 int pupil_pt_export_bvh4(pupil_pt *pt, uint32_t *num_nodes, void *nodes, uint32_t *num_records, float *records,
@@ -2363,7 +2380,7 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
         if (e == hipSuccess) e = hipEventRecord(pt->ev_begin, pt->own_stream);
         if (e == hipSuccess)
             launch_trace_debug(pt->sc, d_rays, d_out, n, any_hit, pt->ovf, pt->ovf_threads, pt->q.work + kWorkRays,
-                               pt->own_stream, stats ? &ts : nullptr);
+                               pt->own_stream, stats ? &ts : nullptr, pt->any_overlap);
         if (e == hipSuccess) e = hipEventRecord(pt->ev_end, pt->own_stream);
         if (e == hipSuccess) e = hipStreamSynchronize(pt->own_stream);
     }
@@ -2541,7 +2558,7 @@ int run_query(pupil_pt *pt, uint32_t n, const float4 *rays, uint32_t flags, cons
     make_rays();
     HIP_TRY(hipMemsetAsync(pt->q.work + kWorkQuery, 0, kWorkKind * sizeof(uint32_t), s));
     launch_trace_debug(pt->sc, (const float *)rays, (float *)hits, n, any ? 1 : 0, pt->ovf, pt->ovf_threads,
-                       pt->q.work + kWorkQuery, s);
+                       pt->q.work + kWorkQuery, s, nullptr, pt->any_overlap);
     if (resolved || scatter) {
         const uint32_t rec_slots = slots ? pt->accel.world_record_slots() : 1u;
         if (slots && !pt->query_slot_valid) {
@@ -2738,7 +2755,7 @@ int radiance_chunk(pupil_pt *pt, hipStream_t s, const float4 *rays, const uint32
                 HIP_TRY(hipStreamSynchronize(s));
                 if (c[0] == 0 && c[1] == 0) break;
             }
-            launch_trace_mixed(pt->sc, ps, q, pt->ovf, pt->ovf_threads, nullptr, s);
+            launch_trace_mixed(pt->sc, ps, q, pt->ovf, pt->ovf_threads, nullptr, s, 0u, 0u, 0u, 0u, 0u, pt->any_overlap);
         }
         if (!pt->shade_list)
             launch_partition(ps.mbin, np, kPartMaxBins, kPartExclusive, 0u, q.bins, q.hist, q.counts,

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(kFr
                 const Bvh4Node n = load_node4(sc, node);
                 float t[4];
                 int l[4];
-                visit4(n, r.o, r.idir, be, tmin, tmax, t, l);
+                visit4(n, r.o, r.idir, be, tmin, tmax, t, l, any);  // shadow rays: overlap order
                 if (t[0] == kInf) {
                     node = st.pop();
                 } else {

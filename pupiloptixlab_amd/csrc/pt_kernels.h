@@ -169,7 +169,8 @@ __device__ __forceinline__ uint32_t inst_of_prim(const DeviceScene &sc, uint32_t
 struct TraceStats {
     unsigned long long *counters;  // [0..1] closest-hit nodes/prims, [14..15] shadow, [2..13] diagnostics,
                                    // [16] reference shadow rays, [18] distinct node fetches,
-                                   // [20..23] queue accounting (handed, activated, retired, listed)
+                                   // [20..23] queue accounting (handed, activated, retired, listed),
+                                   // [24..25] occluded shadow rays: their node visits, their number
     // PUPIL_TRACE_TAIL diagnostics (STATS kernels only, else null): per wave of the
     // persistent launch, s_memrealtime (100 MHz) at start, when its dequeue found
     // the work list drained, at exit, and the rays it took
@@ -209,9 +210,11 @@ uint32_t shade_tables_fit(const DeviceScene &sc);
 // listed paths are at list_base + id, the next render's camera rays (generated there)
 // at ahead_base + [0, ahead_count), dequeued pixel-major when ahead_spp > 1 (as the
 // primary extend)
+// any_overlap: the any-hit lanes' child order (pt_traverse.h visit4)
 void launch_trace_mixed(const DeviceScene &sc, const PathState &ps, const Queues &q, int *ovf, uint32_t ovf_threads,
                         const TraceStats *stats, hipStream_t s, uint32_t ahead_count = 0, uint32_t list_base = 0,
-                        uint32_t ahead_base = 0, uint32_t ahead_spp = 0, uint32_t ahead_local = 0);
+                        uint32_t ahead_base = 0, uint32_t ahead_spp = 0, uint32_t ahead_local = 0,
+                        uint32_t any_overlap = 0);
 // small frames (pt_frame.hip): every path of the frame -- camera ray, bounces, shadow rays --
 // in one persistent launch (no partitions, one drain); the accumulate follows.  Flat BVH4 and
 // two-level world mode only.  ray_cum: running totals of extension [0] and shadow [1] rays.
@@ -229,7 +232,8 @@ void launch_accumulate(const FrameParams &fp, const PathState &ps, const float *
 uint32_t trace_grid_blocks();
 // stats (or null): the persistent kernels' counter variants (queue accounting, node visits)
 void launch_trace_debug(const DeviceScene &sc, const float *rays, float *out, uint32_t n, int any, int *ovf,
-                        uint32_t ovf_threads, uint32_t *work, hipStream_t s, const TraceStats *stats = nullptr);
+                        uint32_t ovf_threads, uint32_t *work, hipStream_t s, const TraceStats *stats = nullptr,
+                        uint32_t any_overlap = 0);
 // flow AOV (pt_flow.hip): the camera rays through the centres of the n local pixels as a
 // kModeRays ray list (2 float4 per ray), and the projection of their hits (launch_trace_debug's
 // 4 floats per ray) through the previous camera into flow[compact ? local pixel : y*w+x]

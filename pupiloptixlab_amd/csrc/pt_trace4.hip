@@ -111,6 +111,13 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
     int node = kSentinel, leaf = 0;
     bool found = false;
     bool any = ANY;  // this lane's ray terminates on its first hit
+    // an any-hit lane sorts its children by overlap, not by distance (pt_traverse.h visit4;
+    // TraceJob::any_overlap)
+    const bool want_overlap = job.any_overlap != 0u;
+    bool ord_overlap = ANY && want_overlap;
+    // STATS: shadow rays by outcome -- node visits of this lane's ray so far, shadow rays that found
+    // an occluder and their visits
+    uint32_t nv_ray = 0, n_found_sh = 0, nv_found_sh = 0;
     bool in_blas = false;  // TL: traversing an instance's BLAS
     uint32_t inst = 0;
     vec3 bo = v3(0.f), bi = v3(0.f);  // TL: box-test ray (object space inside a BLAS)
@@ -222,6 +229,8 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
                         leaf = node;
                         node = kSentinel;
                     }
+                    if (MODE != kModeRays) ord_overlap = any && want_overlap;
+                    if (STATS) nv_ray = 0;
                     active = true;
                 }
             }
@@ -237,6 +246,7 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
         if (STATS) {
             if (kMixed && any) nv_sh++;
             else nv++;
+            nv_ray++;
             const unsigned long long m = __ballot(true);
             if ((int)lane_id() == __ffsll((long long)m) - 1) {
                 dg[0]++;
@@ -253,10 +263,11 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
         }
         float t[4];
         int l[4];
-        if (TL) visit4(n, bo, bi, be, tmin, tmax, t, l);
-        else visit4(n, r.o, r.idir, be, tmin, tmax, t, l);
+        if (TL) visit4(n, bo, bi, be, tmin, tmax, t, l, ord_overlap);
+        else visit4(n, r.o, r.idir, be, tmin, tmax, t, l, ord_overlap);
         if (STATS) {
-            n_cullable += t_node > tmax ? 1u : 0u;
+            // (t_node is a distance only for lanes sorted near to far)
+            n_cullable += !ord_overlap && t_node > tmax ? 1u : 0u;
             n_nohit += t[0] == kInf ? 1u : 0u;
         }
         if (t[0] == kInf) {
@@ -381,6 +392,10 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
                 L.z = L.z + c.z;
                 st_ps(ps.rad + p, L);
             }
+            if (STATS && done && any && found) {
+                n_found_sh++;
+                nv_found_sh += nv_ray;
+            }
         } else if (MODE == kModeRays && done) {
             float *o = job.out + 4 * (size_t)p;
             o[0] = found ? (ANY ? 1.f : tmax) : -1.f;
@@ -395,6 +410,7 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
     if (kMixed) flush_stats<STATS>(&stats, nv_sh, npt_sh, 14);
     flush_stats<STATS>(&stats, n_unique, 0u, 18);
     flush_stats<STATS>(&stats, n_cullable, n_nohit, 8);
+    if (kMixed) flush_stats<STATS>(&stats, nv_found_sh, n_found_sh, 24);
     if (STATS && stats.wave_times && lane_id() == 0) {
         unsigned long long *w = stats.wave_times + 4ull * (blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u);
         w[0] = t_start;
@@ -501,9 +517,10 @@ static void launch_trace4(const DeviceScene &sc, const PathState &ps, const Queu
 }
 
 void launch_trace_debug(const DeviceScene &sc, const float *rays, float *out, uint32_t n, int any, int *ovf,
-                        uint32_t ovf_threads, uint32_t *work, hipStream_t s, const TraceStats *stats) {
+                        uint32_t ovf_threads, uint32_t *work, hipStream_t s, const TraceStats *stats, uint32_t any_overlap) {
     // the production kernel, fed from a ray array
-    const TraceJob job{nullptr, nullptr, n, work, sc.trace_refill, sc.trace_node_min, rays, out, 0u, 0u};
+    TraceJob job{nullptr, nullptr, n, work, sc.trace_refill, sc.trace_node_min, rays, out, 0u, 0u};
+    job.any_overlap = any ? any_overlap : 0u;
     const Queues q{};
     if (any)
         launch_trace4<kModeRays, true>(sc, PathState{}, q, job, ovf, ovf_threads, stats, s);
@@ -523,10 +540,11 @@ void launch_extend(const DeviceScene &sc, const PathState &ps, const Queues &q, 
 
 void launch_trace_mixed(const DeviceScene &sc, const PathState &ps, const Queues &q, int *ovf, uint32_t ovf_threads,
                         const TraceStats *stats, hipStream_t s, uint32_t ahead_count, uint32_t list_base,
-                        uint32_t ahead_base, uint32_t ahead_spp, uint32_t ahead_local) {
-    const TraceJob job{nullptr,       nullptr,   ahead_count,          q.work + kWorkExtend,
-                       sc.trace_refill, sc.trace_node_min, nullptr, nullptr,
-                       ahead_count ? ahead_spp : 0u, ahead_local, list_base, ahead_base};
+                        uint32_t ahead_base, uint32_t ahead_spp, uint32_t ahead_local, uint32_t any_overlap) {
+    TraceJob job{nullptr,       nullptr,   ahead_count,          q.work + kWorkExtend,
+                 sc.trace_refill, sc.trace_node_min, nullptr, nullptr,
+                 ahead_count ? ahead_spp : 0u, ahead_local, list_base, ahead_base};
+    job.any_overlap = any_overlap;
     if (ahead_count) launch_trace4<kModeMixedAhead, false>(sc, ps, q, job, ovf, ovf_threads, stats, s);
     else launch_trace4<kModeMixed, false>(sc, ps, q, job, ovf, ovf_threads, stats, s);
 }

@@ -416,6 +416,13 @@ class PTPass(Pass):
         check(self._lib.pupil_pt_replace_info(self._pt, C.byref(n), C.byref(ms)))
         return {"replacements": n.value, "last_ms": ms.value}
 
+    def shadow_info(self) -> dict:
+        """Shadow rays of the last counter render that found an occluder, the node visits they took,
+        and whether any-hit rays use the overlap child order (pupil_pt_shadow_info)."""
+        n, v, on = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        check(self._lib.pupil_pt_shadow_info(self._pt, C.byref(n), C.byref(v), C.byref(on)))
+        return {"occluded_rays": n.value, "occluded_visits": v.value, "overlap_order": bool(on.value)}
+
     # ---- materials and textures in place (pupil_pt_update_materials / _update_texture_device)
     def update_material(self, world, material: int):
         """Material `material` as `world` holds it now (World.set_material) goes into the engine;
