@@ -388,8 +388,9 @@ int pupil_pt_update_instances(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
  * estimation, and its own hidden geometry does not block the shadow ray, so it still lights
  * the scene; camera and BSDF-sampled rays never see it.
  *
- * Removing an instance is not provided: the reference's path tracer never binds
- * RenderInstanceRemove, and its SBT offsets go stale after a removal. */
+ * Instances are added and removed with pupil_pt_set_instances below, which replaces the table as
+ * a whole (the reference's path tracer never binds RenderInstanceRemove, and its SBT offsets go
+ * stale after a removal). */
 int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *ids,
                                      const float *to_world, const float *to_object,
                                      const uint32_t *visibility_mask);
@@ -544,6 +545,54 @@ int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
 int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape *mesh, uint32_t flags,
                                 void *hip_stream);
 int pupil_pt_replace_info(pupil_pt *pt, uint64_t *replacements, double *last_ms);
+/* The instance table replaced as a whole: instances added, removed, or bound to another shape or
+ * material slot of the engine, in place.  The table becomes instances[0..n); shapes, materials,
+ * emitters, camera and film stay.  shape and material index the engine's existing ones.  After
+ * the call the next render, pupil_pt_query_rays / _query_camera, pupil_pt_radiance_rays and
+ * pupil_pt_motion_vectors equal, bit for bit, those of an engine freshly created on the scene
+ * whose instance list is the new one, with the same masks applied; everything sized or indexed by
+ * the instance or primitive count follows (the primitive tables, the material bins, the cull set,
+ * the query, flow and device-move scratch).  Vertex snapshots of shapes stay.
+ * visibility_mask: n masks as in pupil_pt_update_instances_masked, or NULL: all visible.
+ * flags == 0: transforms from instances[k].to_world / to_object; to_world_device must be NULL.
+ * PUPIL_INSTANCES_DEVICE: the transforms are the n x 12 floats at to_world_device, read in place
+ * behind hip_stream (an event, as PUPIL_VERTS_DEVICE; no device-wide sync) and inverted on the
+ * device as pupil_world_get_desc inverts them; the host structs' to_world / to_object are ignored,
+ * their shape, material, flips and emitter_offset are used.  The engine's host mirror is filled
+ * from one readback of the new table.  On the flattened BVH nothing else grows with n beyond the
+ * upload of the bindings.  In the two-level modes the structure's per-instance stage then fills
+ * the instances' BLAS fields, margins and boxes in the mirror and uploads the table once more
+ * (224 bytes per instance), as pupil_pt_create does.
+ * Ordered after every render, query, radiance call and flow pass enqueued so far; frames in
+ * flight are dropped; returns once the structure is published; accel_refits + 1.
+ * Transactional: everything is validated, allocated and built aside, then swapped in.  A failed
+ * call leaves the engine untouched.
+ * Structure: the flattened BVH is built once.  Two-level world mode, when the set of mesh shapes
+ * shown by at least one instance is unchanged: only the per-instance stage runs (world records,
+ * world BLAS copies, boxes, TLAS) -- no BLAS is built.  When that set changes (a shape gains its
+ * first instance or loses its last), and in two-level object mode (PUPIL_TL_MODE=object, whose
+ * BLAS links depend on the instance count), the whole structure is built.
+ * Emissive instances: the emitter table is not touched, so the emissive instances of the new table
+ * must be the old ones in the same relative order, each with its shape, material, flips and
+ * emitter_offset, and -- unless the device-side emitter table is on
+ * (pupil_pt_enable_device_emitters) -- its transform bit for bit.  Their indices may change; with
+ * the device-side table on it is refreshed before the call returns.  Anything else (an emissive
+ * instance added, removed, reordered, rebound, or moved with the device-side table off) returns
+ * PUPIL_ERR_UNSUPPORTED before anything changes.
+ * PUPIL_ERR_INVALID: NULL pt or instances, n == 0 (as pupil_pt_create on a scene without
+ * instances), a shape, material or emitter range out of range, unknown flags, the device pointer
+ * missing or present without the flag, or not 4-byte aligned.  PUPIL_ERR_UNSUPPORTED: the
+ * builders' limits as pupil_pt_replace_shape_mesh lists them.  PUPIL_ERR_OOM: an allocation failed.
+ * pupil_pt_set_instances_info: successful calls since create; of the last one the BLAS builds it
+ * ran, whether the whole structure was built (flattened: always 1) and the host clock around it;
+ * any out pointer may be NULL.  No ABI bump: detect the symbols. */
+#define PUPIL_INSTANCES_DEVICE 1u
+int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *instances,
+                           const uint32_t *visibility_mask /* n, or NULL = all visible */,
+                           const void *to_world_device /* n x 12 floats, or NULL */, uint32_t flags,
+                           void *hip_stream);
+int pupil_pt_set_instances_info(pupil_pt *pt, uint64_t *calls, uint32_t *last_blas_builds,
+                                uint32_t *last_whole_rebuild, double *last_ms);
 /* Shadow rays of the last render with PUPIL_STATS_COUNTERS (zeros otherwise), beside
  * pupil_pt_counters: those that found an occluder and the node visits they took; the others took
  * node_visits - extend_node_visits minus these.  overlap_order: 1 when the engine's any-hit rays
@@ -1022,6 +1071,9 @@ int pupil_world_add_material(pupil_world *w, const pupil_material *m, uint32_t *
 int pupil_world_add_instance(pupil_world *w, uint32_t shape, uint32_t material, const float to_world[16],
                              uint32_t flip_normals, uint32_t flip_tex_coords, uint32_t is_emitter,
                              const pupil_texture *radiance, uint32_t *out_instance);
+/* Removes an instance; later instances shift down by one.  The description afterwards is that of
+ * a world built without the instance: emitter offsets and select probabilities included. */
+int pupil_world_remove_instance(pupil_world *w, uint32_t instance);
 int pupil_world_add_const_env(pupil_world *w, const float radiance[3]);
 /* Delta lights (PUPIL_EMITTER_POINT / _SPOT / _DIRECTIONAL above).  Both calls read only e->type
  * and the fields that type names (center and color; for a spot nrm[0], pos[0][0], pos[0][1]; for a

@@ -161,6 +161,9 @@ SIGNATURES = {
     "pupil_pt_clear_vertex_snapshots": (C.c_int, [C.c_void_p]),
     "pupil_pt_replace_shape_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Shape), C.c_uint32, C.c_void_p]),
     "pupil_pt_replace_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pupil_pt_set_instances": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Instance), u32p, C.c_void_p, C.c_uint32,
+                                         C.c_void_p]),
+    "pupil_pt_set_instances_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u32p, u32p, C.POINTER(C.c_double)]),
     "pupil_pt_shadow_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p]),
     "pupil_debug_read_prim_tables": (C.c_int, [C.c_void_p, u32p, u32p, u32p, u32p, u32p, u32p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
@@ -225,6 +228,7 @@ SIGNATURES = {
     "pupil_world_set_delta_emitter": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Emitter)]),
     "pupil_world_get_delta_emitter": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Emitter)]),
     "pupil_world_set_instance_transform": (C.c_int, [C.c_void_p, C.c_uint32, f32p]),
+    "pupil_world_remove_instance": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pupil_world_set_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
     "pupil_world_set_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
@@ -241,6 +245,9 @@ SIGNATURES = {
 
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libpupil_pt.so")
+
+
+INSTANCES_DEVICE = 1  # pupil_pt_set_instances: transforms from device memory
 
 
 class PupilError(RuntimeError):

@@ -6,7 +6,7 @@
 #include <utility>
 #include <vector>
 
-#include "pt_kernels.h"
+#include "pt_kernels.h"  // host/instance_record.h: instance_margin_values
 
 namespace pupil {
 
@@ -55,6 +55,13 @@ struct TwoLevelAccel {
     // record slot / shading record in the combined arrays, and whether the BLAS is one root leaf
     std::vector<uint32_t> shape_slots, shape_node_base, shape_rec_base, shape_attr_base;
     std::vector<uint8_t> shape_root_leaf;
+    // per shape, what the instance stage takes from the shape stage (set_two_level_instances runs
+    // it without the BLAS builders): whether the shape has a BLAS, its node count and its root
+    // link before rebasing; blas_builds: BLAS builder runs of the build that made this structure
+    std::vector<uint8_t> shape_used;
+    std::vector<uint32_t> shape_nodes;
+    std::vector<int32_t> shape_root;
+    uint32_t blas_builds = 0;
     float *d_objbox = nullptr;     // exact box of every object-space node (6 floats), scratch of the BLAS refits
     uint32_t *d_vmax = nullptr;    // update_shape_blas: the max |coordinate| reduction's result
     uint32_t root_link4 = (uint32_t)kTraverseDone;
@@ -68,23 +75,6 @@ PT_HD int rebase_link(int link, uint32_t node_base, uint32_t prim_base) {
     return make_leaf(leaf_first(link) + prim_base, leaf_count(link));
 }
 
-// The two margin terms of an instance (accel_two_level.hip instance_margin derives them), one text
-// for the host and for the kernel that moves instances on the device (pt_instances.hip): infinity
-// norms of the 3x3 parts and of the translations, in this order of operations.
-PT_HD void instance_margin_values(const float *to_world, const float *to_object, float vmax, float *margin) {
-    auto mx = [](float a, float b) { return a < b ? b : a; };  // std::max
-    float anorm = 0.f, at = 0.f, mnorm = 0.f, mt = 0.f;
-    for (int r = 0; r < 3; r++) {
-        anorm = mx(anorm, fabsf(to_object[4 * r]) + fabsf(to_object[4 * r + 1]) + fabsf(to_object[4 * r + 2]));
-        mnorm = mx(mnorm, fabsf(to_world[4 * r]) + fabsf(to_world[4 * r + 1]) + fabsf(to_world[4 * r + 2]));
-        at = mx(at, fabsf(to_object[4 * r + 3]));
-        mt = mx(mt, fabsf(to_world[4 * r + 3]));
-    }
-    const float c = 0x1p-18f;
-    margin[0] = c * anorm;
-    margin[1] = c * (anorm * (mnorm * vmax + mt) + at);
-}
-
 // Builds the BLASes, fills the two-level fields of every instance (host copy
 // `insts`, uploaded to d_insts), their world boxes and the TLAS.
 // inst_shape[i] = shape index of instance i (ignored for spheres).  Returns 0, -1 on a HIP
@@ -94,6 +84,19 @@ PT_HD void instance_margin_values(const float *to_world, const float *to_object,
 int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<uint32_t> &inst_shape,
                     std::vector<DevInstance> &insts, DevInstance *d_insts, const DevMaterial *d_mats,
                     uint32_t leaf_size, hipStream_t s, TwoLevelAccel &acc);
+// build_two_level is two stages (accel_two_level.hip): the shape stage builds the BLASes, the
+// object nodes, prims, attrs and the shape_* vectors; the instance stage the instances' fields,
+// the world records and world BLAS copies, the boxes, the braided entries, the TLAS and its level
+// order.  set_two_level_instances (world mode; pupil_pt_set_instances) runs the instance stage
+// alone for a new instance table whose mesh instances show only shapes that have a BLAS in acc:
+// `out` shares acc's shape-stage arrays and gets per-instance arrays of its own, built aside.  On
+// success the caller frees acc's per-instance arrays (free_instance_stage) and takes out; on
+// failure out is empty and acc untouched.  Returns as build_two_level, and -5 when the new table
+// does not fit world mode (the caller builds the whole structure instead).
+int set_two_level_instances(const std::vector<TwoLevelShape> &shapes, const std::vector<uint32_t> &inst_shape,
+                            std::vector<DevInstance> &insts, DevInstance *d_insts, hipStream_t s,
+                            const TwoLevelAccel &acc, TwoLevelAccel &out);
+void free_instance_stage(TwoLevelAccel &acc);
 // Recomputes the world boxes of the `changed` instances (transforms already in
 // insts / d_insts) and rebuilds the TLAS.  -3: the TLAS + BLAS depth exceeds the
 // traversal stacks (kTraceStackEntries).

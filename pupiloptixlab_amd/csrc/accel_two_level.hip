@@ -861,28 +861,13 @@ int rebuild_tlas(TwoLevelAccel &acc, std::vector<DevInstance> &insts, DevInstanc
     return hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
 }
 
-int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<uint32_t> &inst_shape,
-                    std::vector<DevInstance> &insts, DevInstance *d_insts, const DevMaterial *d_mats,
-                    uint32_t leaf_size, hipStream_t s, TwoLevelAccel &acc) {
-    const auto t0 = std::chrono::steady_clock::now();
-    acc = TwoLevelAccel{};
-    const uint32_t n = (uint32_t)insts.size();
-    const char *mode = std::getenv("PUPIL_TL_MODE");  // world (default) | object (A/B)
-    acc.world = !(mode && std::strcmp(mode, "object") == 0);
-    // braid 8 = TLAS over the nodes 8 levels below each instance root.  Config 5 with the GPU-built
-    // TLAS and GPU refits (r03, profiles/r03_tlas_braid_ab.txt): braid 6 / 7 / 8 -> 434 / 445 / 415 ms
-    // per step, instance update 1.4 / 1.5 / 1.9 ms, build 37 / 61 / 131-148 ms.  r04 (two alternating
-    // rounds, profiles/r04_config5_braid_ab.txt): braid 8 / 10 / 11 / 12 -> 402 / 392-395 / 398-400 /
-    // 397-398 ms per step, 37.1 / 35.6 / 36.5 / 36.5 node visits per ray, update 2.0 / 3.0 / 3.1 / 3.4 ms,
-    // build 138 / 277-290 / 311-321 / 333-336 ms: braid 10 is the default
-    if (const char *b = std::getenv("PUPIL_TL_BRAID")) acc.braid = (uint32_t)std::min(12, std::max(0, std::atoi(b)));
-    // BLAS per mesh shape that some instance uses
-    std::vector<uint8_t> used(shapes.size(), 0);
-    std::vector<uint32_t> shape_of(n);
-    for (uint32_t i = 0; i < n; i++) {
-        shape_of[i] = insts[i].kind == PUPIL_SHAPE_SPHERE ? 0xFFFFFFFFu : inst_shape[i];
-        if (shape_of[i] != 0xFFFFFFFFu) used[shape_of[i]] = 1;
-    }
+// The shape stage of build_two_level: a BLAS per mesh shape that some instance uses (`used`),
+// the combined object-space nodes, records and shading records, and the shape_* vectors.  Nothing
+// here depends on the instances but `reserve`, the node slots [0, max(1, instances)) that object
+// mode keeps for its TLAS in front of the BLASes.  Returns as build_two_level; on failure the
+// caller frees acc.
+int two_level_shape_stage(const std::vector<TwoLevelShape> &shapes, const std::vector<uint8_t> &used, uint32_t n,
+                          const DevMaterial *d_mats, uint32_t leaf_size, hipStream_t s, TwoLevelAccel &acc) {
     std::vector<BvhBuildOutput> blas(shapes.size());
     // prim_base: a shape's first primitive (shading records, one per primitive); rec_base: its
     // first BLAS record slot (pt_scene.h kRecF4: leaves on even slots, holes between)
@@ -920,6 +905,7 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
         double ms = 0.0;
         if (sh.num_faces) {
             const int brc = build_bvh_bounded(bin, blas[k], leaf_size, s, &ms, 2u);
+            acc.blas_builds++;
             if (brc != 0) {
                 rc = brc == -3 ? -3 : -1;
                 break;
@@ -946,10 +932,7 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
     if (!rc && (hipMalloc((void **)&acc.nodes4, sizeof(Bvh4Node) * total_nodes) != hipSuccess ||
                 hipMalloc((void **)&acc.prims, sizeof(float4) * kRecF4 * (size_t)std::max(1u, total_slots)) != hipSuccess ||
                 hipMalloc((void **)&acc.attrs, sizeof(float4) * kAttrStride * (size_t)std::max(1u, total_prims)) !=
-                    hipSuccess ||
-                hipMalloc((void **)&acc.d_boxes, sizeof(uint32_t) * 6 * (size_t)n) != hipSuccess ||
-                hipMalloc((void **)&acc.d_list, sizeof(uint32_t) * n) != hipSuccess ||
-                hipMalloc((void **)&acc.d_verts, sizeof(uint32_t) * n) != hipSuccess))
+                    hipSuccess))
         rc = -1;
     for (size_t k = 0; k < shapes.size() && !rc; k++) {
         if (!used[k]) continue;
@@ -970,15 +953,57 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
                                b.num_nodes4, node_base[k], rec_base[k]);
     }
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = -1;
+    // per shape, for the instance stage and the refits (world BLAS copies, update_shape_blas):
+    // level order, record slots, bases, node count and root link
+    acc.shape_levels.assign(shapes.size(), {});
+    acc.shape_slots.assign(shapes.size(), 0u);
+    acc.shape_root_leaf.assign(shapes.size(), 0);
+    acc.shape_nodes.assign(shapes.size(), 0u);
+    acc.shape_root.assign(shapes.size(), kTraverseDone);
+    acc.shape_used = used;
+    acc.shape_node_base = node_base;
+    acc.shape_rec_base = rec_base;
+    acc.shape_attr_base = prim_base;
+    for (size_t k = 0; k < shapes.size(); k++) {
+        acc.shape_levels[k] = blas[k].level_start;
+        acc.shape_slots[k] = used[k] && shapes[k].num_faces ? blas[k].num_records : 0u;
+        acc.shape_root_leaf[k] = (int)blas[k].root_link4 < 0 ? 1 : 0;
+        acc.shape_nodes[k] = blas[k].num_nodes4;
+        acc.shape_root[k] = (int)blas[k].root_link4;
+    }
     for (auto &b : blas) free_lbvh(b);
     if (zeros) (void)hipFree(zeros);
     if (d_ident) (void)hipFree(d_ident);
-    if (rc) {
-        free_two_level(acc);
-        return rc;
-    }
+    if (rc) return rc;
     acc.num_nodes4 = total_nodes;
     acc.num_prims = total_prims;
+    return 0;
+}
+
+// world mode: the most TLAS entries the instances braid into (the instance stage's reserve)
+static uint64_t braided_reserve(const TwoLevelAccel &acc, const std::vector<uint32_t> &shape_of) {
+    uint64_t width = 1;
+    for (uint32_t l = 0; l < acc.braid; l++) width *= 4;
+    uint64_t cap = 0;
+    for (uint32_t k : shape_of) cap += k == 0xFFFFFFFFu ? 1u : std::min<uint64_t>(width, 4ull * acc.shape_nodes[k] + 1u);
+    return cap;
+}
+
+// The instance stage of build_two_level, over a finished shape stage in acc: the two-level fields
+// of every instance (host copy `insts`, uploaded to d_insts), the per-instance arrays, the world
+// records and world BLAS copies, the boxes, the braided entries, the TLAS and its level order.
+// Every shape an instance shows has its BLAS in acc (acc.shape_used).  Returns as build_two_level;
+// on failure the caller frees what the stage allocated (free_instance_stage, or all of acc).
+int two_level_instance_stage(const std::vector<TwoLevelShape> &shapes, const std::vector<uint32_t> &shape_of,
+                             std::vector<DevInstance> &insts, DevInstance *d_insts, hipStream_t s, TwoLevelAccel &acc) {
+    const uint32_t n = (uint32_t)insts.size();
+    uint64_t slots64 = 0;
+    for (size_t k = 0; k < shapes.size(); k++) slots64 += acc.shape_slots[k];
+    if (two_level_fit(slots64, 0, 0, n, false) == TwoLevelFit::None) return -4;
+    if (hipMalloc((void **)&acc.d_boxes, sizeof(uint32_t) * 6 * (size_t)n) != hipSuccess ||
+        hipMalloc((void **)&acc.d_list, sizeof(uint32_t) * n) != hipSuccess ||
+        hipMalloc((void **)&acc.d_verts, sizeof(uint32_t) * n) != hipSuccess)
+        return -1;
     // per instance: BLAS root / record base / margin / world-record base, then the
     // world records, the world boxes and the TLAS
     std::vector<uint32_t> verts(n, 0), faces(n, 0), all(n);
@@ -988,11 +1013,7 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
     // most min(4^braid, 4 x its BLAS nodes + 1) entries (the links `braid` levels below its
     // root), a sphere one (64-bit sum: many instances must not wrap the reserve)
     if (acc.world) {
-        uint64_t width = 1;
-        for (uint32_t l = 0; l < acc.braid; l++) width *= 4;
-        uint64_t cap = 0;
-        for (uint32_t i = 0; i < n; i++)
-            cap += shape_of[i] == 0xFFFFFFFFu ? 1u : std::min<uint64_t>(width, 4ull * blas[shape_of[i]].num_nodes4 + 1u);
+        const uint64_t cap = braided_reserve(acc, shape_of);
         if (cap > kMaxNodes4) {
             std::fprintf(stderr, "[pupil] two-level: %llu braided TLAS entries exceed the node limit, object mode\n",
                          (unsigned long long)cap);
@@ -1012,17 +1033,17 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
             continue;
         }
         const uint32_t k = shape_of[i];
-        d.blas_root = shapes[k].num_faces ? rebase_link((int)blas[k].root_link4, node_base[k], rec_base[k])
+        d.blas_root = shapes[k].num_faces ? rebase_link(acc.shape_root[k], acc.shape_node_base[k], acc.shape_rec_base[k])
                                           : kTraverseDone;
-        d.attr_base = prim_base[k];
-        d.rec_base = rec_base[k];
-        d.wrec_delta = (int32_t)((int64_t)wbase - (int64_t)rec_base[k]);
-        const uint32_t slots = shapes[k].num_faces ? blas[k].num_records : 0u;
+        d.attr_base = acc.shape_attr_base[k];
+        d.rec_base = acc.shape_rec_base[k];
+        d.wrec_delta = (int32_t)((int64_t)wbase - (int64_t)acc.shape_rec_base[k]);
+        const uint32_t slots = acc.shape_slots[k];
         wbase += slots;
-        d.obj_nbase = node_base[k];
-        d.obj_ncount = blas[k].num_nodes4;
+        d.obj_nbase = acc.shape_node_base[k];
+        d.obj_ncount = acc.shape_nodes[k];
         d.wnode_base = (uint32_t)wnodes;
-        wnodes += blas[k].num_nodes4;
+        wnodes += acc.shape_nodes[k];
         verts[i] = shapes[k].num_vertices;
         faces[i] = slots;  // the BLAS record slots k_world_records copies
         instance_margin(d, shapes[k].vmax);
@@ -1049,10 +1070,8 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
     if (wbase >= (1ull << 31) ||
         hipMalloc((void **)&acc.wprims, sizeof(float4) * kRecF4 * (size_t)std::max<uint64_t>(1, wbase)) != hipSuccess ||
         hipMalloc((void **)&acc.d_faces, sizeof(uint32_t) * n) != hipSuccess ||
-        hipMemcpy(acc.d_faces, faces.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess) {
-        free_two_level(acc);
+        hipMemcpy(acc.d_faces, faces.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess)
         return -1;
-    }
     acc.num_wprims = (uint32_t)wbase;
     // the traversal addresses nodes by 32-bit offsets (kMaxNodes4): instance copies beyond
     // that take the object-space structure, whose BLASes are shared
@@ -1061,19 +1080,7 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
                      (unsigned long long)wnodes);
         to_object_mode();
     }
-    // per shape, for refits (world BLAS copies, update_shape_blas): level order, record slots, bases
     acc.inst_shape = shape_of;
-    acc.shape_levels.assign(shapes.size(), {});
-    acc.shape_slots.assign(shapes.size(), 0u);
-    acc.shape_root_leaf.assign(shapes.size(), 0);
-    acc.shape_node_base = node_base;
-    acc.shape_rec_base = rec_base;
-    acc.shape_attr_base = prim_base;
-    for (size_t k = 0; k < shapes.size(); k++) {
-        acc.shape_levels[k] = blas[k].level_start;
-        acc.shape_slots[k] = used[k] && shapes[k].num_faces ? blas[k].num_records : 0u;
-        acc.shape_root_leaf[k] = (int)blas[k].root_link4 < 0 ? 1 : 0;
-    }
     if (acc.world) {  // world BLAS copies + sphere records appended to the world records
         acc.entries.assign(n, {});
         // one leaf (2 slots: the record, then a hole) per sphere
@@ -1098,7 +1105,6 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
             (spheres && hipMemcpy(grown + kRecF4 * wbase, sph.data(), sizeof(float4) * sph.size(), hipMemcpyHostToDevice) !=
                             hipSuccess)) {
             if (grown) (void)hipFree(grown);
-            free_two_level(acc);
             return -1;
         }
         (void)hipFree(acc.wprims);
@@ -1107,12 +1113,78 @@ int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<
     }
     if (hipMemcpy(acc.d_verts, verts.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_insts, insts.data(), sizeof(DevInstance) * n, hipMemcpyHostToDevice) != hipSuccess ||
-        (trc = rebuild_tlas(acc, insts, d_insts, all, s)) != 0) {
-        free_two_level(acc);
+        (trc = rebuild_tlas(acc, insts, d_insts, all, s)) != 0)
         return trc == -3 ? -3 : -1;
+    return 0;
+}
+
+std::vector<uint32_t> two_level_shape_of(const std::vector<uint32_t> &inst_shape, const std::vector<DevInstance> &insts) {
+    std::vector<uint32_t> shape_of(insts.size());
+    for (size_t i = 0; i < insts.size(); i++)
+        shape_of[i] = insts[i].kind == PUPIL_SHAPE_SPHERE ? 0xFFFFFFFFu : inst_shape[i];
+    return shape_of;
+}
+
+int build_two_level(const std::vector<TwoLevelShape> &shapes, const std::vector<uint32_t> &inst_shape,
+                    std::vector<DevInstance> &insts, DevInstance *d_insts, const DevMaterial *d_mats,
+                    uint32_t leaf_size, hipStream_t s, TwoLevelAccel &acc) {
+    const auto t0 = std::chrono::steady_clock::now();
+    acc = TwoLevelAccel{};
+    const uint32_t n = (uint32_t)insts.size();
+    const char *mode = std::getenv("PUPIL_TL_MODE");  // world (default) | object (A/B)
+    acc.world = !(mode && std::strcmp(mode, "object") == 0);
+    // braid 8 = TLAS over the nodes 8 levels below each instance root.  Config 5 with the GPU-built
+    // TLAS and GPU refits (r03, profiles/r03_tlas_braid_ab.txt): braid 6 / 7 / 8 -> 434 / 445 / 415 ms
+    // per step, instance update 1.4 / 1.5 / 1.9 ms, build 37 / 61 / 131-148 ms.  r04 (two alternating
+    // rounds, profiles/r04_config5_braid_ab.txt): braid 8 / 10 / 11 / 12 -> 402 / 392-395 / 398-400 /
+    // 397-398 ms per step, 37.1 / 35.6 / 36.5 / 36.5 node visits per ray, update 2.0 / 3.0 / 3.1 / 3.4 ms,
+    // build 138 / 277-290 / 311-321 / 333-336 ms: braid 10 is the default
+    if (const char *b = std::getenv("PUPIL_TL_BRAID")) acc.braid = (uint32_t)std::min(12, std::max(0, std::atoi(b)));
+    // BLAS per mesh shape that some instance uses
+    const std::vector<uint32_t> shape_of = two_level_shape_of(inst_shape, insts);
+    std::vector<uint8_t> used(shapes.size(), 0);
+    for (uint32_t i = 0; i < n; i++)
+        if (shape_of[i] != 0xFFFFFFFFu) used[shape_of[i]] = 1;
+    int rc = two_level_shape_stage(shapes, used, n, d_mats, leaf_size, s, acc);
+    if (!rc) rc = two_level_instance_stage(shapes, shape_of, insts, d_insts, s, acc);
+    if (rc) {
+        free_two_level(acc);
+        return rc;
     }
     acc.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
+}
+
+int set_two_level_instances(const std::vector<TwoLevelShape> &shapes, const std::vector<uint32_t> &inst_shape,
+                            std::vector<DevInstance> &insts, DevInstance *d_insts, hipStream_t s,
+                            const TwoLevelAccel &acc, TwoLevelAccel &out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    out = acc;  // the shape stage's arrays and vectors are shared until the caller swaps
+    out.d_boxes = nullptr, out.d_list = out.d_verts = out.d_faces = nullptr;
+    out.wprims = nullptr, out.wnodes = nullptr, out.d_wbox = nullptr, out.d_tlas_order = nullptr;
+    out.num_wprims = out.num_wnodes = 0;
+    out.tlas_cap = out.tlas_nodes = out.tlas_depth = out.sah_splits = 0;
+    out.entries.clear(), out.inst_shape.clear(), out.in_tlas.clear(), out.entries_stale.clear();
+    out.tlas_level_start.clear();
+    out.root_link4 = (uint32_t)kTraverseDone;
+    out.blas_builds = 0;
+    int rc = two_level_instance_stage(shapes, two_level_shape_of(inst_shape, insts), insts, d_insts, s, out);
+    if (!rc && !out.world) rc = -5;  // the new table does not fit world mode: object mode lays its BLASes out anew
+    if (rc) {
+        free_instance_stage(out);
+        out = TwoLevelAccel{};
+        return rc;
+    }
+    out.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+void free_instance_stage(TwoLevelAccel &acc) {
+    void *p[] = {acc.d_boxes, acc.d_list, acc.d_verts, acc.wprims, acc.d_faces, acc.wnodes, acc.d_wbox, acc.d_tlas_order};
+    for (void *x : p)
+        if (x) (void)hipFree(x);
+    acc.d_boxes = nullptr, acc.d_list = acc.d_verts = acc.d_faces = nullptr;
+    acc.wprims = nullptr, acc.wnodes = nullptr, acc.d_wbox = nullptr, acc.d_tlas_order = nullptr;
 }
 
 void free_two_level(TwoLevelAccel &acc) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "host/emitter_weight.h"
+#include "host/instance_record.h"
 #include "host/pipe_schedule.h"
 #include "host/prim_tables.h"
 #include "host/scoped_buffer.h"
@@ -278,6 +279,14 @@ struct pupil_pt {
     // clock around the last one
     uint64_t replacements = 0;
     double replace_ms = 0.0;
+    // instance tables replaced as a whole (pupil_pt_set_instances): the successful calls, what the
+    // last one built and the host clock around it; the host's copies of the device-side emitter
+    // bookkeeping (d_emit_inst, d_inst_weight), which a new table re-indexes
+    uint64_t inst_sets = 0;
+    uint32_t inst_set_blas_builds = 0, inst_set_whole = 0;
+    double inst_set_ms = 0.0;
+    std::vector<uint32_t> h_emit_inst;
+    std::vector<float> h_inst_weight;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -1196,6 +1205,8 @@ int device_emitter_setup(pupil_pt *pt, const pupil_scene_desc *scene) {
     if (!emit_inst.empty())  // one entry per triangle or sphere emitter
         HIP_TRY(hipMemcpy(pt->d_emit_inst, emit_inst.data(), sizeof(uint32_t) * emit_inst.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(pt->d_inst_weight, inst_weight.data(), sizeof(float) * inst_weight.size(), hipMemcpyHostToDevice));
+    pt->h_emit_inst = emit_inst;
+    pt->h_inst_weight = inst_weight;
     return PUPIL_OK;
 }
 
@@ -1605,6 +1616,243 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     return PUPIL_OK;
 }
 
+// The instance table as a whole (header: the contract).  The phases of pupil_pt_replace_shape_mesh.
+// Aside: the bindings, a per-shape table, inst_first and the transforms go up, k_fill_instances
+// (pt_instance_set.hip) writes a second instance table, launch_prim_tables the primitive tables;
+// the host mirror is assembled by the same text (host path) or read back in one copy (device
+// path; in the two-level modes the structure's instance stage then fills the two-level fields in the
+// mirror and uploads the table again, as create does).  Build: SceneAccel::set_instances builds the structure over the new tables and swaps it
+// in, or leaves the old one.  Swap: the engine's pointers, counts and mirrors follow, and whatever
+// was sized by the old instance or primitive count is dropped and re-allocated by its next user.
+int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
+                           const void *to_world_device, uint32_t flags, void *hip_stream) {
+    if (!pt || !instances) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (flags & ~PUPIL_INSTANCES_DEVICE) return fail(PUPIL_ERR_INVALID, "unknown flags");
+    const bool device = (flags & PUPIL_INSTANCES_DEVICE) != 0u;
+    if (device != (to_world_device != nullptr))
+        return fail(PUPIL_ERR_INVALID, device ? "PUPIL_INSTANCES_DEVICE without a device pointer"
+                                              : "a device pointer without PUPIL_INSTANCES_DEVICE");
+    if ((uintptr_t)to_world_device & 3u) return fail(PUPIL_ERR_INVALID, "device pointer not 4-byte aligned");
+    if (n == 0) return fail(PUPIL_ERR_INVALID, "scene has no instances");  // as pupil_pt_create
+    const bool two_level = pt->accel.two_level;
+    const uint32_t old_n = (uint32_t)pt->h_insts.size();
+    // ---- everything that can refuse the call from the host's tables
+    std::vector<InstBinding> bind(n);
+    std::vector<uint32_t> counts(n), new_shape(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const pupil_instance &src = instances[i];
+        if (src.shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "instance shape out of range");
+        if (src.material >= pt->num_mats) return fail(PUPIL_ERR_INVALID, "instance material out of range");
+        const ShapeDev &sd = pt->shapes[src.shape];
+        counts[i] = sd.kind == PUPIL_SHAPE_SPHERE ? 1u : sd.num_faces;
+        new_shape[i] = src.shape;
+        InstBinding &b = bind[i];
+        b.shape = src.shape;
+        b.material = src.material;
+        b.flip_normals = src.flip_normals;
+        b.flip_tex_coords = src.flip_tex_coords;
+        b.emitter_offset = src.emitter_offset;
+        b.hidden = visibility_mask && (visibility_mask[i] & 0xFFu) == 0u ? 1u : 0u;
+        b.bin = material_bin(pt->h_mats[src.material].type);
+    }
+    // the emitter table stays: the emissive instances are the old ones, in their order (so every
+    // emitter range is one create checked against the table)
+    std::vector<uint32_t> old_em, new_em;
+    for (uint32_t i = 0; i < old_n; i++)
+        if (pt->h_insts[i].emitter_offset >= 0) old_em.push_back(i);
+    for (uint32_t i = 0; i < n; i++)
+        if (instances[i].emitter_offset >= 0) new_em.push_back(i);
+    if (old_em.size() != new_em.size())
+        return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances added or removed: the emitter table would change");
+    bool emitters_moved = false;
+    for (size_t k = 0; k < old_em.size(); k++) {
+        const DevInstance &o = pt->h_insts[old_em[k]];
+        const pupil_instance &c = instances[new_em[k]];
+        // the same material: its slot, or another slot of the same content
+        const bool same_material = o.material == c.material ||
+                                   std::memcmp(&pt->h_mats[o.material], &pt->h_mats[c.material], sizeof(DevMaterial)) == 0;
+        if (pt->accel.inst_shape[old_em[k]] != c.shape || !same_material || o.flip_normals != c.flip_normals ||
+            o.flip_tex_coords != c.flip_tex_coords || o.emitter_offset != c.emitter_offset)
+            return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances reordered or rebound: the emitter table would change");
+        if (!device && (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) != 0 ||
+                        std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) != 0)) {
+            if (!pt->dev_emit)
+                return fail(PUPIL_ERR_UNSUPPORTED, "an emissive instance moved: the emitter table needs the device-side mode");
+            emitters_moved = true;
+        }
+    }
+    PrimTables tab;
+    if (!prim_tables(counts.data(), n, &tab)) return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives");
+    if (!two_level && tab.num_prims >= (1u << 27))
+        return fail(PUPIL_ERR_UNSUPPORTED, "flattened BVH limited to 2^27 primitives");
+    std::vector<InstShape> shape_tab(pt->shapes.size());  // the per-shape table
+    for (size_t k = 0; k < pt->shapes.size(); k++) {
+        const ShapeDev &sd = pt->shapes[k];
+        shape_tab[k] = InstShape{sd.kind, sd.num_faces, sd.pos, sd.nrm, sd.tex, sd.idx};
+    }
+    HIP_TRY(hipSetDevice(pt->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    pt->accel.counts = SceneAccel::Counts{};
+    hipStream_t s = pt->own_stream;
+    // ---- aside: nothing below is read by the engine until the swap
+    ScratchBuf<uint32_t> prim_inst, inst_first, inst_guide, emit_inst;
+    ScratchBuf<DevInstance> insts;
+    ScratchBuf<InstBinding> d_bind;
+    ScratchBuf<InstShape> d_shapes;
+    ScratchBuf<float> xf, inst_weight;
+    const bool remap = pt->dev_emit && pt->d_inst_weight;
+    if (prim_inst.alloc(tab.num_prims) || inst_first.alloc(tab.inst_first.size()) || inst_guide.alloc(tab.guide_entries) ||
+        insts.alloc(n) || d_bind.alloc(n) || d_shapes.alloc(shape_tab.size()) || (!device && xf.alloc(24 * (size_t)n)) ||
+        (remap && (emit_inst.alloc(pt->dev_emit_count) || inst_weight.alloc(n)))) {
+        (void)hipGetLastError();
+        return fail(PUPIL_ERR_OOM, "instance table: allocation failed");
+    }
+    auto bail = [&](int rc) {  // a failure after the first enqueue: the stream passes what it holds before the buffers go
+        (void)hipStreamSynchronize(s);
+        return rc;
+    };
+#define SET_TRY(expr)                                                                              \
+    do {                                                                                           \
+        const hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess)                                                                      \
+            return bail(fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,            \
+                             std::string(#expr) + ": " + hipGetErrorString(_e)));                  \
+    } while (0)
+    std::vector<float> h_xf;  // host path: n to_world, then n to_object; outlives the copy (the build synchronises)
+    if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
+        SET_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
+        SET_TRY(hipStreamWaitEvent(s, pt->ev_verts, 0));
+    } else {
+        h_xf.resize(24 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) {
+            std::memcpy(&h_xf[12 * (size_t)i], instances[i].to_world, sizeof(float) * 12);
+            std::memcpy(&h_xf[12 * ((size_t)n + i)], instances[i].to_object, sizeof(float) * 12);
+        }
+        SET_TRY(hipMemcpyAsync(xf.get(), h_xf.data(), sizeof(float) * h_xf.size(), hipMemcpyHostToDevice, s));
+    }
+    SET_TRY(hipMemcpyAsync(d_bind.get(), bind.data(), sizeof(InstBinding) * n, hipMemcpyHostToDevice, s));
+    SET_TRY(hipMemcpyAsync(d_shapes.get(), shape_tab.data(), sizeof(InstShape) * shape_tab.size(), hipMemcpyHostToDevice, s));
+    SET_TRY(hipMemcpyAsync(inst_first.get(), tab.inst_first.data(), sizeof(uint32_t) * tab.inst_first.size(),
+                           hipMemcpyHostToDevice, s));
+    launch_prim_tables(inst_first.get(), n, tab.num_prims, tab.guide_shift, tab.guide_entries, prim_inst.get(),
+                       inst_guide.get(), s);
+    FillInstancesJob job{};
+    job.out = insts.get();
+    job.n = n;
+    job.shapes = d_shapes.get();
+    job.bindings = d_bind.get();
+    job.inst_first = inst_first.get();
+    job.to_world = device ? (const float *)to_world_device : xf.get();
+    job.to_object = device ? nullptr : xf.get() + 12 * (size_t)n;
+    launch_fill_instances(job, s);
+    SET_TRY(hipGetLastError());
+    pt->accel.counts.launches += 2;
+    std::vector<DevInstance> mirror(n);
+    if (device) {  // one contiguous readback
+        SET_TRY(hipMemcpyAsync(mirror.data(), insts.get(), sizeof(DevInstance) * n, hipMemcpyDeviceToHost, s));
+        SET_TRY(hipStreamSynchronize(s));
+        pt->accel.counts.syncs++;
+        // the table holds a hidden sphere's device copy: the mirror keeps its real inverse, the same text
+        for (DevInstance &d : mirror)
+            if (d.hidden && d.kind == PUPIL_SHAPE_SPHERE) invert_affine3x4(d.to_world, d.to_object);
+        for (size_t k = 0; k < old_em.size(); k++) {
+            const DevInstance &o = pt->h_insts[old_em[k]], &c = mirror[new_em[k]];
+            if (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) == 0 &&
+                std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) == 0)
+                continue;
+            if (!pt->dev_emit)
+                return fail(PUPIL_ERR_UNSUPPORTED, "an emissive instance moved: the emitter table needs the device-side mode");
+            emitters_moved = true;
+        }
+    } else {
+        for (uint32_t i = 0; i < n; i++)
+            fill_instance_record(mirror[i], shape_tab[bind[i].shape], bind[i], tab.inst_first[i], instances[i].to_world,
+                                 instances[i].to_object, false);
+    }
+    std::vector<uint32_t> h_emit_inst;
+    std::vector<float> h_inst_weight;
+    if (remap) {  // the emitters' instances under their new indices
+        h_emit_inst = pt->h_emit_inst;
+        h_inst_weight.assign(n, 0.f);
+        std::vector<uint32_t> to_new(old_n, 0u);
+        for (size_t k = 0; k < old_em.size(); k++) {
+            to_new[old_em[k]] = new_em[k];
+            h_inst_weight[new_em[k]] = pt->h_inst_weight[old_em[k]];
+        }
+        for (uint32_t &e : h_emit_inst) e = to_new[e];
+        if (!h_emit_inst.empty())
+            SET_TRY(hipMemcpyAsync(emit_inst.get(), h_emit_inst.data(), sizeof(uint32_t) * h_emit_inst.size(),
+                                   hipMemcpyHostToDevice, s));
+        SET_TRY(hipMemcpyAsync(inst_weight.get(), h_inst_weight.data(), sizeof(float) * n, hipMemcpyHostToDevice, s));
+    }
+    // ---- build: after the renders enqueued so far (the swap below frees what they read)
+    SET_TRY(order_after_renders(pt));
+    if (const int rc = pt->accel.set_instances(tab.num_prims, prim_inst.get(), insts.get(), mirror, new_shape, pt->shapes))
+        return bail(rc);
+#undef SET_TRY
+    // ---- swap: the structure is published and the stream idle
+    pt->pipe.invalidate();  // frames in flight were traced against the old table
+    for (void *p : {(void *)pt->d_prim_inst, (void *)pt->sc.inst_first, (void *)pt->sc.inst_guide, (void *)pt->d_insts,
+                    (void *)pt->query_slot, (void *)pt->flow_prev, (void *)pt->flow_verts, (void *)pt->d_move_stage})
+        pt->release(p);
+    pt->query_slot = nullptr;  // sized by the primitive count; the next query that needs it allocates
+    pt->flow_prev = nullptr;   // the flow scratch and the device move's staging block: by the instance count
+    pt->flow_verts = nullptr;
+    pt->flow_verts_stale = true;
+    pt->h_flow_prev.clear(), pt->h_flow_verts.clear();
+    pt->d_move_stage = nullptr;
+    pt->h_move_ids.clear(), pt->h_move_seen.clear(), pt->h_move_stage.clear();
+    if (remap) {
+        pt->release(pt->d_emit_inst);
+        pt->release(pt->d_inst_weight);
+        pt->allocs.push_back(emit_inst.get());
+        pt->allocs.push_back(inst_weight.get());
+        pt->d_emit_inst = emit_inst.release();
+        pt->d_inst_weight = inst_weight.release();
+        pt->h_emit_inst.swap(h_emit_inst);
+        pt->h_inst_weight.swap(h_inst_weight);
+    } else if (pt->d_inst_weight) {  // switched off: the next enable sizes its bookkeeping anew
+        pt->release(pt->d_inst_weight);
+        pt->release(pt->d_emit_sum);
+        pt->d_inst_weight = pt->d_emit_sum = nullptr;
+    }
+    for (void *p : {(void *)prim_inst.get(), (void *)inst_first.get(), (void *)inst_guide.get(), (void *)insts.get()})
+        pt->allocs.push_back(p);
+    pt->d_prim_inst = prim_inst.release();
+    pt->d_insts = insts.release();
+    pt->num_prims = tab.num_prims;
+    DeviceScene &sc = pt->sc;
+    sc.num_prims = tab.num_prims;
+    sc.prim_inst = pt->d_prim_inst;
+    sc.inst_first = inst_first.release();
+    sc.inst_guide = inst_guide.release();
+    sc.inst_guide_shift = tab.guide_shift;
+    sc.instances = pt->d_insts;
+    sc.num_instances = n;
+    pt->totals.bvh_prims = pt->num_prims;
+    pt->accel.refits++;
+    derive_bins(pt);
+    if (const int rc = derive_cull_set(pt)) return rc;  // the build moved the records
+    if (pt->dev_emit && !old_em.empty())
+        if (const int rc = rebuild_emitters(pt)) return rc;
+    pt->inst_sets++;
+    pt->inst_set_blas_builds = pt->accel.last_blas_builds;
+    pt->inst_set_whole = pt->accel.last_whole_rebuild;
+    pt->inst_set_ms = pt->totals.build_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PUPIL_OK;
+}
+
+int pupil_pt_set_instances_info(pupil_pt *pt, uint64_t *calls, uint32_t *last_blas_builds, uint32_t *last_whole_rebuild,
+                                double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (calls) *calls = pt->inst_sets;
+    if (last_blas_builds) *last_blas_builds = pt->inst_set_blas_builds;
+    if (last_whole_rebuild) *last_whole_rebuild = pt->inst_set_whole;
+    if (last_ms) *last_ms = pt->inst_set_ms;
+    return PUPIL_OK;
+}
+
 int pupil_debug_read_prim_tables(pupil_pt *pt, uint32_t *num_prims, uint32_t *guide_shift, uint32_t *guide_entries,
                                  uint32_t *prim_inst, uint32_t *inst_first, uint32_t *inst_guide) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
@@ -1665,6 +1913,8 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
             return fail(PUPIL_ERR_OOM, "instance staging allocation failed");
         }
         HIP_TRY(hipMemset(pt->d_move_stage, 0, sizeof(float) * pupil_pt::kMoveHeader));  // [0]: the skipped ids, a running total
+        const uint32_t so_far = (uint32_t)pt->inst_dev_skipped;  // pupil_pt_set_instances dropped an earlier block
+        if (so_far) HIP_TRY(hipMemcpy(pt->d_move_stage, &so_far, sizeof(so_far), hipMemcpyHostToDevice));
     }
     // after the work enqueued so far on the caller's stream; no device-wide sync
     HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));

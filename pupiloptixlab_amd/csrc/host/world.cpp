@@ -1113,6 +1113,21 @@ int pupil_world_add_instance(pupil_world *w, uint32_t shape, uint32_t material, 
     return PUPIL_OK;
 }
 
+int pupil_world_remove_instance(pupil_world *w, uint32_t instance) {
+    if (!w) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
+    // desc instance k = k-th scene instance with a shape (World::Build skips the others)
+    uint32_t k = 0;
+    auto &list = w->w.scene.instances;
+    for (size_t i = 0; i < list.size(); i++) {
+        if (list[i].shape < 0) continue;
+        if (k++ != instance) continue;
+        list.erase(list.begin() + (std::ptrdiff_t)i);
+        if (instance < w->visibility.size()) w->visibility.erase(w->visibility.begin() + instance);  // the masks shift too
+        return PUPIL_OK;
+    }
+    return Pupil::werr(PUPIL_ERR_INVALID, "instance out of range");
+}
+
 int pupil_world_set_instance_transform(pupil_world *w, uint32_t instance, const float to_world[16]) {
     if (!w || !to_world) return Pupil::werr(PUPIL_ERR_INVALID, "null argument");
     // desc instance k = k-th scene instance with a shape (World::Build skips the others)

@@ -68,6 +68,24 @@ struct SceneAccel {
     // the previous mirror.
     int replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, uint32_t num_prims, const uint32_t *d_prim_inst,
                       DevInstance *d_insts, std::vector<DevInstance> &insts);
+    // The instance table was replaced as a whole (pupil_pt_set_instances).  The engine has built
+    // aside, on the stream: the primitive -> instance table, a second instance table d_insts
+    // (k_fill_instances), `insts`, its host mirror, and `shape_of`, the shape of each new instance.
+    // The structure takes them as its tables, is built over them and published.  Flattened: one
+    // build, as update_shape(rebuild).  Two-level, world mode, the set of mesh shapes shown by at
+    // least one instance unchanged: the instance stage alone (set_two_level_instances) on freshly
+    // sized per-instance arrays -- no BLAS builder runs.  Two-level otherwise -- the set changed,
+    // so a BLAS is missing or left over, or object mode, whose BLASes lie behind a TLAS reserve of
+    // one node per instance and whose links move with the instance count -- the whole structure is
+    // built anew.  Both two-level paths fill the instances' two-level fields in the host mirror and
+    // upload the table again, as create does.  A shape that gains its first instance takes its
+    // arrays and vmax from `shapes` as they are now; one that loses its last is forgotten.
+    // Masks go on after the build, as a fresh engine's do after create.  On failure
+    // the old tables and structure stay; on success `insts` and `shape_of` hold the previous ones.
+    // last_blas_builds / last_whole_rebuild: what the last call ran (flattened: 0 / 1).
+    int set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, DevInstance *d_insts, std::vector<DevInstance> &insts,
+                      std::vector<uint32_t> &shape_of, const std::vector<ShapeDev> &shapes);
+    uint32_t last_blas_builds = 0, last_whole_rebuild = 0;
     // Instances moved on the device (pupil_pt_update_instances_device), in three steps whose kernel
     // launches and synchronisations do not depend on how many moved (flattened BVH, two-level world
     // mode; object mode rebuilds its TLAS through update_instances, correct and no more).

@@ -342,4 +342,102 @@ int SceneAccel::replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, u
     return rc;
 }
 
+int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, DevInstance *d_insts,
+                              std::vector<DevInstance> &insts, std::vector<uint32_t> &shape_of,
+                              const std::vector<ShapeDev> &shapes) {
+    const Tables old_tables = t;
+    const std::vector<TwoLevelShape> old_shapes = tl_shapes;
+    t.num_prims = num_prims;
+    t.d_prim_inst = d_prim_inst;
+    t.d_insts = d_insts;
+    t.insts->swap(insts);
+    inst_shape.swap(shape_of);
+    auto undo = [&](int rc) {
+        t.insts->swap(insts);
+        inst_shape.swap(shape_of);
+        t = old_tables;
+        tl_shapes = old_shapes;
+        return rc;
+    };
+    if (d_moved) {  // sized by the instance count; the next refit allocates
+        (void)hipFree(d_moved);
+        d_moved = nullptr;
+    }
+    last_blas_builds = 0;
+    last_whole_rebuild = 1;
+    if (!two_level) {
+        const int rc = update_flat({}, false, true);
+        return rc != PUPIL_OK ? undo(rc) : rc;
+    }
+    const uint32_t n = (uint32_t)t.insts->size();
+    std::vector<uint8_t> used(tl_shapes.size(), 0);
+    for (uint32_t i = 0; i < n; i++)
+        if ((*t.insts)[i].kind != PUPIL_SHAPE_SPHERE) used[inst_shape[i]] = 1;
+    // built with every instance shown, as create builds; the masks follow
+    std::vector<DevInstance> copy = *t.insts;
+    std::vector<uint32_t> hidden;
+    for (uint32_t i = 0; i < n; i++)
+        if (copy[i].hidden) {
+            hidden.push_back(i);
+            copy[i].hidden = 0u;
+        }
+    TwoLevelAccel ntl{};
+    int rc = -5;
+    const bool stage_only = tl.world && used == tl.shape_used;
+    if (stage_only) rc = set_two_level_instances(tl_shapes, inst_shape, copy, t.d_insts, t.stream, tl, ntl);
+    if (rc == 0) {
+        last_whole_rebuild = 0;
+    } else if (rc == -5) {
+        // A shape without a BLAS in tl gains its first instance: its arrays as they are now, and vmax
+        // as at create.  While no instance showed it, a vertex update or a replacement left no
+        // trace here, so nothing an earlier use left in tl_shapes[k] may be trusted.
+        for (size_t k = 0; k < tl_shapes.size(); k++) {
+            TwoLevelShape &ts = tl_shapes[k];
+            if (!used[k] || (k < tl.shape_used.size() && tl.shape_used[k])) continue;
+            ts = TwoLevelShape{};
+            ts.num_faces = shapes[k].num_faces;
+            ts.num_vertices = shapes[k].num_vertices;
+            ts.positions = shapes[k].pos;
+            ts.normals = shapes[k].nrm;
+            ts.texcoords = shapes[k].tex;
+            ts.indices = shapes[k].idx;
+            if (shape_abs_max(tl, ts, &ts.vmax, t.stream) != 0) return undo(fail(PUPIL_ERR_HIP, "vertex reduction failed"));
+        }
+        copy = *t.insts;
+        for (uint32_t id : hidden) copy[id].hidden = 0u;
+        rc = build_two_level(tl_shapes, inst_shape, copy, t.d_insts, t.d_mats, leaf_size, t.stream, ntl);
+    }
+    auto drop = [&]() {
+        if (last_whole_rebuild) free_two_level(ntl);
+        else free_instance_stage(ntl);
+    };
+    if (rc == 0 && !hidden.empty()) {  // the masks, as pupil_pt_update_instances_masked puts them on a fresh engine
+        std::vector<DevInstance> staged;
+        staged.reserve(hidden.size());
+        for (uint32_t id : hidden) {
+            copy[id].hidden = 1u;
+            staged.push_back(device_instance(copy[id]));
+            if (hipMemcpyAsync(t.d_insts + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice, t.stream) != hipSuccess)
+                rc = -1;
+        }
+        if (rc == 0)
+            rc = rebuild_tlas(ntl, copy, t.d_insts, hidden, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")));
+        if (rc != 0) (void)hipStreamSynchronize(t.stream);  // `staged` outlives its copies
+    }
+    rc = rc != 0 ? builder_error(rc, true, "two-level acceleration rebuild failed") : node_limit(nodes4_of(ntl));
+    if (rc != PUPIL_OK) {  // the old structure stays
+        drop();
+        return undo(rc);
+    }
+    last_blas_builds = ntl.blas_builds;
+    for (size_t k = 0; k < tl_shapes.size(); k++)  // a shape that lost its last instance is forgotten
+        if (!used[k]) tl_shapes[k] = TwoLevelShape{};
+    if (last_whole_rebuild) free_two_level(tl);
+    else free_instance_stage(tl);
+    tl = ntl;
+    *t.insts = copy;
+    ms = tl.build_ms;
+    return publish();
+}
+
 }  // namespace pupil

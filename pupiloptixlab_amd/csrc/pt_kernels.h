@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_scene.h"
+#include "host/instance_record.h"
 
 namespace pupil {
 
@@ -401,6 +402,20 @@ struct ReplaceMeshJob {
     const uint32_t *indices;
 };
 void launch_patch_instances(const ReplaceMeshJob &job, hipStream_t s);
+// A new instance table (pt_instance_set.hip, pupil_pt_set_instances): out[i] for i < n from
+// shapes[bindings[i].shape], bindings[i], inst_first[i] and the transform at to_world + 12 i;
+// to_object: the inverses beside them, or null: each is computed (pt_invert.h).  A hidden sphere
+// gets the NaN to_object of its device copy.  All device arrays; every bindings[i].shape indexes
+// shapes.
+struct FillInstancesJob {
+    DevInstance *out;
+    uint32_t n;
+    const InstShape *shapes;
+    const InstBinding *bindings;
+    const uint32_t *inst_first;
+    const float *to_world, *to_object;
+};
+void launch_fill_instances(const FillInstancesJob &job, hipStream_t s);
 void launch_debug_math(const float *x, const float *y2, float *out, uint32_t n, hipStream_t s);
 // device emitter selection for n random numbers: area index, -1 env, -2 none
 void launch_debug_select(const DeviceScene &sc, const float *p, int *out, uint32_t n, hipStream_t s);

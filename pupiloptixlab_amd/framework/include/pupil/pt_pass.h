@@ -86,6 +86,17 @@ public:
     // Restarts accumulation at the next OnRun.  False: no scene, or the engine refused -- a sphere,
     // a shape an emissive instance shows, an index out of range -- and then nothing has changed.
     bool ReplaceShapeMesh(uint32_t shape, const pupil_shape &mesh, bool device = false, void *stream = nullptr) noexcept;
+    // The instance table as a whole (pupil_pt_set_instances), applied now, under the same threading
+    // rule: the engine's instances become instances[0..n) -- added, removed, or bound to another
+    // shape or material slot of the scene the pass was set on -- with visibility_mask (n masks, or
+    // null: all visible).  Transforms from the structs, or, with to_world_device, from n x 12
+    // device floats read after the work enqueued so far on `stream` (a hipStream_t) and inverted
+    // on the device.  Emissive instances must stay the old ones, in order.  The pass's own
+    // per-instance state follows: recorded instance updates are dropped, and the flow of the next
+    // ComputeMotionVectors covers the camera only.  Restarts accumulation at the next OnRun.
+    // False: no scene, or the engine refused (pupil_last_error()) -- then nothing has changed.
+    bool SetInstances(uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask = nullptr,
+                      const void *to_world_device = nullptr, void *stream = nullptr) noexcept;
     // Screen-space flow since the previous OnRun (pupil_pt_motion_vectors: the camera of that
     // OnRun, and the instance transforms it rendered with if this OnRun moved any), written to
     // the "motion vector" buffer (float2 per pixel, allocated on first use; this rank's tiles in

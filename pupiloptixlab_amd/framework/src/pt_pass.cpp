@@ -391,6 +391,27 @@ bool PTPass::ReplaceShapeMesh(uint32_t shape, const pupil_shape &mesh, bool devi
     return true;
 }
 
+bool PTPass::SetInstances(uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
+                          const void *to_world_device, void *stream) noexcept {
+    if (!m_engine) return false;
+    if (pupil_pt_set_instances(m_engine, n, instances, visibility_mask, to_world_device,
+                               to_world_device ? (uint32_t)PUPIL_INSTANCES_DEVICE : 0u, stream) != PUPIL_OK) {
+        Log("%s: instance table update failed: %s", name.c_str(), pupil_last_error());
+        return false;
+    }
+    {
+        std::scoped_lock lock(m_pending_mutex);  // recorded moves name instances of the old table
+        m_pending.clear();
+    }
+    m_to_world.assign(12 * (size_t)n, 0.f);
+    pupil_pt_get_instance_transforms(m_engine, 0, n, m_to_world.data(), nullptr);
+    m_prev_to_world.clear();
+    m_instances_moved = false;
+    m_device_moved = false;
+    m_dirty = true;
+    return true;
+}
+
 bool PTPass::UpdateEnvParams(float scale, const float to_world[9]) noexcept {
     if (!m_engine || !to_world) return false;
     float to_local[9];

@@ -114,6 +114,22 @@ class Pass:
         raise NotImplementedError
 
 
+def _material_key(m) -> bytes:
+    """What a material holds, without addresses: the struct with its texel pointers cleared, then
+    the texels of its bitmap textures.  Equal for equal materials of separately built worlds."""
+    import hashlib
+
+    c = abi.Material()
+    C.memmove(C.byref(c), C.byref(m), C.sizeof(abi.Material))
+    h = hashlib.sha1()
+    for k in range(4):
+        t = c.tex[k]
+        if t.rgba and t.width and t.height:
+            h.update(C.string_at(t.rgba, 16 * t.width * t.height))
+        t.rgba = None
+    return bytes(c) + h.digest()
+
+
 class PTPass(Pass):
     def __init__(self, name: str = "Path Tracing", device: int = 0, events: Events | None = None):
         super().__init__(name)
@@ -137,6 +153,8 @@ class PTPass(Pass):
         self.tile = (32, 0, 1)  # tile_size, rank, world
         self._world = None  # the World the scene came from: its sensor is re-read when dirty
         self._shape_verts = []  # vertices of each shape of the scene in the engine (update_shape_device)
+        self._mat_slots = {}  # the engine's material slots by content (set_instances), and each slot's content
+        self._mat_keys = []
         self._pending = {}  # RenderInstanceUpdate events since the last render: id(world) -> (world, instances)
         # what motion_vectors() compares against: the camera in the engine and those of the last
         # two renders as (sample_to_camera, camera_to_world), the instance transforms now in the
@@ -410,6 +428,84 @@ class PTPass(Pass):
         return {"num_prims": c[0].value, "guide_shift": c[1].value, "prim_inst": prim_inst[:c[0].value],
                 "inst_first": inst_first, "inst_guide": inst_guide}
 
+    # ---- the instance table as a whole (pupil_pt_set_instances)
+    def _index_materials(self):
+        """content -> the first engine slot that holds it"""
+        self._mat_slots = {}
+        for i, key in enumerate(self._mat_keys):
+            self._mat_slots.setdefault(key, i)
+
+    def _bindings(self, world):
+        """the world's instances as the engine binds them: a copy of desc().instances whose material
+        ids name the ENGINE's material slots (a world's desc carries one material per instance; the
+        engine keeps those it was created with), and the world's visibility masks"""
+        import numpy as np
+
+        desc = world.desc()
+        n = desc.num_instances
+        arr = (abi.Instance * max(1, n))()
+        for i in range(n):
+            C.memmove(C.byref(arr[i]), C.byref(desc.instances[i]), C.sizeof(abi.Instance))
+            key = _material_key(desc.materials[desc.instances[i].material])
+            if key not in self._mat_slots:
+                raise ValueError(f"instance {i} uses a material the engine does not hold: materials are not added "
+                                 "to a live engine")
+            arr[i].material = self._mat_slots[key]
+        vis = np.array([world.instance_visibility(i) for i in range(n)], np.uint32)
+        return n, arr, vis
+
+    def _after_set_instances(self, world):
+        """what the pass itself keeps per instance"""
+        self._world = world
+        self._pending = {}
+        import numpy as np
+
+        self._to_world = np.zeros((world.desc().num_instances, 12), np.float32)  # sizes instance_transforms()
+        self._to_world = self.instance_transforms()[0]
+        self._prev_to_world = None
+        self._moved = False
+        self.dirty = True
+
+    def set_instances(self, world):
+        """The engine's instance table becomes the world's (pupil_pt_set_instances, host path):
+        instances added with World.add_instance, removed with World.remove_instance, or bound to
+        another shape or material of the scene the engine was created on, with the world's
+        visibility masks.  Shapes, materials and emitters stay: emissive instances must be the old
+        ones, in order (PUPIL_ERR_UNSUPPORTED otherwise).  Restarts accumulation."""
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        n, arr, vis = self._bindings(world)
+        check(self._lib.pupil_pt_set_instances(self._pt, n, arr, vis.ctypes.data_as(abi.u32p), None, 0, None))
+        self._after_set_instances(world)
+
+    def set_instances_device(self, world, to_world, stream=None):
+        """As set_instances, with the transforms from `to_world`, an (n, 12) or (n, 3, 4) float32
+        CUDA tensor read in place after the work enqueued so far on `stream` (default: the current
+        stream) and inverted on the device; shapes, materials, flips and masks from the world."""
+        torch = self._torch
+        if not self._pt:
+            raise abi.PupilError(abi.ERR_INVALID, "no scene set")
+        n, arr, vis = self._bindings(world)
+        if not (isinstance(to_world, torch.Tensor) and to_world.is_cuda and to_world.dtype == torch.float32 and
+                to_world.is_contiguous()):
+            raise ValueError("set_instances_device needs a contiguous float32 device tensor")
+        if to_world.device.index != self.device_index:
+            raise ValueError(f"set_instances_device needs a tensor on {self.device}, got {to_world.device}")
+        if to_world.numel() != 12 * n:
+            raise ValueError(f"set_instances_device needs 12 floats for each of the world's {n} instances")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
+        check(self._lib.pupil_pt_set_instances(self._pt, n, arr, vis.ctypes.data_as(abi.u32p),
+                                               C.c_void_p(to_world.data_ptr()), abi.INSTANCES_DEVICE,
+                                               C.c_void_p(s.cuda_stream)))
+        self._after_set_instances(world)
+
+    def set_instances_info(self) -> dict:
+        """Instance tables set since the scene was set; of the last one the BLAS builds it ran,
+        whether the whole structure was built, and its host time."""
+        n, b, w, ms = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_set_instances_info(self._pt, C.byref(n), C.byref(b), C.byref(w), C.byref(ms)))
+        return {"calls": n.value, "last_blas_builds": b.value, "last_whole_rebuild": w.value, "last_ms": ms.value}
+
     def replace_info(self) -> dict:
         """Meshes replaced since the scene was set and the host time of the last call."""
         n, ms = C.c_uint64(0), C.c_double(0.0)
@@ -447,6 +543,10 @@ class PTPass(Pass):
             C.memmove(C.byref(mats[k]), C.byref(desc.materials[i]), C.sizeof(abi.Material))
         idv = np.array(ids, np.uint32)
         check(self._lib.pupil_pt_update_materials(self._pt, len(ids), idv.ctypes.data_as(C.POINTER(C.c_uint32)), mats))
+        for k, i in enumerate(ids):  # set_instances binds materials by what the slots hold now
+            if i < len(self._mat_keys):
+                self._mat_keys[i] = _material_key(mats[k])
+        self._index_materials()
         self.mark_dirty()
 
     def update_texture_device(self, material: int, slot: int, tensor, stream=None):
@@ -709,6 +809,10 @@ class PTPass(Pass):
         check(self._lib.pupil_pt_create(C.byref(desc), self.device_index, C.byref(self._pt)))
         self.width, self.height = desc.width, desc.height
         self._shape_verts = [desc.shapes[i].num_vertices for i in range(desc.num_shapes)]
+        # the engine's material slots by content, for set_instances (the first slot of equal ones)
+        self._mat_slots = {}
+        self._mat_keys = [_material_key(desc.materials[i]) for i in range(desc.num_materials)]
+        self._index_materials()
         self.scene_max_depth = desc.max_depth
         self._max_depth = desc.max_depth
         self._accumulate = True

@@ -221,6 +221,13 @@ class World:
         self._desc = None
         return out.value
 
+    def remove_instance(self, instance: int):
+        """Remove instance `instance` (index into desc().instances); later instances shift down by
+        one, their visibility masks with them.  The next desc() is that of a world built without
+        it; PTPass.set_instances hands the new table to the engine."""
+        check(self._lib.pupil_world_remove_instance(self._h, int(instance)))
+        self._desc = None
+
     def set_instance_transform(self, instance: int, to_world):
         """Move instance `instance` (index into desc().instances); the next desc()
         carries the new matrices and area emitters (world/world.cpp:45-54)."""
