@@ -67,12 +67,8 @@ vec3 pixel_average(const pupil_texture &t) {
 }
 
 // device scratch of one call, freed on every return path (pupil_debug_partition)
-struct HipScratchAlloc {
-    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
-    static void free(void *p) { (void)hipFree(p); }
-};
 template <typename T>
-using ScratchBuf = ScopedBuffer<T, HipScratchAlloc>;
+using ScratchBuf = ScopedBuffer<T, HipDevice>;
 
 // material bin of a material type (0 is the miss bin, 8 holds every unknown type)
 uint32_t material_bin(uint32_t type) { return type >= 1u && type <= 7u ? type : 8u; }
@@ -101,7 +97,6 @@ struct pupil_pt {
     bool fresh_shade = true;
     bool fresh() const { return fresh_shade && shade_list; }
     uint32_t width = 0, height = 0, max_depth = 1;
-    uint32_t num_prims = 0;
     // Pipelined frames (render_pipelined, PUPIL_PIPE): the path state is a ring of K slots of one
     // batch each, and consecutive renders that continue each other keep up to K frames in
     // flight.  The schedule, its knobs and its state: host/pipe_schedule.h
@@ -166,9 +161,12 @@ struct pupil_pt {
     unsigned long long *tail_buf = nullptr;
     uint32_t tail_waves = 0, tail_launches = 0;
     pupil_pt_counters totals{};
-    // scene tables kept for dynamic updates (pupil_pt_update_instance / _update_emitters)
-    std::vector<DevInstance> h_insts;
-    DevInstance *d_insts = nullptr;
+    // the instance table, its host mirror and the primitive -> instance tables: their one owner
+    // (host/scene_tables.h), and the two names most readers use
+    EngineTables tables;
+    std::vector<DevInstance> &h_insts() { return tables.cur().mirror; }
+    const std::vector<DevInstance> &h_insts() const { return tables.cur().mirror; }
+    DevInstance *d_insts() const { return tables.cur().insts.get(); }
     DevMaterial *d_mats = nullptr;
     uint32_t num_mats = 0;
     // material updates (pupil_pt_update_materials / _update_texture_device): the host mirror of
@@ -178,7 +176,6 @@ struct pupil_pt {
     std::vector<DevMaterial> h_mats;
     uint64_t mat_updates = 0;
     double mat_ms = 0.0;
-    uint32_t *d_prim_inst = nullptr;
     DevEmitter *d_areas = nullptr, *d_env = nullptr;
     float *d_cdf = nullptr;
     uint32_t *d_guide = nullptr;
@@ -591,6 +588,13 @@ hipError_t order_after_renders(pupil_pt *pt) {
     return e == hipSuccess ? hipStreamWaitEvent(pt->own_stream, pt->ev_sync, 0) : e;
 }
 
+// the engine's own stream waits for the work enqueued so far on the caller's stream, whose device
+// memory a call is about to read; no device-wide sync
+hipError_t order_after_caller(pupil_pt *pt, void *hip_stream) {
+    hipError_t e = hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream);
+    return e == hipSuccess ? hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0) : e;
+}
+
 // Local pixel list of a rank: tiles t with t % world == rank, row-major tile
 // order, row-major pixels inside a tile (clipped at the image border).
 
@@ -930,12 +934,11 @@ int convert_materials(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<D
     return PUPIL_OK;
 }
 
-// instances, the primitive -> instance table and the shading's lookup tables over it, uploaded
-// with the materials
+// The scene's instances, validated, as the first generation of the tables -- staged and adopted
+// as an update's are (host/scene_tables.h), the records by fill_instance_record -- and the
+// materials.
 int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector<DevMaterial> &mats) {
-    std::vector<DevInstance> &insts = pt->h_insts;
-    insts.resize(scene->num_instances);
-    std::vector<uint32_t> prim_inst;
+    const uint32_t n = scene->num_instances;
     // an instance's emitter range lies within the triangle and sphere emitters: the delta lights
     // behind them belong to no primitive
     uint32_t true_areas = 0;
@@ -944,67 +947,37 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
             const uint32_t t = scene->area_emitters[e].type;
             true_areas += t >= PUPIL_EMITTER_POINT && t <= PUPIL_EMITTER_DIRECTIONAL ? 0u : 1u;
         }
-    for (uint32_t i = 0; i < scene->num_instances; i++) {
+    std::vector<uint32_t> counts(n);
+    for (uint32_t i = 0; i < n; i++) {
         const pupil_instance &src = scene->instances[i];
         if (src.shape >= scene->num_shapes) return fail(PUPIL_ERR_INVALID, "instance shape out of range");
         if (src.material >= mats.size()) return fail(PUPIL_ERR_INVALID, "instance material out of range");
         const pupil_shape &sh = scene->shapes[src.shape];
-        DevInstance &d = insts[i];
-        std::memset(&d, 0, sizeof(d));
-        std::memcpy(d.to_world, src.to_world, sizeof(d.to_world));
-        std::memcpy(d.to_object, src.to_object, sizeof(d.to_object));
-        d.kind = sh.kind;
-        d.material = src.material;
-        d.prim_offset = (uint32_t)prim_inst.size();
-        d.emitter_offset = src.emitter_offset;
-        d.flip_normals = src.flip_normals;
-        d.flip_tex_coords = src.flip_tex_coords;
-        d.bin = material_bin(mats[src.material].type);
-        d.blas_root = kTraverseDone;
-        d.positions = pt->shapes[src.shape].pos;
-        d.normals = pt->shapes[src.shape].nrm;
-        d.texcoords = pt->shapes[src.shape].tex;
-        d.indices = pt->shapes[src.shape].idx;
-        const uint32_t nprim = sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
-        if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + nprim > true_areas)
+        counts[i] = sh.kind == PUPIL_SHAPE_SPHERE ? 1u : sh.num_faces;
+        if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + counts[i] > true_areas)
             return fail(PUPIL_ERR_INVALID, "emitter offset out of range");
-        prim_inst.insert(prim_inst.end(), nprim, i);
     }
-    pt->num_prims = (uint32_t)prim_inst.size();
-    if (prim_inst.size() >= (1ull << 31)) return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives");
-    // the shading's prim -> instance lookup (pt_kernels.h inst_of_prim): instance starts and a
-    // guide table of at most ~8 K entries over the prim ids
-    std::vector<uint32_t> inst_first(insts.size() + 1);
-    for (size_t i = 0; i < insts.size(); i++) inst_first[i] = insts[i].prim_offset;
-    inst_first[insts.size()] = (uint32_t)prim_inst.size();
-    const uint32_t guide_shift = prim_guide_shift(prim_inst.size());
-    std::vector<uint32_t> inst_guide;
-    if (!prim_inst.empty()) {
-        const size_t nb = ((prim_inst.size() - 1) >> guide_shift) + 1;
-        inst_guide.resize(nb + 1);
-        for (size_t k = 0; k <= nb; k++)
-            inst_guide[k] = prim_inst[std::min(k << guide_shift, prim_inst.size() - 1)];
-    } else {
-        inst_guide.assign(2, 0u);
-    }
-    uint32_t *d_inst_first = nullptr, *d_inst_guide = nullptr;
-    if (pt->upload(&pt->d_insts, insts.data(), insts.size()) || pt->upload(&pt->d_mats, mats.data(), mats.size()) ||
-        pt->upload(&pt->d_prim_inst, prim_inst.data(), prim_inst.size()) ||
-        pt->upload(&d_inst_first, inst_first.data(), inst_first.size()) ||
-        pt->upload(&d_inst_guide, inst_guide.data(), inst_guide.size()))
-        return fail(PUPIL_ERR_OOM, "scene upload failed");
+    if (pt->upload(&pt->d_mats, mats.data(), mats.size())) return fail(PUPIL_ERR_OOM, "scene upload failed");
     pt->num_mats = (uint32_t)mats.size();
     pt->h_mats = mats;
-    DeviceScene &sc = pt->sc;
-    sc.num_prims = pt->num_prims;
-    sc.prim_inst = pt->d_prim_inst;
-    sc.inst_first = d_inst_first;
-    sc.inst_guide = d_inst_guide;
-    sc.inst_guide_shift = guide_shift;
-    sc.instances = pt->d_insts;
-    sc.materials = pt->d_mats;
-    sc.num_instances = (uint32_t)insts.size();
-    sc.num_materials = (uint32_t)mats.size();
+    pt->sc.materials = pt->d_mats;
+    pt->sc.num_materials = (uint32_t)mats.size();
+    hipStream_t s = pt->own_stream;
+    EngineTables::Generation gen;
+    // the flattened BVH's limit: SceneAccel::build, which chooses the mode
+    if (const int rc = EngineTables::stage(counts.data(), n, false, s, gen)) return drained(s, rc);
+    for (uint32_t i = 0; i < n; i++) {
+        const pupil_instance &src = scene->instances[i];
+        const ShapeDev &sd = pt->shapes[src.shape];
+        const InstShape shape{scene->shapes[src.shape].kind, counts[i], sd.pos, sd.nrm, sd.tex, sd.idx};
+        const InstBinding bind{src.shape,          src.material, src.flip_normals, src.flip_tex_coords,
+                               src.emitter_offset, 0u,           material_bin(mats[src.material].type)};
+        fill_instance_record(gen.mirror[i], shape, bind, gen.first[i], src.to_world, src.to_object, false);
+    }
+    HIP_TRY_DRAINED(s, hipGetLastError());
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(gen.insts.get(), gen.mirror.data(), sizeof(DevInstance) * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
     return PUPIL_OK;
 }
 
@@ -1017,7 +990,7 @@ void derive_bins(pupil_pt *pt) {
     const bool was_list = pt->shade_list;
     const uint32_t was_single = sc.single_bin;
     uint32_t bins = 0;
-    for (const DevInstance &d : pt->h_insts) bins |= 1u << d.bin;
+    for (const DevInstance &d : pt->h_insts()) bins |= 1u << d.bin;
     pt->shade_list = (bins & (bins - 1u)) == 0u;
     if (const char *sl = std::getenv("PUPIL_SHADE_LIST")) {
         if (std::strcmp(sl, "bins") == 0) pt->shade_list = false;
@@ -1093,6 +1066,37 @@ int alloc_workspace(pupil_pt *pt) {
     return PUPIL_OK;
 }
 
+// Drops what a change of the records or of the tables has outdated; its next user scans or
+// allocates anew.  Always (the records moved): the cull set's scan and the content of the query
+// slot map, which name record slots.  tables (the swap of an update that resized them): the slot
+// map itself, sized by the primitive count, and the vertex snapshot of the shape that was
+// `replaced`, sized by its old vertex count -- the flow pass sees none.  instances: the instance
+// count changed too, which sized the flow scratch and the device move's staging block.
+void drop_stale(pupil_pt *pt, bool tables = false, bool instances = false, ShapeDev *replaced = nullptr) {
+    pt->cull_scanned = 0;
+    pt->query_slot_valid = false;
+    if (!tables) return;
+    pt->release(pt->query_slot);
+    pt->query_slot = nullptr;
+    if (replaced) {
+        pt->release(replaced->prev);
+        replaced->prev = nullptr;
+        if (replaced->prev_valid) {
+            pt->snapshots--;
+            pt->flow_verts_stale = true;
+        }
+        replaced->prev_valid = false;
+    }
+    if (!instances) return;
+    for (void *p : {(void *)pt->flow_prev, (void *)pt->flow_verts, (void *)pt->d_move_stage}) pt->release(p);
+    pt->flow_prev = nullptr;
+    pt->flow_verts = nullptr;
+    pt->flow_verts_stale = true;
+    pt->h_flow_prev.clear(), pt->h_flow_verts.clear();
+    pt->d_move_stage = nullptr;
+    pt->h_move_ids.clear(), pt->h_move_seen.clear(), pt->h_move_stage.clear();
+}
+
 // ------------------------------------------------------------------ terminal-ray cull set
 // DeviceScene::cull_set from the structure and the tables as they are now: the record slots of
 // every primitive of an instance that carries emitters, found by a scan of the traversal's own
@@ -1114,12 +1118,11 @@ int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
     DeviceScene &sc = pt->sc;
     sc.cull_set = pt->d_cull + 1;
     sc.cull_n = 0;
-    if (records_changed) pt->cull_scanned = 0;
-    if (records_changed) pt->query_slot_valid = false;  // a rebuild moves the records the map names
+    if (records_changed) drop_stale(pt);
     if (!pt->cull_on || sc.has_env || !sc.prims || (sc.two_level && !sc.tl_world)) return PUPIL_OK;
     uint64_t emissive = 0;  // primitives: a mesh instance's faces, a sphere
-    for (size_t i = 0; i < pt->h_insts.size(); i++) {
-        const DevInstance &d = pt->h_insts[i];
+    for (size_t i = 0; i < pt->h_insts().size(); i++) {
+        const DevInstance &d = pt->h_insts()[i];
         if (d.emitter_offset < 0) continue;
         emissive += d.kind == PUPIL_SHAPE_MESH ? pt->shapes[pt->accel.inst_shape[i]].num_faces : 1u;
     }
@@ -1130,7 +1133,7 @@ int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
     }
     uint32_t found[1 + kCullSetMax] = {};
     HIP_TRY(hipMemsetAsync(pt->d_cull, 0, sizeof(found), pt->own_stream));
-    launch_cull_scan(sc.prims, pt->accel.world_record_slots(), pt->d_insts, (uint32_t)pt->h_insts.size(), pt->d_cull,
+    launch_cull_scan(sc.prims, pt->accel.world_record_slots(), pt->d_insts(), (uint32_t)pt->h_insts().size(), pt->d_cull,
                      kCullSetMax, pt->own_stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(found, pt->d_cull, sizeof(found), hipMemcpyDeviceToHost, pt->own_stream));
@@ -1153,7 +1156,7 @@ int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std
                           std::vector<float> &inst_weight) {
     // ne: the triangle and sphere emitters, which the ranges must cover; the delta lights behind
     // them (the rebuild leaves them as they are) must be the engine's, type for type
-    const uint32_t ni = (uint32_t)pt->h_insts.size(), ne = pt->num_true_areas;
+    const uint32_t ni = (uint32_t)pt->h_insts().size(), ne = pt->num_true_areas;
     if (scene->num_instances != ni) return fail(PUPIL_ERR_INVALID, "the scene's instance count is not the engine's");
     if (scene->num_area_emitters != pt->sc.num_areas)
         return fail(PUPIL_ERR_INVALID, "the scene's area emitter count is not the engine's");
@@ -1169,7 +1172,7 @@ int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std
     inst_weight.assign(ni, 0.f);
     uint32_t next = 0;  // emitter ranges follow each other in instance order (World::Build)
     for (uint32_t i = 0; i < ni; i++) {
-        const DevInstance &d = pt->h_insts[i];
+        const DevInstance &d = pt->h_insts()[i];
         if (scene->instances[i].emitter_offset != d.emitter_offset)
             return fail(PUPIL_ERR_INVALID, "an instance's emitter_offset is not the engine's");
         if (d.emitter_offset < 0) continue;
@@ -1222,7 +1225,7 @@ int rebuild_emitters(pupil_pt *pt) {
     job.count = pt->num_true_areas;
     job.total = pt->sc.num_areas;
     job.emitter_num = pt->sc.num_areas + (pt->sc.has_env ? 1u : 0u);
-    job.instances = pt->d_insts;
+    job.instances = pt->d_insts();
     job.emit_inst = pt->d_emit_inst;
     job.inst_weight = pt->d_inst_weight;
     job.weight = pt->d_emit_weight;
@@ -1235,7 +1238,7 @@ int rebuild_emitters(pupil_pt *pt) {
     pt->accel.counts.launches += job.count ? (job.guide ? 5u : 4u) : 0u;
     pt->accel.counts.syncs++;
     pt->emit_refreshes++;
-    pt->emit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->emit_ms = ms_since(t0);
     return derive_cull_set(pt, false);
 }
 
@@ -1298,10 +1301,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     if (!rc) rc = convert_materials(pt, scene, mats);
     if (!rc) rc = upload_tables(pt, scene, mats);
     if (!rc) rc = upload_emitters(pt, scene);
-    if (!rc)
-        rc = pt->accel.build({pt->own_stream, pt->num_prims, pt->d_prim_inst, pt->d_insts, pt->d_mats, &pt->h_insts,
-                              &pt->sc, &pt->totals},
-                             scene, pt->shapes);
+    if (!rc) rc = pt->accel.build({pt->own_stream, &pt->tables, pt->d_mats, &pt->sc, &pt->totals}, scene, pt->shapes);
     if (!rc) read_knobs(pt);
     if (!rc) rc = alloc_workspace(pt);
     if (!rc) rc = pt->accel.publish();
@@ -1310,7 +1310,6 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
         delete pt;
         return rc;
     }
-    pt->totals.bvh_prims = pt->num_prims;
     pt->totals.build_ms = pt->accel.ms;
     *out = pt;
     return PUPIL_OK;
@@ -1350,7 +1349,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     if (!pt || (n && (!ids || (!to_world && !visibility_mask) || !to_world != !to_object)))
         return fail(PUPIL_ERR_INVALID, "null argument");
     for (uint32_t k = 0; k < n; k++)
-        if (ids[k] >= pt->h_insts.size()) return fail(PUPIL_ERR_INVALID, "instance index out of range");
+        if (ids[k] >= pt->h_insts().size()) return fail(PUPIL_ERR_INVALID, "instance index out of range");
     if (n == 0) return PUPIL_OK;
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
@@ -1360,7 +1359,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     bool emitters_moved = false;  // device-side emitter table: a transform of an emissive instance
     for (uint32_t k = 0; k < n; k++) {
         const uint32_t id = ids[k];
-        DevInstance &d = pt->h_insts[id];
+        DevInstance &d = pt->h_insts()[id];
         if (to_world) {
             emitters_moved = emitters_moved || d.emitter_offset >= 0;
             std::memcpy(d.to_world, to_world + 12 * (size_t)k, sizeof(d.to_world));
@@ -1375,8 +1374,8 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     std::vector<DevInstance> staged;
     staged.reserve(changed.size());
     for (uint32_t id : changed) {
-        staged.push_back(device_instance(pt->h_insts[id]));
-        HIP_TRY(hipMemcpyAsync(pt->d_insts + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
+        staged.push_back(device_instance(pt->h_insts()[id]));
+        HIP_TRY(hipMemcpyAsync(pt->d_insts() + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
                                pt->own_stream));
     }
     pt->accel.refits++;  // once the tables have changed, before the structure follows: a failed update counts
@@ -1401,10 +1400,10 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     const bool device = (flags & PUPIL_VERTS_DEVICE) != 0u, rebuild = (flags & PUPIL_VERTS_REBUILD) != 0u;
     std::vector<uint32_t> changed;
     bool emissive = false;
-    for (uint32_t i = 0; i < (uint32_t)pt->h_insts.size(); i++)
-        if (pt->accel.inst_shape[i] == shape && pt->h_insts[i].kind == PUPIL_SHAPE_MESH) {
+    for (uint32_t i = 0; i < (uint32_t)pt->h_insts().size(); i++)
+        if (pt->accel.inst_shape[i] == shape && pt->h_insts()[i].kind == PUPIL_SHAPE_MESH) {
             changed.push_back(i);
-            emissive = emissive || pt->h_insts[i].emitter_offset >= 0;
+            emissive = emissive || pt->h_insts()[i].emitter_offset >= 0;
         }
     if (device && emissive && !pt->dev_emit)
         return fail(PUPIL_ERR_UNSUPPORTED, "device vertices of an emissive shape: the emitter table needs the host path");
@@ -1413,10 +1412,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     HIP_TRY(order_after_renders(pt));  // no render may still read the old vertices
     pt->pipe.invalidate();          // frames in flight were traced against the old geometry
     const size_t bytes = sizeof(float) * 3 * (size_t)sd.num_vertices;
-    if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
-        HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
-        HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
-    }
+    if (device) HIP_TRY(order_after_caller(pt, hip_stream));
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     HIP_TRY(hipMemcpyAsync(sd.pos, positions, bytes, kind, pt->own_stream));
     if (normals) HIP_TRY(hipMemcpyAsync(sd.nrm, normals, bytes, kind, pt->own_stream));
@@ -1427,7 +1423,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
         HIP_TRY(hipStreamSynchronize(pt->own_stream));
     } else {
         if (const int rc = pt->accel.update_shape(shape, changed, rebuild)) return rc;
-        pt->totals.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        pt->totals.build_ms = ms_since(t0);
     }
     pt->accel.refits++;  // only once the structure has followed: a failed update does not count
     if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
@@ -1470,14 +1466,13 @@ int pupil_pt_clear_vertex_snapshots(pupil_pt *pt) {
     return PUPIL_OK;
 }
 
-// New topology for one mesh shape (header: the contract).  Three phases.  Aside: the new shape
-// arrays, the primitive -> instance tables and a second instance table are allocated and filled
-// on the engine's stream (pt_replace.hip) while everything the engine reads stays as it is; the
-// host computes only the instances' prefix sums (host/prim_tables.h).  Build: SceneAccel::
-// replace_shape rebuilds the whole structure over the new tables and swaps it in, or leaves the
-// old one.  Swap: the engine's pointers, counts and mirrors follow, whatever was sized or indexed
-// by the old primitive count is dropped (the query slot map, the shape's vertex snapshot, the cull
-// set's scan), and the old arrays are freed -- the stream has passed every render that read them.
+// New topology for one mesh shape (header: the contract).  Three phases.  Aside: a generation of
+// the tables is staged (host/scene_tables.h) and the new shape arrays and its instance table are
+// filled on the engine's stream (pt_replace.hip) while everything the engine reads stays as it
+// is.  Build: SceneAccel::replace_shape rebuilds the whole structure over the staged tables and
+// swaps it in, or leaves the old one.  Swap: the staged generation is adopted -- the old arrays
+// are freed, the stream has passed every render that read them -- and whatever was sized or
+// indexed by the old primitive count is dropped (drop_stale).
 int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape *mesh, uint32_t flags, void *hip_stream) {
     if (!pt || !mesh || !mesh->positions || !mesh->indices) return fail(PUPIL_ERR_INVALID, "null argument");
     if (flags & ~PUPIL_VERTS_DEVICE) return fail(PUPIL_ERR_INVALID, "unknown flags");
@@ -1487,21 +1482,17 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     if (mesh->num_faces == 0 || mesh->num_vertices == 0) return fail(PUPIL_ERR_INVALID, "mesh without faces or vertices");
     const bool device = (flags & PUPIL_VERTS_DEVICE) != 0u;
     const size_t nv = mesh->num_vertices, nf = mesh->num_faces;
-    const uint32_t ni = (uint32_t)pt->h_insts.size();
+    const uint32_t ni = (uint32_t)pt->h_insts().size();
     std::vector<uint32_t> counts(ni);
     bool used = false;
     for (uint32_t i = 0; i < ni; i++) {
-        const DevInstance &d = pt->h_insts[i];
+        const DevInstance &d = pt->h_insts()[i];
         const bool shows = d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape;
         if (shows && d.emitter_offset >= 0)
             return fail(PUPIL_ERR_UNSUPPORTED, "an instance of the shape is emissive: its emitter range would change");
         used = used || shows;
         counts[i] = shows ? mesh->num_faces : d.kind == PUPIL_SHAPE_MESH ? pt->shapes[pt->accel.inst_shape[i]].num_faces : 1u;
     }
-    PrimTables tab;
-    if (!prim_tables(counts.data(), ni, &tab)) return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives");
-    if (!pt->accel.two_level && tab.num_prims >= (1u << 27))
-        return fail(PUPIL_ERR_UNSUPPORTED, "flattened BVH limited to 2^27 primitives");
     if (!device)
         for (size_t i = 0; i < 3 * nf; i++)
             if (mesh->indices[i] >= mesh->num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
@@ -1509,61 +1500,41 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     const auto t0 = std::chrono::steady_clock::now();
     pt->accel.counts = SceneAccel::Counts{};
     hipStream_t s = pt->own_stream;
-    // ---- aside: nothing below is read by the engine until the swap
+    // ---- aside: nothing below is read by the engine until the swap.  The tables first: their
+    // limits refuse the call before anything is allocated; from there a failure lets the stream pass
+    EngineTables::Generation gen;
+    if (const int rc = EngineTables::stage(counts.data(), ni, !pt->accel.two_level, s, gen)) return drained(s, rc);
     ScratchBuf<float> pos, nrm, tex;
-    ScratchBuf<uint32_t> idx, prim_inst, inst_first, inst_guide, idx_max;
-    ScratchBuf<DevInstance> insts;
+    ScratchBuf<uint32_t> idx, idx_max;
     if (pos.alloc(3 * nv) || (mesh->normals && nrm.alloc(3 * nv)) || (mesh->texcoords && tex.alloc(2 * nv)) ||
-        idx.alloc(3 * nf) || prim_inst.alloc(tab.num_prims) || inst_first.alloc(tab.inst_first.size()) ||
-        inst_guide.alloc(tab.guide_entries) || idx_max.alloc(1) || insts.alloc(ni)) {
-        (void)hipGetLastError();
-        return fail(PUPIL_ERR_OOM, "mesh replacement: allocation failed");
-    }
-    // a failure after the first enqueue: the stream passes what it holds before the buffers go
-    auto bail = [&](int rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    };
-#define REPLACE_TRY(expr)                                                                          \
-    do {                                                                                           \
-        const hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess)                                                                      \
-            return bail(fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,            \
-                             std::string(#expr) + ": " + hipGetErrorString(_e)));                  \
-    } while (0)
-    if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
-        REPLACE_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
-        REPLACE_TRY(hipStreamWaitEvent(s, pt->ev_verts, 0));
-    }
+        idx.alloc(3 * nf) || idx_max.alloc(1))
+        return drained(s, fail(PUPIL_ERR_OOM, "mesh replacement: allocation failed"));
+    if (device) HIP_TRY_DRAINED(s, order_after_caller(pt, hip_stream));
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    REPLACE_TRY(hipMemcpyAsync(idx.get(), mesh->indices, sizeof(uint32_t) * 3 * nf, kind, s));
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(idx.get(), mesh->indices, sizeof(uint32_t) * 3 * nf, kind, s));
     if (device) {  // the index check of the host path, as a reduction: 4 bytes come back
         uint32_t largest = 0;
-        REPLACE_TRY(hipMemsetAsync(idx_max.get(), 0, sizeof(uint32_t), s));
+        HIP_TRY_DRAINED(s, hipMemsetAsync(idx_max.get(), 0, sizeof(uint32_t), s));
         launch_index_max(idx.get(), 3 * nf, idx_max.get(), s);
-        REPLACE_TRY(hipGetLastError());
-        REPLACE_TRY(hipMemcpyAsync(&largest, idx_max.get(), sizeof(largest), hipMemcpyDeviceToHost, s));
-        REPLACE_TRY(hipStreamSynchronize(s));
+        HIP_TRY_DRAINED(s, hipGetLastError());
+        HIP_TRY_DRAINED(s, hipMemcpyAsync(&largest, idx_max.get(), sizeof(largest), hipMemcpyDeviceToHost, s));
+        HIP_TRY_DRAINED(s, hipStreamSynchronize(s));
         pt->accel.counts.launches++, pt->accel.counts.syncs++;
         if (largest >= mesh->num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
     }
-    REPLACE_TRY(hipMemcpyAsync(pos.get(), mesh->positions, sizeof(float) * 3 * nv, kind, s));
-    if (mesh->normals) REPLACE_TRY(hipMemcpyAsync(nrm.get(), mesh->normals, sizeof(float) * 3 * nv, kind, s));
-    if (mesh->texcoords) REPLACE_TRY(hipMemcpyAsync(tex.get(), mesh->texcoords, sizeof(float) * 2 * nv, kind, s));
-    REPLACE_TRY(hipMemcpyAsync(inst_first.get(), tab.inst_first.data(), sizeof(uint32_t) * tab.inst_first.size(),
-                               hipMemcpyHostToDevice, s));
-    launch_prim_tables(inst_first.get(), ni, tab.num_prims, tab.guide_shift, tab.guide_entries, prim_inst.get(),
-                       inst_guide.get(), s);
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(pos.get(), mesh->positions, sizeof(float) * 3 * nv, kind, s));
+    if (mesh->normals) HIP_TRY_DRAINED(s, hipMemcpyAsync(nrm.get(), mesh->normals, sizeof(float) * 3 * nv, kind, s));
+    if (mesh->texcoords) HIP_TRY_DRAINED(s, hipMemcpyAsync(tex.get(), mesh->texcoords, sizeof(float) * 2 * nv, kind, s));
     // the second instance table: the engine's own, then the prim offsets and the shape's pointers
-    REPLACE_TRY(hipMemcpyAsync(insts.get(), pt->d_insts, sizeof(DevInstance) * ni, hipMemcpyDeviceToDevice, s));
-    const ReplaceMeshJob job{insts.get(), ni, inst_first.get(), sd.pos, pos.get(), nrm.get(), tex.get(), idx.get()};
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(gen.insts.get(), pt->d_insts(), sizeof(DevInstance) * ni, hipMemcpyDeviceToDevice, s));
+    const ReplaceMeshJob job{gen.insts.get(), ni, gen.inst_first.get(), sd.pos, pos.get(), nrm.get(), tex.get(), idx.get()};
     launch_patch_instances(job, s);
-    REPLACE_TRY(hipGetLastError());
-    pt->accel.counts.launches += 2;
-    std::vector<DevInstance> mirror = pt->h_insts;  // the same patch on the host mirror
+    HIP_TRY_DRAINED(s, hipGetLastError());
+    pt->accel.counts.launches += 2;  // with the tables' fill
+    gen.mirror = pt->h_insts();  // the same patch on the host mirror
     for (uint32_t i = 0; i < ni; i++) {
-        DevInstance &d = mirror[i];
-        d.prim_offset = tab.inst_first[i];
+        DevInstance &d = gen.mirror[i];
+        d.prim_offset = gen.first[i];
         if (d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape) {
             d.positions = pos.get();
             d.normals = nrm.get();
@@ -1573,46 +1544,25 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     }
     // ---- build: after the renders enqueued so far (the builders share the engine's stream with
     // nothing of theirs, but the swap below frees what they read)
-    REPLACE_TRY(order_after_renders(pt));
+    HIP_TRY_DRAINED(s, order_after_renders(pt));
     ShapeDev fresh = sd;
     fresh.num_vertices = mesh->num_vertices;
     fresh.num_faces = mesh->num_faces;
     fresh.pos = pos.get(), fresh.nrm = nrm.get(), fresh.tex = tex.get(), fresh.idx = idx.get();
     fresh.prev = nullptr, fresh.prev_valid = false;
-    if (const int rc = pt->accel.replace_shape(shape, fresh, used, tab.num_prims, prim_inst.get(), insts.get(), mirror))
-        return bail(rc);
-#undef REPLACE_TRY
+    if (const int rc = pt->accel.replace_shape(shape, fresh, used, gen)) return drained(s, rc);
     // ---- swap: the structure is published and the stream idle
     pt->pipe.invalidate();  // frames in flight were traced against the old geometry
-    for (void *p : {(void *)sd.pos, (void *)sd.nrm, (void *)sd.tex, (void *)sd.idx, (void *)sd.prev, (void *)pt->d_prim_inst,
-                    (void *)pt->sc.inst_first, (void *)pt->sc.inst_guide, (void *)pt->d_insts, (void *)pt->query_slot})
-        pt->release(p);
-    for (void *p : {(void *)pos.get(), (void *)nrm.get(), (void *)tex.get(), (void *)idx.get(), (void *)prim_inst.get(),
-                    (void *)inst_first.get(), (void *)inst_guide.get(), (void *)insts.get()})
+    drop_stale(pt, true, false, &sd);
+    for (void *p : {(void *)sd.pos, (void *)sd.nrm, (void *)sd.tex, (void *)sd.idx}) pt->release(p);
+    for (void *p : {(void *)pos.release(), (void *)nrm.release(), (void *)tex.release(), (void *)idx.release()})
         if (p) pt->allocs.push_back(p);
-    if (sd.prev_valid) {  // the snapshot held the old vertex count: the flow pass sees none
-        pt->snapshots--;
-        pt->flow_verts_stale = true;
-    }
     sd = fresh;
-    (void)pos.release(), (void)nrm.release(), (void)tex.release(), (void)idx.release();
-    pt->query_slot = nullptr;  // sized by the primitive count; the next query that needs it allocates
-    pt->d_prim_inst = prim_inst.release();
-    pt->d_insts = insts.release();
-    pt->num_prims = tab.num_prims;
-    DeviceScene &sc = pt->sc;
-    sc.num_prims = tab.num_prims;
-    sc.prim_inst = pt->d_prim_inst;
-    sc.inst_first = inst_first.release();
-    sc.inst_guide = inst_guide.release();
-    sc.inst_guide_shift = tab.guide_shift;
-    sc.instances = pt->d_insts;
-    pt->totals.bvh_prims = pt->num_prims;
+    pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
     pt->accel.refits++;
     if (const int rc = derive_cull_set(pt)) return rc;  // the rebuild moved the records
     pt->replacements++;
-    pt->replace_ms = pt->totals.build_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->replace_ms = pt->totals.build_ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -1621,9 +1571,10 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
 // (pt_instance_set.hip) writes a second instance table, launch_prim_tables the primitive tables;
 // the host mirror is assembled by the same text (host path) or read back in one copy (device
 // path; in the two-level modes the structure's instance stage then fills the two-level fields in the
-// mirror and uploads the table again, as create does).  Build: SceneAccel::set_instances builds the structure over the new tables and swaps it
-// in, or leaves the old one.  Swap: the engine's pointers, counts and mirrors follow, and whatever
-// was sized by the old instance or primitive count is dropped and re-allocated by its next user.
+// mirror and uploads the table again, as create does).  Build: SceneAccel::set_instances builds the
+// structure over the staged tables and swaps it in, or leaves the old one.  Swap: the staged
+// generation is adopted, and whatever was sized by the old instance or primitive count is dropped
+// and re-allocated by its next user (drop_stale).
 int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
                            const void *to_world_device, uint32_t flags, void *hip_stream) {
     if (!pt || !instances) return fail(PUPIL_ERR_INVALID, "null argument");
@@ -1635,7 +1586,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     if ((uintptr_t)to_world_device & 3u) return fail(PUPIL_ERR_INVALID, "device pointer not 4-byte aligned");
     if (n == 0) return fail(PUPIL_ERR_INVALID, "scene has no instances");  // as pupil_pt_create
     const bool two_level = pt->accel.two_level;
-    const uint32_t old_n = (uint32_t)pt->h_insts.size();
+    const uint32_t old_n = (uint32_t)pt->h_insts().size();
     // ---- everything that can refuse the call from the host's tables
     std::vector<InstBinding> bind(n);
     std::vector<uint32_t> counts(n), new_shape(n);
@@ -1659,14 +1610,14 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     // emitter range is one create checked against the table)
     std::vector<uint32_t> old_em, new_em;
     for (uint32_t i = 0; i < old_n; i++)
-        if (pt->h_insts[i].emitter_offset >= 0) old_em.push_back(i);
+        if (pt->h_insts()[i].emitter_offset >= 0) old_em.push_back(i);
     for (uint32_t i = 0; i < n; i++)
         if (instances[i].emitter_offset >= 0) new_em.push_back(i);
     if (old_em.size() != new_em.size())
         return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances added or removed: the emitter table would change");
     bool emitters_moved = false;
     for (size_t k = 0; k < old_em.size(); k++) {
-        const DevInstance &o = pt->h_insts[old_em[k]];
+        const DevInstance &o = pt->h_insts()[old_em[k]];
         const pupil_instance &c = instances[new_em[k]];
         // the same material: its slot, or another slot of the same content
         const bool same_material = o.material == c.material ||
@@ -1681,10 +1632,6 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
             emitters_moved = true;
         }
     }
-    PrimTables tab;
-    if (!prim_tables(counts.data(), n, &tab)) return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 primitives");
-    if (!two_level && tab.num_prims >= (1u << 27))
-        return fail(PUPIL_ERR_UNSUPPORTED, "flattened BVH limited to 2^27 primitives");
     std::vector<InstShape> shape_tab(pt->shapes.size());  // the per-shape table
     for (size_t k = 0; k < pt->shapes.size(); k++) {
         const ShapeDev &sd = pt->shapes[k];
@@ -1694,69 +1641,51 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     const auto t0 = std::chrono::steady_clock::now();
     pt->accel.counts = SceneAccel::Counts{};
     hipStream_t s = pt->own_stream;
-    // ---- aside: nothing below is read by the engine until the swap
-    ScratchBuf<uint32_t> prim_inst, inst_first, inst_guide, emit_inst;
-    ScratchBuf<DevInstance> insts;
+    // ---- aside: nothing below is read by the engine until the swap.  The tables first: their
+    // limits refuse the call before anything is allocated; from there a failure lets the stream pass
+    EngineTables::Generation gen;
+    if (const int rc = EngineTables::stage(counts.data(), n, !two_level, s, gen)) return drained(s, rc);
+    ScratchBuf<uint32_t> emit_inst;
     ScratchBuf<InstBinding> d_bind;
     ScratchBuf<InstShape> d_shapes;
     ScratchBuf<float> xf, inst_weight;
     const bool remap = pt->dev_emit && pt->d_inst_weight;
-    if (prim_inst.alloc(tab.num_prims) || inst_first.alloc(tab.inst_first.size()) || inst_guide.alloc(tab.guide_entries) ||
-        insts.alloc(n) || d_bind.alloc(n) || d_shapes.alloc(shape_tab.size()) || (!device && xf.alloc(24 * (size_t)n)) ||
-        (remap && (emit_inst.alloc(pt->dev_emit_count) || inst_weight.alloc(n)))) {
-        (void)hipGetLastError();
-        return fail(PUPIL_ERR_OOM, "instance table: allocation failed");
-    }
-    auto bail = [&](int rc) {  // a failure after the first enqueue: the stream passes what it holds before the buffers go
-        (void)hipStreamSynchronize(s);
-        return rc;
-    };
-#define SET_TRY(expr)                                                                              \
-    do {                                                                                           \
-        const hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess)                                                                      \
-            return bail(fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,            \
-                             std::string(#expr) + ": " + hipGetErrorString(_e)));                  \
-    } while (0)
+    if (d_bind.alloc(n) || d_shapes.alloc(shape_tab.size()) || (!device && xf.alloc(24 * (size_t)n)) ||
+        (remap && (emit_inst.alloc(pt->dev_emit_count) || inst_weight.alloc(n))))
+        return drained(s, fail(PUPIL_ERR_OOM, "instance table: allocation failed"));
     std::vector<float> h_xf;  // host path: n to_world, then n to_object; outlives the copy (the build synchronises)
-    if (device) {  // after the work enqueued so far on the caller's stream; no device-wide sync
-        SET_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
-        SET_TRY(hipStreamWaitEvent(s, pt->ev_verts, 0));
+    if (device) {
+        HIP_TRY_DRAINED(s, order_after_caller(pt, hip_stream));
     } else {
         h_xf.resize(24 * (size_t)n);
         for (uint32_t i = 0; i < n; i++) {
             std::memcpy(&h_xf[12 * (size_t)i], instances[i].to_world, sizeof(float) * 12);
             std::memcpy(&h_xf[12 * ((size_t)n + i)], instances[i].to_object, sizeof(float) * 12);
         }
-        SET_TRY(hipMemcpyAsync(xf.get(), h_xf.data(), sizeof(float) * h_xf.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY_DRAINED(s, hipMemcpyAsync(xf.get(), h_xf.data(), sizeof(float) * h_xf.size(), hipMemcpyHostToDevice, s));
     }
-    SET_TRY(hipMemcpyAsync(d_bind.get(), bind.data(), sizeof(InstBinding) * n, hipMemcpyHostToDevice, s));
-    SET_TRY(hipMemcpyAsync(d_shapes.get(), shape_tab.data(), sizeof(InstShape) * shape_tab.size(), hipMemcpyHostToDevice, s));
-    SET_TRY(hipMemcpyAsync(inst_first.get(), tab.inst_first.data(), sizeof(uint32_t) * tab.inst_first.size(),
-                           hipMemcpyHostToDevice, s));
-    launch_prim_tables(inst_first.get(), n, tab.num_prims, tab.guide_shift, tab.guide_entries, prim_inst.get(),
-                       inst_guide.get(), s);
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(d_bind.get(), bind.data(), sizeof(InstBinding) * n, hipMemcpyHostToDevice, s));
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(d_shapes.get(), shape_tab.data(), sizeof(InstShape) * shape_tab.size(), hipMemcpyHostToDevice, s));
     FillInstancesJob job{};
-    job.out = insts.get();
+    job.out = gen.insts.get();
     job.n = n;
     job.shapes = d_shapes.get();
     job.bindings = d_bind.get();
-    job.inst_first = inst_first.get();
+    job.inst_first = gen.inst_first.get();
     job.to_world = device ? (const float *)to_world_device : xf.get();
     job.to_object = device ? nullptr : xf.get() + 12 * (size_t)n;
     launch_fill_instances(job, s);
-    SET_TRY(hipGetLastError());
-    pt->accel.counts.launches += 2;
-    std::vector<DevInstance> mirror(n);
+    HIP_TRY_DRAINED(s, hipGetLastError());
+    pt->accel.counts.launches += 2;  // with the tables' fill
     if (device) {  // one contiguous readback
-        SET_TRY(hipMemcpyAsync(mirror.data(), insts.get(), sizeof(DevInstance) * n, hipMemcpyDeviceToHost, s));
-        SET_TRY(hipStreamSynchronize(s));
+        HIP_TRY_DRAINED(s, hipMemcpyAsync(gen.mirror.data(), gen.insts.get(), sizeof(DevInstance) * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY_DRAINED(s, hipStreamSynchronize(s));
         pt->accel.counts.syncs++;
         // the table holds a hidden sphere's device copy: the mirror keeps its real inverse, the same text
-        for (DevInstance &d : mirror)
+        for (DevInstance &d : gen.mirror)
             if (d.hidden && d.kind == PUPIL_SHAPE_SPHERE) invert_affine3x4(d.to_world, d.to_object);
         for (size_t k = 0; k < old_em.size(); k++) {
-            const DevInstance &o = pt->h_insts[old_em[k]], &c = mirror[new_em[k]];
+            const DevInstance &o = pt->h_insts()[old_em[k]], &c = gen.mirror[new_em[k]];
             if (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) == 0 &&
                 std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) == 0)
                 continue;
@@ -1766,7 +1695,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         }
     } else {
         for (uint32_t i = 0; i < n; i++)
-            fill_instance_record(mirror[i], shape_tab[bind[i].shape], bind[i], tab.inst_first[i], instances[i].to_world,
+            fill_instance_record(gen.mirror[i], shape_tab[bind[i].shape], bind[i], gen.first[i], instances[i].to_world,
                                  instances[i].to_object, false);
     }
     std::vector<uint32_t> h_emit_inst;
@@ -1781,27 +1710,16 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         }
         for (uint32_t &e : h_emit_inst) e = to_new[e];
         if (!h_emit_inst.empty())
-            SET_TRY(hipMemcpyAsync(emit_inst.get(), h_emit_inst.data(), sizeof(uint32_t) * h_emit_inst.size(),
+            HIP_TRY_DRAINED(s, hipMemcpyAsync(emit_inst.get(), h_emit_inst.data(), sizeof(uint32_t) * h_emit_inst.size(),
                                    hipMemcpyHostToDevice, s));
-        SET_TRY(hipMemcpyAsync(inst_weight.get(), h_inst_weight.data(), sizeof(float) * n, hipMemcpyHostToDevice, s));
+        HIP_TRY_DRAINED(s, hipMemcpyAsync(inst_weight.get(), h_inst_weight.data(), sizeof(float) * n, hipMemcpyHostToDevice, s));
     }
     // ---- build: after the renders enqueued so far (the swap below frees what they read)
-    SET_TRY(order_after_renders(pt));
-    if (const int rc = pt->accel.set_instances(tab.num_prims, prim_inst.get(), insts.get(), mirror, new_shape, pt->shapes))
-        return bail(rc);
-#undef SET_TRY
+    HIP_TRY_DRAINED(s, order_after_renders(pt));
+    if (const int rc = pt->accel.set_instances(gen, new_shape, pt->shapes)) return drained(s, rc);
     // ---- swap: the structure is published and the stream idle
     pt->pipe.invalidate();  // frames in flight were traced against the old table
-    for (void *p : {(void *)pt->d_prim_inst, (void *)pt->sc.inst_first, (void *)pt->sc.inst_guide, (void *)pt->d_insts,
-                    (void *)pt->query_slot, (void *)pt->flow_prev, (void *)pt->flow_verts, (void *)pt->d_move_stage})
-        pt->release(p);
-    pt->query_slot = nullptr;  // sized by the primitive count; the next query that needs it allocates
-    pt->flow_prev = nullptr;   // the flow scratch and the device move's staging block: by the instance count
-    pt->flow_verts = nullptr;
-    pt->flow_verts_stale = true;
-    pt->h_flow_prev.clear(), pt->h_flow_verts.clear();
-    pt->d_move_stage = nullptr;
-    pt->h_move_ids.clear(), pt->h_move_seen.clear(), pt->h_move_stage.clear();
+    drop_stale(pt, true, true);
     if (remap) {
         pt->release(pt->d_emit_inst);
         pt->release(pt->d_inst_weight);
@@ -1816,20 +1734,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         pt->release(pt->d_emit_sum);
         pt->d_inst_weight = pt->d_emit_sum = nullptr;
     }
-    for (void *p : {(void *)prim_inst.get(), (void *)inst_first.get(), (void *)inst_guide.get(), (void *)insts.get()})
-        pt->allocs.push_back(p);
-    pt->d_prim_inst = prim_inst.release();
-    pt->d_insts = insts.release();
-    pt->num_prims = tab.num_prims;
-    DeviceScene &sc = pt->sc;
-    sc.num_prims = tab.num_prims;
-    sc.prim_inst = pt->d_prim_inst;
-    sc.inst_first = inst_first.release();
-    sc.inst_guide = inst_guide.release();
-    sc.inst_guide_shift = tab.guide_shift;
-    sc.instances = pt->d_insts;
-    sc.num_instances = n;
-    pt->totals.bvh_prims = pt->num_prims;
+    pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
     pt->accel.refits++;
     derive_bins(pt);
     if (const int rc = derive_cull_set(pt)) return rc;  // the build moved the records
@@ -1838,8 +1743,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     pt->inst_sets++;
     pt->inst_set_blas_builds = pt->accel.last_blas_builds;
     pt->inst_set_whole = pt->accel.last_whole_rebuild;
-    pt->inst_set_ms = pt->totals.build_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->inst_set_ms = pt->totals.build_ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -1897,7 +1801,7 @@ int pupil_pt_update_instance(pupil_pt *pt, uint32_t instance, const float to_wor
 int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *ids_device, const void *to_world_device,
                                      const void *to_object_device, void *hip_stream) {
     if (!pt || !to_world_device) return fail(PUPIL_ERR_INVALID, "null argument");
-    const uint32_t ni = (uint32_t)pt->h_insts.size();
+    const uint32_t ni = (uint32_t)pt->h_insts().size();
     if (n > ni) return fail(PUPIL_ERR_INVALID, "more list entries than instances");
     for (const void *p : {(const void *)ids_device, to_world_device, to_object_device})
         if ((uintptr_t)p & 3u) return fail(PUPIL_ERR_INVALID, "device pointer not 4-byte aligned");
@@ -1916,9 +1820,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
         const uint32_t so_far = (uint32_t)pt->inst_dev_skipped;  // pupil_pt_set_instances dropped an earlier block
         if (so_far) HIP_TRY(hipMemcpy(pt->d_move_stage, &so_far, sizeof(so_far), hipMemcpyHostToDevice));
     }
-    // after the work enqueued so far on the caller's stream; no device-wide sync
-    HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));
-    HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    HIP_TRY(order_after_caller(pt, hip_stream));
     std::vector<uint32_t> &ids = pt->h_move_ids;  // the list as the caller gave it
     ids.resize(n);
     if (ids_device) {
@@ -1936,7 +1838,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
         if (id >= ni || seen[id]) continue;
         seen[id] = 1;
         changed.push_back(id);
-        emissive = emissive || pt->h_insts[id].emitter_offset >= 0;
+        emissive = emissive || pt->h_insts()[id].emitter_offset >= 0;
     }
     if (emissive && !pt->dev_emit)
         return fail(PUPIL_ERR_UNSUPPORTED,
@@ -1944,7 +1846,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
     HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
     pt->pipe.invalidate();          // frames in flight were traced against the old geometry
     MoveInstancesJob job{};
-    job.instances = pt->d_insts;
+    job.instances = pt->d_insts();
     job.num_instances = ni;
     job.n = n;
     job.ids = ids_device;
@@ -1977,7 +1879,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
         if (id >= ni || seen[id]) continue;  // of a repeated id the first entry is mirrored
         seen[id] = 1;
         const float *e = st.data() + pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * k;
-        DevInstance &d = pt->h_insts[id];
+        DevInstance &d = pt->h_insts()[id];
         std::memcpy(d.to_world, e, sizeof(d.to_world));
         std::memcpy(d.to_object, e + 12, sizeof(d.to_object));
         if (pt->accel.two_level) std::memcpy(d.margin, e + 24, sizeof(d.margin));
@@ -1997,8 +1899,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
     pt->inst_dev_moved += changed.size();
     pt->inst_dev_launches = cnt.launches;
     pt->inst_dev_syncs = cnt.syncs;
-    pt->inst_dev_ms = pt->totals.build_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->inst_dev_ms = pt->totals.build_ms = ms_since(t0);
     if (skipped_now)
         g_last_error = std::to_string(skipped_now) + " of " + std::to_string(n) + " instance ids out of range: skipped";
     return PUPIL_OK;
@@ -2006,10 +1907,10 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
 
 int pupil_pt_get_instance_transforms(pupil_pt *pt, uint32_t first, uint32_t n, float *to_world, float *to_object) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
-    const size_t ni = pt->h_insts.size();
+    const size_t ni = pt->h_insts().size();
     if (first > ni || n > ni - first) return fail(PUPIL_ERR_INVALID, "instance range out of bounds");
     for (uint32_t k = 0; k < n; k++) {
-        const DevInstance &d = pt->h_insts[first + k];
+        const DevInstance &d = pt->h_insts()[first + k];
         if (to_world) std::memcpy(to_world + 12 * (size_t)k, d.to_world, sizeof(d.to_world));
         if (to_object) std::memcpy(to_object + 12 * (size_t)k, d.to_object, sizeof(d.to_object));
     }
@@ -2184,14 +2085,14 @@ int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
     }
     std::vector<DevInstance> staged;  // outlives the copies (synchronised below)
     if (type_changed) {
-        staged.reserve(pt->h_insts.size());
-        for (size_t i = 0; i < pt->h_insts.size(); i++) {
-            DevInstance &d = pt->h_insts[i];
+        staged.reserve(pt->h_insts().size());
+        for (size_t i = 0; i < pt->h_insts().size(); i++) {
+            DevInstance &d = pt->h_insts()[i];
             const uint32_t bin = material_bin(pt->h_mats[d.material].type);
             if (bin == d.bin) continue;
             d.bin = bin;
             staged.push_back(device_instance(d));
-            HIP_TRY(hipMemcpyAsync(pt->d_insts + i, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
+            HIP_TRY(hipMemcpyAsync(pt->d_insts() + i, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
                                    pt->own_stream));
         }
         if (!staged.empty()) {
@@ -2203,7 +2104,7 @@ int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     for (void *p : stale) pt->release(p);  // the stream has passed them
     pt->mat_updates++;
-    pt->mat_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->mat_ms = ms_since(t0);
     return derive_cull_set(pt, false);
 }
 
@@ -2226,8 +2127,7 @@ int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slo
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(order_after_renders(pt));  // no render may still read the old texels
     pt->pipe.invalidate();
-    HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));  // after the caller's work; no device-wide sync
-    HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    HIP_TRY(order_after_caller(pt, hip_stream));
     HIP_TRY(hipMemcpyAsync((void *)t.data, rgba_device, sizeof(float4) * (size_t)width * height, hipMemcpyDeviceToDevice,
                            pt->own_stream));
     const uint32_t diffuse_slot = m.type == PUPIL_MAT_PLASTIC ? 0u : 1u;
@@ -2238,7 +2138,7 @@ int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slo
     }
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     pt->mat_updates++;
-    pt->mat_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->mat_ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -2289,8 +2189,7 @@ int pupil_pt_update_env_device(pupil_pt *pt, const void *rgba_device, uint32_t w
     HIP_TRY(order_after_renders(pt));  // no render may still read the old texels and tables
     pt->pipe.invalidate();
     pt->env_stale = true;  // from here env_src no longer describes the device
-    HIP_TRY(hipEventRecord(pt->ev_verts, (hipStream_t)hip_stream));  // after the caller's work; no device-wide sync
-    HIP_TRY(hipStreamWaitEvent(pt->own_stream, pt->ev_verts, 0));
+    HIP_TRY(order_after_caller(pt, hip_stream));
     HIP_TRY(hipMemcpyAsync((void *)e.radiance.data, rgba_device, sizeof(float4) * (size_t)width * height,
                            hipMemcpyDeviceToDevice, pt->own_stream));
     launch_env_tables({e.radiance.data, width, height, const_cast<float *>(e.col_cdf), const_cast<float *>(e.row_cdf),
@@ -2299,7 +2198,7 @@ int pupil_pt_update_env_device(pupil_pt *pt, const void *rgba_device, uint32_t w
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     pt->env_updates++;
-    pt->env_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->env_ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -2323,7 +2222,7 @@ int pupil_pt_update_env_params(pupil_pt *pt, float scale, const float to_world[9
                            pt->own_stream));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     pt->env_updates++;
-    pt->env_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pt->env_ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -2473,7 +2372,7 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     c.ring_bytes = pt->ring_bytes + sizeof(float) * (uint64_t)pt->aov_cap;
     c.ring_budget_bytes = (uint64_t)pt->knobs.budget;
     c.accel_refits = pt->accel.refits;
-    for (const DevInstance &d : pt->h_insts) c.hidden_instances += d.hidden ? 1u : 0u;
+    for (const DevInstance &d : pt->h_insts()) c.hidden_instances += d.hidden ? 1u : 0u;
     c.frame_launches = pt->frame_launches;
     for (int a = 0; a < 3; a++) c.node_bound[a] = pt->sc.node_bound[a];
     if (pt->last_paths) {
@@ -2704,14 +2603,14 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
         else HIP_TRY(hipEventSynchronize(pt->ev_flow));  // the previous upload has left the staging copies
     }
     if (prev_to_world) {
-        const size_t nf = 12 * pt->h_insts.size();
+        const size_t nf = 12 * pt->h_insts().size();
         if (!pt->flow_prev) HIP_TRY(pt->alloc(&pt->flow_prev, nf));
         pt->h_flow_prev.assign(prev_to_world, prev_to_world + nf);
         if (nf) HIP_TRY(hipMemcpyAsync(pt->flow_prev, pt->h_flow_prev.data(), sizeof(float) * nf, hipMemcpyHostToDevice, s));
         job.prev_to_world = pt->flow_prev;
     }
     if (table) {
-        const size_t ni = pt->h_insts.size();
+        const size_t ni = pt->h_insts().size();
         if (!pt->flow_verts) HIP_TRY(pt->alloc(&pt->flow_verts, ni));
         pt->h_flow_verts.assign(ni, nullptr);
         for (size_t i = 0; i < ni; i++) {
@@ -2797,7 +2696,7 @@ int run_query(pupil_pt *pt, uint32_t n, const float4 *rays, uint32_t flags, cons
     }
     const bool slots = geo && !pt->sc.two_level;  // reconstruct() names flat records by slot
     if (slots && !pt->query_slot) {
-        HIP_TRY(pt->alloc(&pt->query_slot, pt->num_prims));
+        HIP_TRY(pt->alloc(&pt->query_slot, pt->tables.cur().num_prims));
         pt->query_grows++;
     }
     if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
@@ -2812,7 +2711,7 @@ int run_query(pupil_pt *pt, uint32_t n, const float4 *rays, uint32_t flags, cons
     if (resolved || scatter) {
         const uint32_t rec_slots = slots ? pt->accel.world_record_slots() : 1u;
         if (slots && !pt->query_slot_valid) {
-            launch_query_prim_slots(pt->sc.prims, rec_slots, pt->num_prims, pt->query_slot, s);
+            launch_query_prim_slots(pt->sc.prims, rec_slots, pt->tables.cur().num_prims, pt->query_slot, s);
             pt->query_slot_valid = true;
         }
         const QueryJob job{rays,

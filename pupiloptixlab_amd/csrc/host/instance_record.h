@@ -1,10 +1,9 @@
 // instance_record.h — one instance's 224-byte DevInstance record from what it binds: one text for
-// pupil_pt_set_instances' host mirror, for the kernel that fills a new instance table on the
-// device (pt_instance_set.hip k_fill_instances) and for the stand-alone host driver of the tests.
-// The record is what pupil_pt_create's upload_tables uploads for the same instance.  The
-// two-level fields (BLAS root and bases, margins, world box) stay as upload_tables leaves them:
-// build_two_level's instance stage fills them in the host mirror and uploads the table again, at
-// create and after pupil_pt_set_instances alike.
+// pupil_pt_create, for pupil_pt_set_instances' host mirror, for the kernel that fills a new
+// instance table on the device (pt_instance_set.hip k_fill_instances) and for the stand-alone host
+// driver of the tests.  The two-level fields (BLAS root and bases, margins, world box) are left
+// empty: build_two_level's instance stage fills them in the host mirror and uploads the table
+// again, at create and after pupil_pt_set_instances alike.
 #pragma once
 
 #include <math.h>
@@ -71,7 +70,7 @@ PT_HD void fill_instance_record(DevInstance &d, const InstShape &sh, const InstB
     d.normals = sh.normals;
     d.texcoords = sh.texcoords;
     d.indices = sh.indices;
-    // the two-level fields as upload_tables leaves them: the structure's instance stage fills them
+    // the two-level fields, empty: the structure's instance stage fills them
     d.blas_root = kTraverseDone;
     d.attr_base = 0u;
     d.bin = b.bin;

@@ -2,10 +2,12 @@
 // and what the engine's host code shares with it.
 #pragma once
 
+#include <chrono>
 #include <string>
 
 #include "../../include/pupil_pt.h"
 #include "accel_two_level.h"
+#include "host/scene_tables.h"
 
 namespace pupil {
 
@@ -19,6 +21,44 @@ int fail(int code, const std::string &msg);
             return fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,                        \
                         std::string(#expr) + ": " + hipGetErrorString(_e));                               \
     } while (0)
+
+// the host clock: milliseconds since t0
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// After the first enqueue of an update that builds aside: the stream passes what it holds before
+// the call's own buffers go with the return.
+inline int drained(hipStream_t stream, int rc) {
+    (void)hipStreamSynchronize(stream);
+    return rc;
+}
+#define HIP_TRY_DRAINED(stream, expr)                                                                     \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess)                                                                             \
+            return drained(stream, fail(_e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP,        \
+                                        std::string(#expr) + ": " + hipGetErrorString(_e)));              \
+    } while (0)
+
+// the device of the engine's tables (host/scene_tables.h) and of a call's scratch
+struct HipDevice {
+    using Stream = hipStream_t;
+    static hipError_t alloc(void **p, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) (void)hipGetLastError();
+        return e;
+    }
+    static void free(void *p) { (void)hipFree(p); }
+    static int fill(const TableGeneration<HipDevice> &g, hipStream_t stream) {
+        HIP_TRY(hipMemcpyAsync(g.inst_first.get(), g.first.data(), sizeof(uint32_t) * g.first.size(), hipMemcpyHostToDevice,
+                               stream));
+        launch_prim_tables(g.inst_first.get(), g.num_instances, g.num_prims, g.guide_shift, g.guide_entries,
+                           g.prim_inst.get(), g.inst_guide.get(), stream);
+        return PUPIL_OK;
+    }
+};
+using EngineTables = SceneTables<HipDevice>;
 
 // a shape's engine-owned device arrays (those the instances point at)
 struct ShapeDev {
@@ -37,16 +77,21 @@ struct ShapeDev {
 // writer of the structure's fields of DeviceScene and of totals.bvh_nodes / bvh_depth /
 // two_level, and every update ends in it.
 struct SceneAccel {
-    // The engine's tables the structure is built over and publishes to, valid for the engine's
-    // life.  Before an update, insts / d_insts already hold the new transforms and masks, and
-    // the shapes' device arrays the new vertices.
+    // What the structure is built over and publishes to, valid for the engine's life.  The
+    // instance and primitive tables are read through their owner, never copied: before an update
+    // its current generation (mirror and device table) already holds the new transforms and
+    // masks, and the shapes' device arrays the new vertices.
+    // The hand-off of an update that resizes a table (replace_shape, set_instances), in one place:
+    // the engine stages a generation aside (SceneTables::stage) and fills its instance table and
+    // mirror; for the length of the call the structure reads that generation instead of the
+    // current one and builds over it; on success the engine adopts it (SceneTables::adopt), on
+    // failure the current tables and the old structure are untouched and the staged generation
+    // goes with the engine's call.
+    using Generation = EngineTables::Generation;
     struct Tables {
         hipStream_t stream;  // the engine's own
-        uint32_t num_prims;
-        const uint32_t *d_prim_inst;
-        DevInstance *d_insts;
+        EngineTables *tables;
         const DevMaterial *d_mats;
-        std::vector<DevInstance> *insts;
         DeviceScene *sc;
         pupil_pt_counters *totals;
     };
@@ -59,19 +104,14 @@ struct SceneAccel {
     // rebuild: PUPIL_VERTS_REBUILD
     int update_shape(uint32_t shape, const std::vector<uint32_t> &changed, bool rebuild);
     // Mesh shape `shape` got new topology (pupil_pt_replace_shape_mesh).  The engine has built
-    // aside, on the stream: `mesh`, the shape's new arrays and counts; the primitive -> instance
-    // table d_prim_inst of num_prims primitives; a second instance table d_insts with the new prim
-    // offsets and array pointers, and `insts`, the host mirror patched the same way.  The
-    // structure takes them as its tables and, when an instance shows the shape (`used`), is
-    // rebuilt over them as by update_shape(rebuild) and published.  On failure the old tables and
-    // the old structure stay and nothing of *insts' owner has changed; on success `insts` holds
-    // the previous mirror.
-    int replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, uint32_t num_prims, const uint32_t *d_prim_inst,
-                      DevInstance *d_insts, std::vector<DevInstance> &insts);
+    // aside, on the stream: `mesh`, the shape's new arrays and counts, and `staged`, whose
+    // instance table and mirror carry the new prim offsets and array pointers.  When an instance
+    // shows the shape (`used`), the structure is rebuilt over `staged` as by update_shape(rebuild)
+    // and published.
+    int replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, Generation &staged);
     // The instance table was replaced as a whole (pupil_pt_set_instances).  The engine has built
-    // aside, on the stream: the primitive -> instance table, a second instance table d_insts
-    // (k_fill_instances), `insts`, its host mirror, and `shape_of`, the shape of each new instance.
-    // The structure takes them as its tables, is built over them and published.  Flattened: one
+    // aside, on the stream: `staged` (its instance table by k_fill_instances) and `shape_of`, the
+    // shape of each new instance.  The structure is built over `staged` and published.  Flattened: one
     // build, as update_shape(rebuild).  Two-level, world mode, the set of mesh shapes shown by at
     // least one instance unchanged: the instance stage alone (set_two_level_instances) on freshly
     // sized per-instance arrays -- no BLAS builder runs.  Two-level otherwise -- the set changed,
@@ -80,11 +120,10 @@ struct SceneAccel {
     // built anew.  Both two-level paths fill the instances' two-level fields in the host mirror and
     // upload the table again, as create does.  A shape that gains its first instance takes its
     // arrays and vmax from `shapes` as they are now; one that loses its last is forgotten.
-    // Masks go on after the build, as a fresh engine's do after create.  On failure
-    // the old tables and structure stay; on success `insts` and `shape_of` hold the previous ones.
+    // Masks go on after the build, as a fresh engine's do after create.  On success `shape_of`
+    // holds the previous shapes.
     // last_blas_builds / last_whole_rebuild: what the last call ran (flattened: 0 / 1).
-    int set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, DevInstance *d_insts, std::vector<DevInstance> &insts,
-                      std::vector<uint32_t> &shape_of, const std::vector<ShapeDev> &shapes);
+    int set_instances(Generation &staged, std::vector<uint32_t> &shape_of, const std::vector<ShapeDev> &shapes);
     uint32_t last_blas_builds = 0, last_whole_rebuild = 0;
     // Instances moved on the device (pupil_pt_update_instances_device), in three steps whose kernel
     // launches and synchronisations do not depend on how many moved (flattened BVH, two-level world
@@ -134,6 +173,14 @@ private:
     int update_tlas(const std::vector<uint32_t> &changed);
     int flag_instances(const std::vector<uint32_t> *changed, uint32_t nodes);
     Tables t{};
+    // the generation the structure reads: the current one, or `over` for the length of a hand-off
+    Generation *over = nullptr;
+    Generation &g() const { return over ? *over : t.tables->cur(); }
+    struct BuildOver {  // scope of a hand-off
+        SceneAccel &a;
+        BuildOver(SceneAccel &accel, Generation &staged) : a(accel) { a.over = &staged; }
+        ~BuildOver() { a.over = nullptr; }
+    };
     // flattened-BVH refits: per-instance moved flags and the node-box scratch
     uint8_t *d_moved = nullptr;
     std::vector<uint8_t> h_moved;

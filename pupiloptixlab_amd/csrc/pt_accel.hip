@@ -2,7 +2,6 @@
 #include "pt_accel.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -83,11 +82,11 @@ int SceneAccel::build(const Tables &tables, const pupil_scene_desc *scene, const
             for (size_t v = 0; v < 3 * (size_t)sh.num_vertices; v++) vmax = std::max(vmax, std::fabs(sh.positions[v]));
             ts.vmax = vmax;
         }
-        const int rc = build_two_level(tl_shapes, inst_shape, *t.insts, t.d_insts, t.d_mats, leaf_size, t.stream, tl);
+        const int rc = build_two_level(tl_shapes, inst_shape, g().mirror, g().insts.get(), t.d_mats, leaf_size, t.stream, tl);
         if (rc != 0) return builder_error(rc, true, "two-level acceleration build failed");
         ms = tl.build_ms;
     } else {
-        const BvhBuildInput bin{t.num_prims, t.d_prim_inst, t.d_insts, t.d_mats};
+        const BvhBuildInput bin{g().num_prims, g().prim_inst.get(), g().insts.get(), t.d_mats};
         const int rc = build_bvh_bounded(bin, bvh, leaf_size, t.stream, &ms, 0);
         if (rc != 0) return builder_error(rc, false, "LBVH build failed");
     }
@@ -147,7 +146,7 @@ int SceneAccel::publish() {
 // the flags of the instances whose records a refit rewrites (`changed`, or null: the hidden
 // ones) on the device, and the node-box scratch of a tree of `nodes` nodes
 int SceneAccel::flag_instances(const std::vector<uint32_t> *changed, uint32_t nodes) {
-    const std::vector<DevInstance> &insts = *t.insts;
+    const std::vector<DevInstance> &insts = g().mirror;
     if (!d_moved) HIP_TRY(hipMalloc((void **)&d_moved, std::max<size_t>(1, insts.size())));
     if (!refit_box) HIP_TRY(hipMalloc((void **)&refit_box, sizeof(float) * 6 * (size_t)std::max(1u, nodes)));
     h_moved.assign(insts.size(), 0);
@@ -165,7 +164,7 @@ int SceneAccel::flag_instances(const std::vector<uint32_t> *changed, uint32_t no
 // place, or a rebuild with the masks applied to the new tree before it replaces the old one
 // (refit = false, PUPIL_FLAT_UPDATE=rebuild, a tree without a level order).
 int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs, bool flagged) {
-    const BvhBuildInput bin{t.num_prims, t.d_prim_inst, t.d_insts, t.d_mats};
+    const BvhBuildInput bin{g().num_prims, g().prim_inst.get(), g().insts.get(), t.d_mats};
     if (refit && !is_rebuild(std::getenv("PUPIL_FLAT_UPDATE"))) {
         if (!flagged)
             if (const int rc = flag_instances(&changed, bvh.num_nodes4)) return rc;
@@ -188,7 +187,7 @@ int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bo
         refit_box = nullptr;
     }
     bool any_hidden = false;
-    for (const DevInstance &d : *t.insts) any_hidden = any_hidden || d.hidden != 0u;
+    for (const DevInstance &d : g().mirror) any_hidden = any_hidden || d.hidden != 0u;
     if (rc == PUPIL_OK && any_hidden) {  // the build covered every instance: the masks go on like a refit's
         rc = flag_instances(nullptr, nb.num_nodes4);
         const int hrc = rc ? 0 : refit_bvh4(bin, nb, d_moved, refit_box, t.stream, &hms, true);
@@ -209,7 +208,7 @@ int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bo
 // regenerated: world mode refits it like the reference's IAS update, object mode rebuilds it
 // (PUPIL_TL_UPDATE=rebuild: full build in both).
 int SceneAccel::update_tlas(const std::vector<uint32_t> &changed) {
-    const int rc = rebuild_tlas(tl, *t.insts, t.d_insts, changed, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")),
+    const int rc = rebuild_tlas(tl, g().mirror, g().insts.get(), changed, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")),
                                 &counts.launches, &counts.syncs);
     return rc != 0 ? builder_error(rc, true, "TLAS rebuild failed") : publish();
 }
@@ -218,7 +217,7 @@ int SceneAccel::update_instances(const std::vector<uint32_t> &changed) {
     if (!two_level) return update_flat(changed, true, false);
     const auto t0 = std::chrono::steady_clock::now();
     if (const int rc = update_tlas(changed)) return rc;
-    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -229,7 +228,7 @@ int SceneAccel::move_begin(uint32_t **list, uint8_t **moved) {
         return PUPIL_OK;
     }
     if (is_rebuild(std::getenv("PUPIL_FLAT_UPDATE"))) return PUPIL_OK;  // a rebuild reads no flag
-    const size_t n = std::max<size_t>(1, t.insts->size());
+    const size_t n = std::max<size_t>(1, g().mirror.size());
     if (!d_moved) HIP_TRY(hipMalloc((void **)&d_moved, n));
     if (!refit_box) HIP_TRY(hipMalloc((void **)&refit_box, sizeof(float) * 6 * (size_t)std::max(1u, bvh.num_nodes4)));
     HIP_TRY(hipMemsetAsync(d_moved, 0, n, t.stream));
@@ -239,7 +238,7 @@ int SceneAccel::move_begin(uint32_t **list, uint8_t **moved) {
 
 void SceneAccel::move_boxes(uint32_t count, float *box, uint32_t stride) {
     if (!two_level || !tl.world || count == 0) return;
-    instance_boxes_device(tl, t.d_insts, count, box, stride, t.stream);
+    instance_boxes_device(tl, g().insts.get(), count, box, stride, t.stream);
     counts.launches += 2;
 }
 
@@ -247,11 +246,11 @@ int SceneAccel::move_finish(const std::vector<uint32_t> &changed, uint32_t count
     if (!two_level) return update_flat(changed, true, false, d_moved != nullptr && !is_rebuild(std::getenv("PUPIL_FLAT_UPDATE")));
     if (!tl.world) return update_instances(changed);  // the host's TLAS build, from the mirror
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = move_world_instances(tl, *t.insts, t.d_insts, changed, count, t.stream,
+    const int rc = move_world_instances(tl, g().mirror, g().insts.get(), changed, count, t.stream,
                                         !is_rebuild(std::getenv("PUPIL_TL_UPDATE")), &counts.launches, &counts.syncs);
     if (rc != 0) return builder_error(rc, true, "TLAS rebuild failed");
     if (const int prc = publish()) return prc;
-    ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms = ms_since(t0);
     return PUPIL_OK;
 }
 
@@ -261,12 +260,12 @@ int SceneAccel::move_finish(const std::vector<uint32_t> &changed, uint32_t count
 uint32_t SceneAccel::world_record_slots() const {
     uint64_t slots = two_level ? tl.num_wprims : bvh.num_records;
     if (two_level && tl.world)
-        for (const DevInstance &d : *t.insts) slots += d.kind == PUPIL_SHAPE_SPHERE ? 2u : 0u;
+        for (const DevInstance &d : g().mirror) slots += d.kind == PUPIL_SHAPE_SPHERE ? 2u : 0u;
     return (uint32_t)slots;
 }
 
 void SceneAccel::update_bins() {
-    launch_record_bins(two_level ? tl.wprims : bvh.prims, world_record_slots(), t.d_insts, (uint32_t)t.insts->size(),
+    launch_record_bins(two_level ? tl.wprims : bvh.prims, world_record_slots(), g().insts.get(), (uint32_t)g().mirror.size(),
                        t.stream);
 }
 
@@ -285,8 +284,8 @@ int SceneAccel::update_shape(uint32_t shape, const std::vector<uint32_t> &change
         if (update_shape_blas(tl, shape, ts, &vmax, t.stream) != 0) return fail(PUPIL_ERR_HIP, "BLAS refit failed");
         ts.vmax = vmax;
         for (uint32_t id : changed) {
-            (*t.insts)[id].vmax = vmax;
-            refresh_instance_margins((*t.insts)[id]);
+            g().mirror[id].vmax = vmax;
+            refresh_instance_margins(g().mirror[id]);
         }
         return update_tlas(changed);
     }
@@ -295,9 +294,9 @@ int SceneAccel::update_shape(uint32_t shape, const std::vector<uint32_t> &change
     // device vertices never come back to the host
     if (shape_abs_max(tl, ts, &vmax, t.stream) != 0) return fail(PUPIL_ERR_HIP, "vertex reduction failed");
     ts.vmax = vmax;
-    std::vector<DevInstance> insts = *t.insts;  // build_two_level refills the two-level fields
+    std::vector<DevInstance> insts = g().mirror;  // build_two_level refills the two-level fields
     TwoLevelAccel ntl{};
-    int rc = build_two_level(tl_shapes, inst_shape, insts, t.d_insts, t.d_mats, leaf_size, t.stream, ntl);
+    int rc = build_two_level(tl_shapes, inst_shape, insts, g().insts.get(), t.d_mats, leaf_size, t.stream, ntl);
     rc = rc != 0 ? builder_error(rc, true, "two-level acceleration rebuild failed") : node_limit(nodes4_of(ntl));
     if (rc != PUPIL_OK) {  // the old structure stays
         free_two_level(ntl);
@@ -305,17 +304,12 @@ int SceneAccel::update_shape(uint32_t shape, const std::vector<uint32_t> &change
     }
     free_two_level(tl);
     tl = ntl;
-    *t.insts = insts;
+    g().mirror = insts;
     return publish();
 }
 
-int SceneAccel::replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, uint32_t num_prims,
-                              const uint32_t *d_prim_inst, DevInstance *d_insts, std::vector<DevInstance> &insts) {
-    const Tables old_tables = t;
-    t.num_prims = num_prims;
-    t.d_prim_inst = d_prim_inst;
-    t.d_insts = d_insts;
-    t.insts->swap(insts);
+int SceneAccel::replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, Generation &staged) {
+    const BuildOver scope(*this, staged);
     if (!used) {  // no instance shows the shape: no structure holds it (the two-level build skips it too)
         HIP_TRY(hipStreamSynchronize(t.stream));
         return PUPIL_OK;
@@ -331,31 +325,19 @@ int SceneAccel::replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, u
         ts.texcoords = mesh.tex;
         ts.indices = mesh.idx;  // vmax: update_shape reduces it from the new array
     }
-    // both rebuilds build aside and swap on success: flat over t's tables, two-level over
-    // tl_shapes and a copy of *t.insts, uploaded to t.d_insts -- the second table
+    // both rebuilds build aside and swap on success: flat over the staged tables, two-level over
+    // tl_shapes and a copy of the staged mirror, uploaded to the staged instance table
     const int rc = update_shape(shape, {}, true);
-    if (rc != PUPIL_OK) {
-        t.insts->swap(insts);
-        t = old_tables;
-        if (two_level) tl_shapes[shape] = old_shape;
-    }
+    if (rc != PUPIL_OK && two_level) tl_shapes[shape] = old_shape;
     return rc;
 }
 
-int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, DevInstance *d_insts,
-                              std::vector<DevInstance> &insts, std::vector<uint32_t> &shape_of,
-                              const std::vector<ShapeDev> &shapes) {
-    const Tables old_tables = t;
+int SceneAccel::set_instances(Generation &staged, std::vector<uint32_t> &shape_of, const std::vector<ShapeDev> &shapes) {
+    const BuildOver scope(*this, staged);
     const std::vector<TwoLevelShape> old_shapes = tl_shapes;
-    t.num_prims = num_prims;
-    t.d_prim_inst = d_prim_inst;
-    t.d_insts = d_insts;
-    t.insts->swap(insts);
     inst_shape.swap(shape_of);
-    auto undo = [&](int rc) {
-        t.insts->swap(insts);
+    auto undo = [&](int rc) {  // of the structure's own inputs; the tables: `scope`
         inst_shape.swap(shape_of);
-        t = old_tables;
         tl_shapes = old_shapes;
         return rc;
     };
@@ -369,12 +351,12 @@ int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, D
         const int rc = update_flat({}, false, true);
         return rc != PUPIL_OK ? undo(rc) : rc;
     }
-    const uint32_t n = (uint32_t)t.insts->size();
+    const uint32_t n = (uint32_t)g().mirror.size();
     std::vector<uint8_t> used(tl_shapes.size(), 0);
     for (uint32_t i = 0; i < n; i++)
-        if ((*t.insts)[i].kind != PUPIL_SHAPE_SPHERE) used[inst_shape[i]] = 1;
+        if (g().mirror[i].kind != PUPIL_SHAPE_SPHERE) used[inst_shape[i]] = 1;
     // built with every instance shown, as create builds; the masks follow
-    std::vector<DevInstance> copy = *t.insts;
+    std::vector<DevInstance> copy = g().mirror;
     std::vector<uint32_t> hidden;
     for (uint32_t i = 0; i < n; i++)
         if (copy[i].hidden) {
@@ -384,7 +366,7 @@ int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, D
     TwoLevelAccel ntl{};
     int rc = -5;
     const bool stage_only = tl.world && used == tl.shape_used;
-    if (stage_only) rc = set_two_level_instances(tl_shapes, inst_shape, copy, t.d_insts, t.stream, tl, ntl);
+    if (stage_only) rc = set_two_level_instances(tl_shapes, inst_shape, copy, g().insts.get(), t.stream, tl, ntl);
     if (rc == 0) {
         last_whole_rebuild = 0;
     } else if (rc == -5) {
@@ -403,9 +385,9 @@ int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, D
             ts.indices = shapes[k].idx;
             if (shape_abs_max(tl, ts, &ts.vmax, t.stream) != 0) return undo(fail(PUPIL_ERR_HIP, "vertex reduction failed"));
         }
-        copy = *t.insts;
+        copy = g().mirror;
         for (uint32_t id : hidden) copy[id].hidden = 0u;
-        rc = build_two_level(tl_shapes, inst_shape, copy, t.d_insts, t.d_mats, leaf_size, t.stream, ntl);
+        rc = build_two_level(tl_shapes, inst_shape, copy, g().insts.get(), t.d_mats, leaf_size, t.stream, ntl);
     }
     auto drop = [&]() {
         if (last_whole_rebuild) free_two_level(ntl);
@@ -417,11 +399,11 @@ int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, D
         for (uint32_t id : hidden) {
             copy[id].hidden = 1u;
             staged.push_back(device_instance(copy[id]));
-            if (hipMemcpyAsync(t.d_insts + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice, t.stream) != hipSuccess)
+            if (hipMemcpyAsync(g().insts.get() + id, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice, t.stream) != hipSuccess)
                 rc = -1;
         }
         if (rc == 0)
-            rc = rebuild_tlas(ntl, copy, t.d_insts, hidden, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")));
+            rc = rebuild_tlas(ntl, copy, g().insts.get(), hidden, t.stream, !is_rebuild(std::getenv("PUPIL_TL_UPDATE")));
         if (rc != 0) (void)hipStreamSynchronize(t.stream);  // `staged` outlives its copies
     }
     rc = rc != 0 ? builder_error(rc, true, "two-level acceleration rebuild failed") : node_limit(nodes4_of(ntl));
@@ -435,7 +417,7 @@ int SceneAccel::set_instances(uint32_t num_prims, const uint32_t *d_prim_inst, D
     if (last_whole_rebuild) free_two_level(tl);
     else free_instance_stage(tl);
     tl = ntl;
-    *t.insts = copy;
+    g().mirror = copy;
     ms = tl.build_ms;
     return publish();
 }

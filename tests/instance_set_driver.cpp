@@ -1,7 +1,7 @@
 // instance_set_driver.cpp — csrc/host/instance_record.h on the host: the record assembly that
-// pupil_pt_set_instances' host mirror and the fill kernel (pt_instance_set.hip) share, against the
-// record pupil_pt_create's upload_tables writes (restated below, field by field) with the prim
-// offsets of host/prim_tables.h; the two-level fields stay as upload_tables leaves them.
+// pupil_pt_create, pupil_pt_set_instances' host mirror and the fill kernel (pt_instance_set.hip)
+// share, against the record's specification (restated below, field by field) with the prim
+// offsets of host/prim_tables.h; the two-level fields stay zero for the structure's instance stage.
 // Built with -fsanitize=address,undefined by test_instance_set_host.py: every table is sized
 // exactly, so an index past an end fails the run.
 #include <cmath>
@@ -36,7 +36,7 @@ struct Source {  // what a pupil_instance and its mask carry
     float to_world[12];
 };
 
-// what upload_tables (engine.hip) writes for instance `src`
+// the specification: the record of instance `src`, all zero outside the fields named here
 DevInstance reference(const Source &src, const InstShape &sh, uint32_t bin, uint32_t prim_offset, const float *to_object) {
     DevInstance d;
     std::memset(&d, 0, sizeof(d));

@@ -1,6 +1,6 @@
 // prim_tables_driver.cpp — csrc/host/prim_tables.h on the host: the prefix sums, the guide's
 // geometry and the lookup the fill kernel runs per primitive (pt_replace.hip), against the
-// tables pupil_pt_create builds from an explicit prim_inst array.  Built with
+// tables' specification, restated below from an explicit prim_inst array.  Built with
 // -fsanitize=address,undefined by test_prim_tables_host.py: every table is sized exactly, so
 // an index past an end fails the run.
 #include <algorithm>
@@ -24,7 +24,7 @@ int g_cases = 0;
         }                                                               \
     } while (0)
 
-// what upload_tables (engine.hip) builds at create
+// the specification: what every engine's tables must be, at create and after an update
 void reference(const std::vector<uint32_t> &counts, std::vector<uint32_t> &prim_inst, std::vector<uint32_t> &inst_first,
                std::vector<uint32_t> &inst_guide, uint32_t &shift) {
     prim_inst.clear();
