@@ -176,40 +176,11 @@ struct pupil_pt {
     std::vector<DevMaterial> h_mats;
     uint64_t mat_updates = 0;
     double mat_ms = 0.0;
-    DevEmitter *d_areas = nullptr, *d_env = nullptr;
-    float *d_cdf = nullptr;
-    uint32_t *d_guide = nullptr;
-    // the type of every entry of the emitter table (sc.num_areas of them): the triangle and sphere
-    // emitters [0, num_true_areas), which the instances' emitter ranges cover, then the delta lights
-    // -- point and spot, then directional -- which no primitive carries and no ray hits
-    std::vector<uint32_t> emit_types;
-    uint32_t num_true_areas = 0;
-    pupil_emitter env_src{};  // the env emitter the tables were built from (same_env)
-    bool env_src_valid = false;
-    // The env map from device memory (pupil_pt_update_env_device / _update_env_params).  h_env: the
-    // host mirror of *d_env as upload_emitters wrote it -- its type, size and device pointers;
-    // normalization is stale after a device update.  env_stale: env_src no longer describes the
-    // device (same_env answers false until the next upload_emitters).  d_env_sums: the row sums
-    // the table kernels pass between their stages (pt_envmap.hip), sized on first use
-    DevEmitter h_env{};
-    bool env_stale = false;
-    float *d_env_sums = nullptr;
-    uint32_t env_sums_cap = 0;
-    uint64_t env_updates = 0;
-    double env_ms = 0.0;  // host clock around the last update
-    std::vector<DevEmitter> h_emit_areas;  // host sources of in-place emitter updates
-    std::vector<float> h_emit_cdf;
-    std::vector<uint32_t> h_emit_guide;
-    // device-side emitter table (pupil_pt_enable_device_emitters): while dev_emit, vertex and
-    // transform updates of emissive instances rebuild the table from the engine's own arrays
-    // (pt_emitters.hip).  Per emitter its instance, per instance the select weight of its
-    // radiance, and the rebuild's scratch (weights, select probabilities, the weight sum)
-    bool dev_emit = false;
-    uint32_t dev_emit_count = 0;  // emitters the arrays below were sized for
-    uint32_t *d_emit_inst = nullptr;
-    float *d_inst_weight = nullptr, *d_emit_weight = nullptr, *d_emit_select = nullptr, *d_emit_sum = nullptr;
-    uint64_t emit_refreshes = 0;
-    double emit_ms = 0.0;  // host clock around the last rebuild
+    // the emitter state's one owner (host/emitter_tables.h); the successful pupil_pt_update_env_* calls
+    // and device-side rebuilds, and the host clock around the last one
+    EngineEmitters emitters;
+    uint64_t env_updates = 0, emit_refreshes = 0;
+    double env_ms = 0.0, emit_ms = 0.0;
     // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
     // and the event that orders a caller's stream before a device-to-device copy (vertices, texels)
     std::vector<ShapeDev> shapes;
@@ -277,13 +248,10 @@ struct pupil_pt {
     uint64_t replacements = 0;
     double replace_ms = 0.0;
     // instance tables replaced as a whole (pupil_pt_set_instances): the successful calls, what the
-    // last one built and the host clock around it; the host's copies of the device-side emitter
-    // bookkeeping (d_emit_inst, d_inst_weight), which a new table re-indexes
+    // last one built and the host clock around it
     uint64_t inst_sets = 0;
     uint32_t inst_set_blas_builds = 0, inst_set_whole = 0;
     double inst_set_ms = 0.0;
-    std::vector<uint32_t> h_emit_inst;
-    std::vector<float> h_inst_weight;
 
     template <typename T>
     hipError_t alloc(T **p, size_t count) {
@@ -343,29 +311,6 @@ struct pupil_pt {
 
 namespace {
 
-// everything of a texture but its texels (data stays null); refuses what no engine can sample
-int texture_desc(const pupil_texture &t, DevTexture &d) {
-    std::memset(&d, 0, sizeof(d));
-    d.type = t.type;
-    d.width = t.width;
-    d.height = t.height;
-    d.filter = t.filter;
-    for (int k = 0; k < 3; k++) {
-        d.c0[k] = t.c0[k];
-        d.c1[k] = t.c1[k];
-    }
-    for (int k = 0; k < 4; k++) {
-        d.r0[k] = t.transform[k];
-        d.r1[k] = t.transform[4 + k];
-    }
-    if (t.type == PUPIL_TEX_BITMAP) {
-        if (!t.rgba || !t.width || !t.height) return fail(PUPIL_ERR_INVALID, "bitmap texture without texels");
-    } else if (t.type > PUPIL_TEX_CHECKERBOARD) {
-        return fail(PUPIL_ERR_INVALID, "unknown texture type");
-    }
-    return PUPIL_OK;
-}
-
 int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
     if (const int rc = texture_desc(t, d)) return rc;
     if (t.type == PUPIL_TEX_BITMAP) {
@@ -373,187 +318,6 @@ int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
         HIP_TRY(pt->upload(&texels, reinterpret_cast<const float4 *>(t.rgba), (size_t)t.width * t.height));
         d.data = texels;
     }
-    return PUPIL_OK;
-}
-
-// EnvMap::Eval (env.h:58-62) lerps row_weight[row], row_weight[row + 1] with row <= h - 2,
-// and SampleDirect's column walk ends at w - 1: neither is defined for a one-texel side
-bool env_map_size_ok(uint32_t w, uint32_t h) { return w >= 2 && h >= 2; }
-
-int convert_emitter(pupil_pt *pt, const pupil_emitter &e, DevEmitter &d) {
-    std::memset(&d, 0, sizeof(d));
-    d.type = e.type;
-    d.select_probability = e.select_probability;
-    d.area = e.area;
-    d.radius = e.radius;
-    int rc = upload_texture(pt, e.radiance, d.radiance);
-    if (rc) return rc;
-    for (int k = 0; k < 3; k++) {
-        d.pos[k] = v3(e.pos[k][0], e.pos[k][1], e.pos[k][2]);
-        d.nrm[k] = v3(e.nrm[k][0], e.nrm[k][1], e.nrm[k][2]);
-        d.tex[k] = v2(e.tex[k][0], e.tex[k][1]);
-    }
-    d.center = v3(e.center[0], e.center[1], e.center[2]);
-    d.color = v3(e.color[0], e.color[1], e.color[2]);
-    d.scale = e.scale;
-    for (int k = 0; k < 9; k++) {
-        d.to_world[k] = e.to_world[k];
-        d.to_local[k] = e.to_local[k];
-    }
-    if (e.type == PUPIL_EMITTER_ENV_MAP) {
-        // BuildEnvMapCdfTable (world/emitter.cpp:107-149)
-        const pupil_texture &t = e.radiance;
-        if (t.type != PUPIL_TEX_BITMAP || !t.rgba) return fail(PUPIL_ERR_INVALID, "env map needs a bitmap");
-        const size_t w = t.width, h = t.height;
-        if (!env_map_size_ok(t.width, t.height)) return fail(PUPIL_ERR_INVALID, "env map smaller than 2 x 2 texels");
-        // One block col_cdf | row_cdf | row_weight | 0.0f, the reference's layout
-        // (world/emitter.cpp:364-375) plus a trailing zero.  SampleDirect's row index is h
-        // whenever xi.x > row_cdf[h - 1]: its column search then walks row_cdf, as in the
-        // reference, and row_weight[h] -- allocator padding there -- is the zero, so the
-        // sample has pdf 0.  The tail is never shorter than one column walk (w - 1 floats).
-        const size_t tail = std::max((h + 1) + h + 1, w);
-        std::vector<float> tables((w + 1) * h + tail, 0.f);
-        float *col_cdf = tables.data(), *row_cdf = col_cdf + (w + 1) * h, *row_weight = row_cdf + (h + 1);
-        size_t ci = 0, ri = 0;
-        float row_sum = 0.f;
-        row_cdf[ri++] = 0.f;
-        for (size_t y = 0; y < h; ++y) {
-            float col_sum = 0.f;
-            col_cdf[ci++] = 0.f;
-            for (size_t x = 0; x < w; ++x) {
-                const size_t pix = y * w + x;
-                col_sum += luminance(v3(t.rgba[pix * 4 + 0], t.rgba[pix * 4 + 1], t.rgba[pix * 4 + 2]));
-                col_cdf[ci++] = col_sum;
-            }
-            for (size_t x = 1; x < w; ++x) col_cdf[ci - x - 1] /= col_sum;
-            col_cdf[ci - 1] = 1.f;
-            const float weight = std::sin((y + 0.5f) * kPi / h);
-            row_weight[y] = weight;
-            row_sum += col_sum * weight;
-            row_cdf[ri++] = row_sum;
-        }
-        for (size_t y = 1; y < h; ++y) row_cdf[ri - y - 1] /= row_sum;
-        row_cdf[ri - 1] = 1.f;
-        d.normalization = 1.f / (row_sum * (2.f * kPi / w) * (kPi / h));
-        d.map_w = (uint32_t)w;
-        d.map_h = (uint32_t)h;
-        float *block = nullptr;
-        HIP_TRY(pt->upload(&block, tables.data(), tables.size()));
-        d.col_cdf = block;
-        d.row_cdf = block + (row_cdf - col_cdf);
-        d.row_weight = block + (row_weight - col_cdf);
-    }
-    return PUPIL_OK;
-}
-
-// EmitterGroup (render/emitter.h:110-135): the area emitters, their sequential selection
-// CDF and its guide table (2^bits >= emitter count buckets, at most 2^20, guide[k] = first
-// i with cdf[i] >= k / 2^bits; empty for PUPIL_EMITTER_SELECT=binary, the plain binary
-// search A/B, or fewer than two emitters).  Bitmap radiance textures are uploaded here.
-// The table's shape: each entry's type, and the number of triangle and sphere emitters in front.
-// The table must be in SelectOneEmiiter's scan order (render/emitter.h:110-135): areas, points
-// (point and spot lights), directionals.
-int emitter_table_shape(const pupil_scene_desc *scene, std::vector<uint32_t> &types, uint32_t &true_areas) {
-    types.resize(scene->num_area_emitters);
-    true_areas = 0;
-    uint32_t stage = 0;  // 0 areas, 1 points, 2 directionals
-    for (uint32_t e = 0; e < scene->num_area_emitters; e++) {
-        const uint32_t t = scene->area_emitters[e].type;
-        uint32_t s;
-        if (t == PUPIL_EMITTER_TRI_AREA || t == PUPIL_EMITTER_SPHERE) s = 0;
-        else if (t == PUPIL_EMITTER_POINT || t == PUPIL_EMITTER_SPOT) s = 1;
-        else if (t == PUPIL_EMITTER_DIRECTIONAL) s = 2;
-        else return fail(PUPIL_ERR_INVALID, "emitter table entry of an unknown or env type");
-        if (s < stage) return fail(PUPIL_ERR_INVALID, "emitter table out of order: areas, point / spot, directional");
-        stage = s;
-        true_areas += s == 0 ? 1u : 0u;
-        types[e] = t;
-    }
-    return PUPIL_OK;
-}
-
-int emitter_tables(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<DevEmitter> &areas, std::vector<float> &cdf,
-                   std::vector<uint32_t> &guide, uint32_t &bits) {
-    areas.assign(scene->num_area_emitters, DevEmitter{});
-    cdf.assign(scene->num_area_emitters, 0.f);
-    float sum_p = 0.f;
-    for (uint32_t e = 0; e < scene->num_area_emitters; e++) {
-        int rc = convert_emitter(pt, scene->area_emitters[e], areas[e]);
-        if (rc) return rc;
-        cdf[e] = sum_p + areas[e].select_probability;
-        sum_p = cdf[e];
-    }
-    bits = 0;
-    while ((1u << bits) < scene->num_area_emitters && bits < 20) bits++;
-    const char *sel = std::getenv("PUPIL_EMITTER_SELECT");
-    guide.clear();
-    if (scene->num_area_emitters > 1 && !(sel && std::strcmp(sel, "binary") == 0)) {
-        const uint32_t m = 1u << bits;
-        guide.resize(m + 1);
-        uint32_t i = 0;
-        for (uint32_t k = 0; k <= m; k++) {
-            const float t = (float)k / (float)m;
-            while (i < cdf.size() && cdf[i] < t) i++;
-            guide[k] = i;
-        }
-    }
-    return PUPIL_OK;
-}
-
-// the scene's env emitter is the one the engine holds (an update may then keep its tables)
-bool same_env(const pupil_pt *pt, const pupil_scene_desc *scene) {
-    const bool has = scene->env && scene->env->type != PUPIL_EMITTER_NONE;
-    if (has != pt->env_src_valid) return false;
-    if (pt->env_stale) return false;  // texels or parameters came from pupil_pt_update_env_*: env_src is not the device's
-    return !has || std::memcmp(&pt->env_src, scene->env, sizeof(pupil_emitter)) == 0;
-}
-
-// replaces the previous tables (creation, and updates that change their shapes)
-int upload_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
-    std::vector<DevEmitter> areas;
-    std::vector<float> cdf;
-    std::vector<uint32_t> g;
-    uint32_t bits = 0;
-    std::vector<uint32_t> types;
-    uint32_t true_areas = 0;
-    if (const int rc = emitter_table_shape(scene, types, true_areas)) return rc;
-    if (const int rc = emitter_tables(pt, scene, areas, cdf, g, bits)) return rc;
-    DevEmitter *d_areas = nullptr, *d_env = nullptr;
-    float *d_cdf = nullptr;
-    uint32_t *d_guide = nullptr;
-    if (pt->upload(&d_areas, areas.data(), areas.size()) || pt->upload(&d_cdf, cdf.data(), cdf.size()))
-        return fail(PUPIL_ERR_OOM, "emitter upload failed");
-    if (!g.empty() && pt->upload(&d_guide, g.data(), g.size())) return fail(PUPIL_ERR_OOM, "emitter guide upload failed");
-    pt->env_src_valid = false;
-    DevEmitter h_env{};
-    if (scene->env && scene->env->type != PUPIL_EMITTER_NONE) {
-        pt->env_src = *scene->env;
-        pt->env_src_valid = true;
-        DevEmitter env;
-        int rc = convert_emitter(pt, *scene->env, env);
-        if (rc) return rc;
-        if (pt->upload(&d_env, &env, 1)) return fail(PUPIL_ERR_OOM, "env upload failed");
-        h_env = env;
-    }
-    pt->release(pt->d_areas);
-    pt->release(pt->d_cdf);
-    pt->release(pt->d_env);
-    pt->release(pt->d_guide);
-    pt->d_areas = d_areas;
-    pt->d_cdf = d_cdf;
-    pt->d_guide = d_guide;
-    pt->sc.area_guide = d_guide;
-    pt->sc.guide_bits = bits;
-    pt->d_env = d_env;
-    pt->h_env = h_env;
-    pt->env_stale = false;  // env_src describes the device again
-    pt->sc.areas = d_areas;
-    pt->sc.area_cdf = d_cdf;
-    pt->sc.num_areas = scene->num_area_emitters;
-    pt->emit_types.swap(types);
-    pt->num_true_areas = true_areas;
-    pt->sc.has_env = d_env ? 1u : 0u;
-    pt->sc.env = d_env;
     return PUPIL_OK;
 }
 
@@ -1156,7 +920,7 @@ int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std
                           std::vector<float> &inst_weight) {
     // ne: the triangle and sphere emitters, which the ranges must cover; the delta lights behind
     // them (the rebuild leaves them as they are) must be the engine's, type for type
-    const uint32_t ni = (uint32_t)pt->h_insts().size(), ne = pt->num_true_areas;
+    const uint32_t ni = (uint32_t)pt->h_insts().size(), ne = pt->emitters.cur().num_true_areas;
     if (scene->num_instances != ni) return fail(PUPIL_ERR_INVALID, "the scene's instance count is not the engine's");
     if (scene->num_area_emitters != pt->sc.num_areas)
         return fail(PUPIL_ERR_INVALID, "the scene's area emitter count is not the engine's");
@@ -1165,7 +929,7 @@ int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std
     for (uint32_t e = 0; e < pt->sc.num_areas; e++) {
         const uint32_t t = scene->area_emitters[e].type;
         const bool delta = t >= PUPIL_EMITTER_POINT && t <= PUPIL_EMITTER_DIRECTIONAL;
-        if (delta != (e >= ne) || (delta && t != pt->emit_types[e]))
+        if (delta != (e >= ne) || (delta && t != pt->emitters.cur().types[e]))
             return fail(PUPIL_ERR_INVALID, "the scene's delta lights are not the engine's");
     }
     emit_inst.assign(ne, 0u);
@@ -1187,30 +951,18 @@ int device_emitter_tables(const pupil_pt *pt, const pupil_scene_desc *scene, std
     return PUPIL_OK;
 }
 
-// validates `scene` against the engine, then uploads the bookkeeping (the engine's stream is idle
-// or ordered by the caller; the copies are synchronous)
+// validates `scene` against the engine, then stages the bookkeeping aside (synchronous copies into
+// fresh arrays) and adopts it; after a refusal or failure the bookkeeping and the mode are what they were
 int device_emitter_setup(pupil_pt *pt, const pupil_scene_desc *scene) {
     std::vector<uint32_t> emit_inst;
     std::vector<float> inst_weight;
     if (const int rc = device_emitter_tables(pt, scene, emit_inst, inst_weight)) return rc;
     // sized for the whole table: the select scratch and the CDF chain span the delta lights too
-    const uint32_t ne = pt->sc.num_areas;
-    if (!pt->d_emit_inst || pt->dev_emit_count != ne) {
-        for (void *p : {(void *)pt->d_emit_inst, (void *)pt->d_emit_weight, (void *)pt->d_emit_select}) pt->release(p);
-        pt->d_emit_inst = nullptr;
-        pt->d_emit_weight = pt->d_emit_select = nullptr;
-        if (pt->alloc(&pt->d_emit_inst, ne) || pt->alloc(&pt->d_emit_weight, ne) || pt->alloc(&pt->d_emit_select, ne))
-            return fail(PUPIL_ERR_OOM, "emitter bookkeeping allocation failed");
-        pt->dev_emit_count = ne;
-    }
-    if (!pt->d_inst_weight && (pt->alloc(&pt->d_inst_weight, inst_weight.size()) || pt->alloc(&pt->d_emit_sum, 1)))
-        return fail(PUPIL_ERR_OOM, "emitter bookkeeping allocation failed");
-    if (!emit_inst.empty())  // one entry per triangle or sphere emitter
-        HIP_TRY(hipMemcpy(pt->d_emit_inst, emit_inst.data(), sizeof(uint32_t) * emit_inst.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pt->d_inst_weight, inst_weight.data(), sizeof(float) * inst_weight.size(), hipMemcpyHostToDevice));
-    pt->h_emit_inst = emit_inst;
-    pt->h_inst_weight = inst_weight;
-    return PUPIL_OK;
+    EngineEmitters::Bookkeeping staged;
+    staged.enabled = pt->emitters.book().enabled;
+    const int rc = EngineEmitters::Bookkeeping::stage(std::move(emit_inst), std::move(inst_weight), pt->sc.num_areas, staged);
+    if (!rc) pt->emitters.book() = std::move(staged);
+    return rc;
 }
 
 // the rebuild (pt_emitters.hip) on the engine's stream, which the caller has ordered after the
@@ -1218,19 +970,21 @@ int device_emitter_setup(pupil_pt *pt, const pupil_scene_desc *scene) {
 int rebuild_emitters(pupil_pt *pt) {
     const auto t0 = std::chrono::steady_clock::now();
     EmitterJob job{};
-    job.areas = pt->d_areas;
-    job.cdf = pt->d_cdf;
-    job.guide = pt->d_guide;
-    job.guide_bits = pt->sc.guide_bits;
-    job.count = pt->num_true_areas;
+    const EngineEmitters::Generation &g = pt->emitters.cur();
+    const EngineEmitters::Bookkeeping &book = pt->emitters.book();
+    job.areas = g.areas.get();
+    job.cdf = g.cdf.get();
+    job.guide = g.guide.get();
+    job.guide_bits = g.guide_bits;
+    job.count = g.num_true_areas;
     job.total = pt->sc.num_areas;
     job.emitter_num = pt->sc.num_areas + (pt->sc.has_env ? 1u : 0u);
     job.instances = pt->d_insts();
-    job.emit_inst = pt->d_emit_inst;
-    job.inst_weight = pt->d_inst_weight;
-    job.weight = pt->d_emit_weight;
-    job.select = pt->d_emit_select;
-    job.sum = pt->d_emit_sum;
+    job.emit_inst = book.emit_inst.get();
+    job.inst_weight = book.inst_weight.get();
+    job.weight = book.weight.get();
+    job.select = book.select.get();
+    job.sum = book.sum.get();
     launch_emitter_rebuild(job, pt->own_stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
@@ -1246,9 +1000,9 @@ int rebuild_emitters(pupil_pt *pt) {
 // still describes the engine's emitter ranges (its radiance weights are taken anew), else it goes
 // off and pupil_last_error says so; the update itself has succeeded either way
 int keep_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
-    if (!pt->dev_emit) return PUPIL_OK;
+    if (!pt->emitters.book().enabled) return PUPIL_OK;
     if (device_emitter_setup(pt, scene) != PUPIL_OK) {
-        pt->dev_emit = false;
+        pt->emitters.book().enabled = false;
         g_last_error = "device-side emitter table switched off: " + g_last_error;
     }
     return PUPIL_OK;
@@ -1300,7 +1054,7 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     if (!rc) rc = upload_shapes(pt, scene);
     if (!rc) rc = convert_materials(pt, scene, mats);
     if (!rc) rc = upload_tables(pt, scene, mats);
-    if (!rc) rc = upload_emitters(pt, scene);
+    if (!rc) rc = pt->emitters.update(scene, pt->own_stream, pt->sc);
     if (!rc) rc = pt->accel.build({pt->own_stream, &pt->tables, pt->d_mats, &pt->sc, &pt->totals}, scene, pt->shapes);
     if (!rc) read_knobs(pt);
     if (!rc) rc = alloc_workspace(pt);
@@ -1382,7 +1136,7 @@ int pupil_pt_update_instances_masked(pupil_pt *pt, uint32_t n, const uint32_t *i
     if (const int rc = pt->accel.update_instances(changed)) return rc;
     pt->totals.build_ms = pt->accel.ms;
     if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
-    if (pt->dev_emit && emitters_moved) return rebuild_emitters(pt);
+    if (pt->emitters.book().enabled && emitters_moved) return rebuild_emitters(pt);
     return PUPIL_OK;
 }
 
@@ -1405,7 +1159,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
             changed.push_back(i);
             emissive = emissive || pt->h_insts()[i].emitter_offset >= 0;
         }
-    if (device && emissive && !pt->dev_emit)
+    if (device && emissive && !pt->emitters.book().enabled)
         return fail(PUPIL_ERR_UNSUPPORTED, "device vertices of an emissive shape: the emitter table needs the host path");
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
@@ -1427,7 +1181,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     }
     pt->accel.refits++;  // only once the structure has followed: a failed update does not count
     if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
-    if (pt->dev_emit && emissive) return rebuild_emitters(pt);
+    if (pt->emitters.book().enabled && emissive) return rebuild_emitters(pt);
     return PUPIL_OK;
 }
 
@@ -1627,7 +1381,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
             return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances reordered or rebound: the emitter table would change");
         if (!device && (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) != 0 ||
                         std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) != 0)) {
-            if (!pt->dev_emit)
+            if (!pt->emitters.book().enabled)
                 return fail(PUPIL_ERR_UNSUPPORTED, "an emissive instance moved: the emitter table needs the device-side mode");
             emitters_moved = true;
         }
@@ -1645,14 +1399,17 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     // limits refuse the call before anything is allocated; from there a failure lets the stream pass
     EngineTables::Generation gen;
     if (const int rc = EngineTables::stage(counts.data(), n, !two_level, s, gen)) return drained(s, rc);
-    ScratchBuf<uint32_t> emit_inst;
     ScratchBuf<InstBinding> d_bind;
     ScratchBuf<InstShape> d_shapes;
-    ScratchBuf<float> xf, inst_weight;
-    const bool remap = pt->dev_emit && pt->d_inst_weight;
-    if (d_bind.alloc(n) || d_shapes.alloc(shape_tab.size()) || (!device && xf.alloc(24 * (size_t)n)) ||
-        (remap && (emit_inst.alloc(pt->dev_emit_count) || inst_weight.alloc(n))))
+    ScratchBuf<float> xf;
+    if (d_bind.alloc(n) || d_shapes.alloc(shape_tab.size()) || (!device && xf.alloc(24 * (size_t)n)))
         return drained(s, fail(PUPIL_ERR_OOM, "instance table: allocation failed"));
+    // the device-side emitter bookkeeping: the emitters' instances under their new indices
+    EngineEmitters::Bookkeeping book;
+    const bool remap = pt->emitters.book().enabled;
+    if (remap)
+        if (const int rc = pt->emitters.book().restage(old_em, new_em, n, book, "instance table: allocation failed"))
+            return drained(s, rc);
     std::vector<float> h_xf;  // host path: n to_world, then n to_object; outlives the copy (the build synchronises)
     if (device) {
         HIP_TRY_DRAINED(s, order_after_caller(pt, hip_stream));
@@ -1689,7 +1446,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
             if (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) == 0 &&
                 std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) == 0)
                 continue;
-            if (!pt->dev_emit)
+            if (!pt->emitters.book().enabled)
                 return fail(PUPIL_ERR_UNSUPPORTED, "an emissive instance moved: the emitter table needs the device-side mode");
             emitters_moved = true;
         }
@@ -1698,47 +1455,18 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
             fill_instance_record(gen.mirror[i], shape_tab[bind[i].shape], bind[i], gen.first[i], instances[i].to_world,
                                  instances[i].to_object, false);
     }
-    std::vector<uint32_t> h_emit_inst;
-    std::vector<float> h_inst_weight;
-    if (remap) {  // the emitters' instances under their new indices
-        h_emit_inst = pt->h_emit_inst;
-        h_inst_weight.assign(n, 0.f);
-        std::vector<uint32_t> to_new(old_n, 0u);
-        for (size_t k = 0; k < old_em.size(); k++) {
-            to_new[old_em[k]] = new_em[k];
-            h_inst_weight[new_em[k]] = pt->h_inst_weight[old_em[k]];
-        }
-        for (uint32_t &e : h_emit_inst) e = to_new[e];
-        if (!h_emit_inst.empty())
-            HIP_TRY_DRAINED(s, hipMemcpyAsync(emit_inst.get(), h_emit_inst.data(), sizeof(uint32_t) * h_emit_inst.size(),
-                                   hipMemcpyHostToDevice, s));
-        HIP_TRY_DRAINED(s, hipMemcpyAsync(inst_weight.get(), h_inst_weight.data(), sizeof(float) * n, hipMemcpyHostToDevice, s));
-    }
     // ---- build: after the renders enqueued so far (the swap below frees what they read)
     HIP_TRY_DRAINED(s, order_after_renders(pt));
     if (const int rc = pt->accel.set_instances(gen, new_shape, pt->shapes)) return drained(s, rc);
     // ---- swap: the structure is published and the stream idle
     pt->pipe.invalidate();  // frames in flight were traced against the old table
     drop_stale(pt, true, true);
-    if (remap) {
-        pt->release(pt->d_emit_inst);
-        pt->release(pt->d_inst_weight);
-        pt->allocs.push_back(emit_inst.get());
-        pt->allocs.push_back(inst_weight.get());
-        pt->d_emit_inst = emit_inst.release();
-        pt->d_inst_weight = inst_weight.release();
-        pt->h_emit_inst.swap(h_emit_inst);
-        pt->h_inst_weight.swap(h_inst_weight);
-    } else if (pt->d_inst_weight) {  // switched off: the next enable sizes its bookkeeping anew
-        pt->release(pt->d_inst_weight);
-        pt->release(pt->d_emit_sum);
-        pt->d_inst_weight = pt->d_emit_sum = nullptr;
-    }
+    pt->emitters.book() = std::move(book);  // switched off: dropped, the next enable sizes its bookkeeping anew
     pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
     pt->accel.refits++;
     derive_bins(pt);
     if (const int rc = derive_cull_set(pt)) return rc;  // the build moved the records
-    if (pt->dev_emit && !old_em.empty())
+    if (pt->emitters.book().enabled && !old_em.empty())
         if (const int rc = rebuild_emitters(pt)) return rc;
     pt->inst_sets++;
     pt->inst_set_blas_builds = pt->accel.last_blas_builds;
@@ -1840,7 +1568,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
         changed.push_back(id);
         emissive = emissive || pt->h_insts()[id].emitter_offset >= 0;
     }
-    if (emissive && !pt->dev_emit)
+    if (emissive && !pt->emitters.book().enabled)
         return fail(PUPIL_ERR_UNSUPPORTED,
                     "device transforms of an emissive instance: the emitter table needs the host path");
     HIP_TRY(order_after_renders(pt));  // no render may still read the old tables
@@ -1892,7 +1620,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
         pt->accel.refits++;  // as the host entry: once the tables have changed
         if (const int rc = pt->accel.move_finish(changed, n)) return rc;
         if (const int rc = derive_cull_set(pt)) return rc;  // a rebuild moves the records
-        if (pt->dev_emit && emissive)
+        if (pt->emitters.book().enabled && emissive)
             if (const int rc = rebuild_emitters(pt)) return rc;
     }
     pt->inst_dev_updates++;
@@ -1947,39 +1675,7 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
     pt->pipe.invalidate();
-    // the table's shape: its counts and, entry by entry, its types (a light added, removed or turned
-    // from point to directional changes it; a light moved, recoloured or re-aimed does not)
-    std::vector<uint32_t> types;
-    uint32_t true_areas = 0;
-    if (const int rc = emitter_table_shape(scene, types, true_areas)) return rc;
-    bool in_place = pt->d_areas && types == pt->emit_types && same_env(pt, scene);
-    for (uint32_t e = 0; in_place && e < scene->num_area_emitters; e++)
-        in_place = scene->area_emitters[e].radiance.type != PUPIL_TEX_BITMAP;
-    if (in_place) {
-        std::vector<DevEmitter> areas;
-        std::vector<float> cdf;
-        std::vector<uint32_t> guide;
-        uint32_t bits = 0;
-        if (const int rc = emitter_tables(pt, scene, areas, cdf, guide, bits)) return rc;
-        if (guide.empty() == (pt->d_guide != nullptr) || bits != pt->sc.guide_bits) in_place = false;
-        if (in_place) {
-            pt->h_emit_areas.swap(areas);  // kept alive until the copies have run (synchronised below)
-            pt->h_emit_cdf.swap(cdf);
-            pt->h_emit_guide.swap(guide);
-            HIP_TRY(hipMemcpyAsync(pt->d_areas, pt->h_emit_areas.data(), sizeof(DevEmitter) * pt->h_emit_areas.size(),
-                                   hipMemcpyHostToDevice, pt->own_stream));
-            HIP_TRY(hipMemcpyAsync(pt->d_cdf, pt->h_emit_cdf.data(), sizeof(float) * pt->h_emit_cdf.size(),
-                                   hipMemcpyHostToDevice, pt->own_stream));
-            if (pt->d_guide)
-                HIP_TRY(hipMemcpyAsync(pt->d_guide, pt->h_emit_guide.data(), sizeof(uint32_t) * pt->h_emit_guide.size(),
-                                       hipMemcpyHostToDevice, pt->own_stream));
-            HIP_TRY(hipStreamSynchronize(pt->own_stream));
-            if (const int rc = derive_cull_set(pt, false)) return rc;
-            return keep_device_emitters(pt, scene);
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(pt->own_stream));  // the old tables are freed below
-    if (const int rc = upload_emitters(pt, scene)) return rc;
+    if (const int rc = pt->emitters.update(scene, pt->own_stream, pt->sc)) return rc;
     if (const int rc = derive_cull_set(pt, false)) return rc;  // the scene may have gained or lost its env emitter
     return keep_device_emitters(pt, scene);
 }
@@ -1987,28 +1683,23 @@ int pupil_pt_update_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
 int pupil_pt_enable_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
     if (!scene) {
-        pt->dev_emit = false;
+        pt->emitters.book().enabled = false;
         return PUPIL_OK;
     }
     HIP_TRY(hipSetDevice(pt->device));
-    // everything that can refuse the scene runs before anything of the engine changes
-    {
-        std::vector<uint32_t> emit_inst;
-        std::vector<float> inst_weight;
-        if (const int rc = device_emitter_tables(pt, scene, emit_inst, inst_weight)) return rc;
-    }
+    // everything that can refuse the scene runs before anything of the engine changes (no render reads the bookkeeping)
+    if (const int rc = device_emitter_setup(pt, scene)) return rc;
     HIP_TRY(order_after_renders(pt));  // no render may still read the table
     pt->pipe.invalidate();
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
-    if (const int rc = device_emitter_setup(pt, scene)) return rc;
     if (const int rc = rebuild_emitters(pt)) return rc;
-    pt->dev_emit = true;
+    pt->emitters.book().enabled = true;
     return PUPIL_OK;
 }
 
 int pupil_pt_refresh_emitters(pupil_pt *pt) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (!pt->dev_emit) return fail(PUPIL_ERR_INVALID, "the device-side emitter table is not enabled");
+    if (!pt->emitters.book().enabled) return fail(PUPIL_ERR_INVALID, "the device-side emitter table is not enabled");
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
     pt->pipe.invalidate();  // frames in flight were shaded with the old table
@@ -2017,7 +1708,7 @@ int pupil_pt_refresh_emitters(pupil_pt *pt) {
 
 int pupil_pt_device_emitters_info(pupil_pt *pt, uint32_t *enabled, uint64_t *refreshes, double *last_ms) {
     if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (enabled) *enabled = pt->dev_emit ? 1u : 0u;
+    if (enabled) *enabled = pt->emitters.book().enabled ? 1u : 0u;
     if (refreshes) *refreshes = pt->emit_refreshes;
     if (last_ms) *last_ms = pt->emit_ms;
     return PUPIL_OK;
@@ -2149,18 +1840,6 @@ int pupil_pt_material_info(pupil_pt *pt, uint64_t *updates, double *last_ms) {
     return PUPIL_OK;
 }
 
-extern "C++" {
-namespace {
-// the engine holds an env map (not a constant env, not none) the two entries below can rewrite
-int env_map_held(const pupil_pt *pt) {
-    const DevEmitter &e = pt->h_env;
-    if (!pt->d_env || e.type != PUPIL_EMITTER_ENV_MAP || !e.radiance.data || !e.col_cdf)
-        return fail(PUPIL_ERR_INVALID, "the scene has no env map: give it one with pupil_pt_update_emitters first");
-    return PUPIL_OK;
-}
-}  // namespace
-}  // extern "C++"
-
 // The texels of the env map from device memory, ordered like pupil_pt_update_texture_device: an
 // event on the caller's stream, the engine's stream waits for it, then the copy device to device
 // into the engine's own texels and the two table stages of pt_envmap.hip, which rewrite col_cdf,
@@ -2169,34 +1848,13 @@ int env_map_held(const pupil_pt *pt) {
 int pupil_pt_update_env_device(pupil_pt *pt, const void *rgba_device, uint32_t width, uint32_t height,
                                void *hip_stream) {
     if (!pt || !rgba_device) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (const int rc = env_map_held(pt)) return rc;
-    const DevEmitter &e = pt->h_env;
-    if (e.map_w != width || e.map_h != height)
-        return fail(PUPIL_ERR_INVALID, "the env map is " + std::to_string(e.map_w) + " x " + std::to_string(e.map_h) +
-                                           ": set the size with pupil_pt_update_emitters first");
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
-    if (pt->env_sums_cap < height) {  // the first call, or the first since the map grew
-        float *sums = nullptr;
-        if (pt->alloc(&sums, height) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(PUPIL_ERR_OOM, "env scratch allocation failed");
-        }
-        pt->release(pt->d_env_sums);  // no kernel reads it: every call returns behind its own
-        pt->d_env_sums = sums;
-        pt->env_sums_cap = height;
-    }
+    if (const int rc = pt->emitters.reserve_env_texels(width, height)) return rc;
     HIP_TRY(order_after_renders(pt));  // no render may still read the old texels and tables
     pt->pipe.invalidate();
-    pt->env_stale = true;  // from here env_src no longer describes the device
     HIP_TRY(order_after_caller(pt, hip_stream));
-    HIP_TRY(hipMemcpyAsync((void *)e.radiance.data, rgba_device, sizeof(float4) * (size_t)width * height,
-                           hipMemcpyDeviceToDevice, pt->own_stream));
-    launch_env_tables({e.radiance.data, width, height, const_cast<float *>(e.col_cdf), const_cast<float *>(e.row_cdf),
-                       e.row_weight, pt->d_env_sums, pt->d_env},
-                      pt->own_stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (const int rc = pt->emitters.write_env_texels(rgba_device, pt->own_stream)) return rc;
     pt->env_updates++;
     pt->env_ms = ms_since(t0);
     return PUPIL_OK;
@@ -2205,22 +1863,12 @@ int pupil_pt_update_env_device(pupil_pt *pt, const void *rgba_device, uint32_t w
 // scale, to_world and to_local of the device's env emitter: two small copies, no table, no texel
 int pupil_pt_update_env_params(pupil_pt *pt, float scale, const float to_world[9], const float to_local[9]) {
     if (!pt || !to_world || !to_local) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (const int rc = env_map_held(pt)) return rc;
-    static_assert(offsetof(DevEmitter, to_local) == offsetof(DevEmitter, to_world) + 9 * sizeof(float),
-                  "to_world and to_local go up in one copy");
+    if (const int rc = pt->emitters.env_map_held()) return rc;
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(order_after_renders(pt));  // no render may still read the old parameters
     pt->pipe.invalidate();
-    pt->env_stale = true;
-    DevEmitter &e = pt->h_env;  // outlives the copies (synchronised below)
-    e.scale = scale;
-    std::memcpy(e.to_world, to_world, sizeof(e.to_world));
-    std::memcpy(e.to_local, to_local, sizeof(e.to_local));
-    HIP_TRY(hipMemcpyAsync(&pt->d_env->scale, &e.scale, sizeof(float), hipMemcpyHostToDevice, pt->own_stream));
-    HIP_TRY(hipMemcpyAsync(pt->d_env->to_world, e.to_world, sizeof(e.to_world) + sizeof(e.to_local), hipMemcpyHostToDevice,
-                           pt->own_stream));
-    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (const int rc = pt->emitters.write_env_params(scale, to_world, to_local, pt->own_stream)) return rc;
     pt->env_updates++;
     pt->env_ms = ms_since(t0);
     return PUPIL_OK;
@@ -3030,8 +2678,8 @@ int pupil_debug_read_emitters(pupil_pt *pt, uint32_t first, uint32_t n, float *o
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     std::vector<DevEmitter> areas(n);
     std::vector<float> cdf(n);
-    HIP_TRY(hipMemcpy(areas.data(), pt->d_areas + first, sizeof(DevEmitter) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cdf.data(), pt->d_cdf + first, sizeof(float) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(areas.data(), pt->emitters.cur().areas.get() + first, sizeof(DevEmitter) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cdf.data(), pt->emitters.cur().cdf.get() + first, sizeof(float) * n, hipMemcpyDeviceToHost));
     for (uint32_t e = 0; e < n; e++) {
         const DevEmitter &d = areas[e];
         float *o = out + 24 * (size_t)e;
@@ -3064,14 +2712,15 @@ int pupil_debug_shade_tables(pupil_pt *pt, uint32_t caps[4], uint32_t *fit) {
 
 int pupil_debug_read_emitter_guide(pupil_pt *pt, uint32_t *bits, uint32_t *guide, uint32_t *inout_count) {
     if (!pt || !inout_count) return fail(PUPIL_ERR_INVALID, "null argument");
-    const uint32_t count = pt->d_guide ? (1u << pt->sc.guide_bits) + 1u : 0u;
-    if (bits) *bits = pt->sc.guide_bits;
+    const EngineEmitters::Generation &g = pt->emitters.cur();
+    const uint32_t count = g.guide.get() ? (1u << g.guide_bits) + 1u : 0u;
+    if (bits) *bits = g.guide_bits;
     if (guide && count) {
         if (*inout_count < count) return fail(PUPIL_ERR_INVALID, "output too small");
         HIP_TRY(hipSetDevice(pt->device));
         HIP_TRY(order_after_renders(pt));
         HIP_TRY(hipStreamSynchronize(pt->own_stream));
-        HIP_TRY(hipMemcpy(guide, pt->d_guide, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(guide, g.guide.get(), sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
     }
     *inout_count = count;
     return PUPIL_OK;
@@ -3105,7 +2754,7 @@ int debug_probe(pupil_pt *pt, uint32_t n, const float *in, uint32_t in_w, float 
 int pupil_debug_env(pupil_pt *pt, uint32_t n, const float *xi_or_dir, const float *pos_nrm, uint32_t mode, float *out) {
     if (!pt || !xi_or_dir || !pos_nrm || !out) return fail(PUPIL_ERR_INVALID, "null argument");
     if (mode > 1u) return fail(PUPIL_ERR_INVALID, "unknown mode");
-    if (!pt->sc.has_env || !pt->d_env) return fail(PUPIL_ERR_INVALID, "the scene has no env emitter");
+    if (!pt->emitters.cur().env.get()) return fail(PUPIL_ERR_INVALID, "the scene has no env emitter");
     if (n == 0) return PUPIL_OK;
     if (mode == 0u)  // the CDF searches take random numbers: anything else is not an input of SampleDirect
         for (uint32_t i = 0; i < n; i++)
@@ -3121,12 +2770,12 @@ int pupil_debug_emitter_sample(pupil_pt *pt, uint32_t emitter, uint32_t n, const
     if (!pt || !xi || !pos_nrm || !out) return fail(PUPIL_ERR_INVALID, "null argument");
     if (emitter > pt->sc.num_areas) return fail(PUPIL_ERR_INVALID, "emitter index beyond the env's");
     const bool env = emitter == pt->sc.num_areas;
-    if (env && (!pt->sc.has_env || !pt->d_env)) return fail(PUPIL_ERR_INVALID, "the scene has no env emitter");
+    if (env && !pt->emitters.cur().env.get()) return fail(PUPIL_ERR_INVALID, "the scene has no env emitter");
     if (n == 0) return PUPIL_OK;
     for (uint32_t i = 0; i < n; i++)  // the CDF searches take random numbers (pupil_debug_env)
         if (!(xi[3 * i] >= 0.f && xi[3 * i] <= 1.f && xi[3 * i + 1] >= 0.f && xi[3 * i + 1] <= 1.f))
             return fail(PUPIL_ERR_INVALID, "xi outside [0, 1]");
-    const DevEmitter *e = env ? pt->d_env : pt->d_areas + emitter;
+    const DevEmitter *e = env ? pt->emitters.cur().env.get() : pt->emitters.cur().areas.get() + emitter;
     return debug_probe(pt, n, xi, 3, out, 8, [&](const float *din, float *dout) {
         launch_debug_emitter_sample(e, din, pos_nrm, dout, n, pt->own_stream);
     });
@@ -3135,8 +2784,8 @@ int pupil_debug_emitter_sample(pupil_pt *pt, uint32_t emitter, uint32_t n, const
 int pupil_debug_read_env_tables(pupil_pt *pt, uint32_t *width, uint32_t *height, float *col_cdf, float *row_cdf,
                                 float *row_weight, float *normalization) {
     if (!pt || !width || !height) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (const int rc = env_map_held(pt)) return rc;
-    const DevEmitter &e = pt->h_env;
+    if (const int rc = pt->emitters.env_map_held()) return rc;
+    const DevEmitter &e = pt->emitters.cur().h_env;
     const size_t w = e.map_w, h = e.map_h;
     *width = e.map_w;
     *height = e.map_h;
@@ -3148,7 +2797,7 @@ int pupil_debug_read_env_tables(pupil_pt *pt, uint32_t *width, uint32_t *height,
     if (row_cdf) HIP_TRY(hipMemcpy(row_cdf, e.row_cdf, sizeof(float) * (h + 1), hipMemcpyDeviceToHost));
     if (row_weight) HIP_TRY(hipMemcpy(row_weight, e.row_weight, sizeof(float) * h, hipMemcpyDeviceToHost));
     if (normalization)
-        HIP_TRY(hipMemcpy(normalization, &pt->d_env->normalization, sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(normalization, &pt->emitters.cur().env.get()->normalization, sizeof(float), hipMemcpyDeviceToHost));
     return PUPIL_OK;
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/pupil_pt.h"
 #include "accel_two_level.h"
+#include "host/emitter_tables.h"
 #include "host/scene_tables.h"
 
 namespace pupil {
@@ -41,7 +42,7 @@ inline int drained(hipStream_t stream, int rc) {
                                         std::string(#expr) + ": " + hipGetErrorString(_e)));              \
     } while (0)
 
-// the device of the engine's tables (host/scene_tables.h) and of a call's scratch
+// the device of the engine's tables (host/scene_tables.h, host/emitter_tables.h) and of a call's scratch
 struct HipDevice {
     using Stream = hipStream_t;
     static hipError_t alloc(void **p, size_t bytes) {
@@ -57,8 +58,26 @@ struct HipDevice {
                            g.prim_inst.get(), g.inst_guide.get(), stream);
         return PUPIL_OK;
     }
+    static hipError_t upload(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+    static int failed(hipError_t e, const char *what) {  // what HIP_TRY(what) returns
+        if (e == hipSuccess) return PUPIL_OK;
+        return fail(e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    static int write(void *dst, const void *src, size_t bytes, hipStream_t stream) {
+        return failed(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+    }
+    static int sync(hipStream_t stream) { return failed(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
+    static int env_tables(const DevEmitter &e, const void *rgba, float *sums, DevEmitter *env, hipStream_t stream) {
+        HIP_TRY(hipMemcpyAsync((void *)e.radiance.data, rgba, sizeof(float4) * (size_t)e.map_w * e.map_h,
+                               hipMemcpyDeviceToDevice, stream));
+        launch_env_tables({e.radiance.data, e.map_w, e.map_h, const_cast<float *>(e.col_cdf), const_cast<float *>(e.row_cdf),
+                           e.row_weight, sums, env},
+                          stream);
+        return failed(hipGetLastError(), "hipGetLastError()");
+    }
 };
 using EngineTables = SceneTables<HipDevice>;
+using EngineEmitters = EmitterTables<HipDevice>;
 
 // a shape's engine-owned device arrays (those the instances point at)
 struct ShapeDev {

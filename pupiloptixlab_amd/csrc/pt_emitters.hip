@@ -1,6 +1,6 @@
 // pt_emitters.hip — the area-emitter table rebuilt on the device (pupil_pt_enable_device_emitters).
 //
-// The host derives the table in world.cpp (AddAreaEmitter, ComputeProbability) and engine.hip
+// The host derives the table in world.cpp (AddAreaEmitter, ComputeProbability) and host/emitter_tables.h
 // (emitter_tables).  The five stages here restate those operations in the host's order, so the
 // table is bit for bit the host's for the same vertices and transforms (the build has
 // -ffp-contract=off on both sides; / and sqrtf are correctly rounded on both):

@@ -1,6 +1,6 @@
 // pt_envmap.hip — the env map's CDF tables rebuilt on the device (pupil_pt_update_env_device).
 //
-// The host derives the tables in engine.hip (convert_emitter's env branch, the reference's
+// The host derives the tables in host/emitter_tables.h (convert_emitter's env branch, the reference's
 // BuildEnvMapCdfTable, world/emitter.cpp:107-149).  The two stages here restate those operations
 // in the host's order, so the block col_cdf | row_cdf | row_weight is bit for bit the host's for
 // the same texels (the build has -ffp-contract=off on both sides; / is correctly rounded on both):

@@ -350,7 +350,7 @@ void launch_record_bins(float4 *recs, uint32_t slots, const DevInstance *instanc
                         hipStream_t s);
 // The env map's tables rebuilt in place from the engine's own texels (pt_envmap.hip): col_cdf
 // ((w + 1) * h), row_cdf (h + 1) and env->normalization, bit for bit what convert_emitter
-// (engine.hip) derives from the same texels.  row_weight (h, the host's std::sin) is read only;
+// (host/emitter_tables.h) derives from the same texels.  row_weight (h, the host's std::sin) is read only;
 // col_sum: scratch, h floats.  kEnvStage: the values a wave stages in the LDS per chunk of a chain.
 constexpr uint32_t kEnvStage = 1024;
 struct EnvTablesJob {

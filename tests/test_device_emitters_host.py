@@ -156,7 +156,7 @@ def desc_table(desc):
 
 
 def host_cdf_and_guide(sp, binary=False):
-    """engine.hip emitter_tables: the sequential CDF, guide_bits and the guide's linear walk"""
+    """host/emitter_tables.h emitter_tables: the sequential CDF, guide_bits and the guide's linear walk"""
     cdf = np.zeros(len(sp), f32)
     s = f32(0.0)
     for i, p in enumerate(sp):
