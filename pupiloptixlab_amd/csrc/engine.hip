@@ -35,40 +35,37 @@ constexpr uint32_t kMaxPairs = 4096;
 
 using namespace pupil;
 
-// fresnel::DiffuseReflectance (render/material/fresnel.h:67-94)
-float diffuse_reflectance(float eta) {
-    if (eta < 1) {
-        return -1.4399f * (eta * eta) + 0.7099f * eta + 0.6681f + 0.0636f / eta;
-    }
-    const float inv_eta = 1.0f / eta;
-    const float inv_eta2 = inv_eta * inv_eta;
-    const float inv_eta3 = inv_eta2 * inv_eta;
-    const float inv_eta4 = inv_eta3 * inv_eta;
-    const float inv_eta5 = inv_eta4 * inv_eta;
-    return 0.919317f - 3.4793f * inv_eta + 6.75335f * inv_eta2 - 7.80989f * inv_eta3 + 4.98554f * inv_eta4 -
-           1.36881f * inv_eta5;
-}
-
-// GetPixelAverage (optix_material.cpp:15-42)
-// (the two halves, pt_kernels.h, are the ones the device restates after a texel update)
-vec3 pixel_average(const pupil_texture &t) {
-    if (t.type == PUPIL_TEX_BITMAP && t.rgba && t.width && t.height) {
-        float r = 0.f, g = 0.f, b = 0.f;
-        for (size_t i = 0, idx = 0; i < t.height; ++i)
-            for (size_t j = 0; j < t.width; ++j) {
-                r += t.rgba[idx++];
-                g += t.rgba[idx++];
-                b += t.rgba[idx++];
-                idx++;
-            }
-        return bitmap_average(v3(r, g, b), t.width, t.height);
-    }
-    return texture_const_average(t.type, t.c0, t.c1);
-}
-
-// device scratch of one call, freed on every return path (pupil_debug_partition)
+// a device array of the engine's, or the scratch of one call: freed with its holder on every path
 template <typename T>
 using ScratchBuf = ScopedBuffer<T, HipDevice>;
+using Event = ScopedHandle<hipEvent_t, HipDevice>;
+
+// src[0 .. count) into a fresh allocation of b
+template <typename T>
+hipError_t upload(ScratchBuf<T> &b, const T *src, size_t count) {
+    hipError_t e = b.alloc(count);
+    if (e == hipSuccess && count) e = hipMemcpy(b.get(), src, sizeof(T) * count, hipMemcpyHostToDevice);
+    return e;
+}
+
+// the arrays of PathState and Queues that are sized by the ring's paths (ensure_state)
+struct Ring {
+    ScratchBuf<float4> ray_o, ray_d, hit, thr, rad, sh_d, sh_c;
+    ScratchBuf<uint4> misc;
+    ScratchBuf<uint8_t> mbin, sflags;
+    ScratchBuf<uint32_t> bins, nxsh, hist;
+};
+
+// what is sized by the instance count, which drop_stale resets whole: the flow pass's previous
+// transforms and snapshot table, the device move's staging block, and their host staging copies
+struct InstanceScratch {
+    ScratchBuf<float> flow_prev, move_stage;
+    ScratchBuf<const float *> flow_verts;
+    std::vector<float> h_flow_prev, h_move_stage;
+    std::vector<const float *> h_flow_verts;
+    std::vector<uint32_t> h_move_ids;
+    std::vector<uint8_t> h_move_seen;
+};
 
 // material bin of a material type (0 is the miss bin, 8 holds every unknown type)
 uint32_t material_bin(uint32_t type) { return type >= 1u && type <= 7u ? type : 8u; }
@@ -85,10 +82,11 @@ int pupil::fail(int code, const std::string &msg) {
 }
 
 struct pupil_pt {
+    // the stream is declared first, so it is destroyed last: every member below frees its device
+    // memory and events before it goes
+    ScopedHandle<hipStream_t, HipDevice> own_stream;
     int device = 0;
-    hipStream_t own_stream = nullptr;
     DeviceScene sc{};
-    std::vector<void *> allocs;
     SceneAccel accel;
     bool primary_interleave = true;  // primary extend dequeues pixel-major (PUPIL_PRIMARY_ORDER)
     bool shade_list = false;  // shade walks the traced list instead of a material partition (PUPIL_SHADE_LIST)
@@ -106,26 +104,28 @@ struct pupil_pt {
     uint32_t bin_mask = 0;            // material bins of the scene's instances + the miss bin (partition)
     uint64_t frame_launches = 0;      // renders run as one persistent launch (pt_frame.hip)
     uint64_t ring_bytes = 0;          // path state + queues + AOV scratch allocated now
-    float *aov_scratch = nullptr;     // K slots x 7 floats per local pixel
+    ScratchBuf<float> aov_scratch;    // K slots x 7 floats per local pixel
     size_t aov_cap = 0;
     hipStream_t last_stream = nullptr;  // of the last render (NULL = the default stream)
     bool rendered = false;
     // path state / queues (grown on demand)
     size_t cap = 0;
-    PathState ps{};
-    Queues q{};
-    int *ovf = nullptr;
+    Ring ring;
+    PathState ps{};  // the pointers of `ring`
+    Queues q{};      // the pointers of `ring`, q_counts and q_work
+    ScratchBuf<uint32_t> q_counts, q_work;
+    ScratchBuf<int> ovf;
     uint32_t ovf_threads = 0;
     // pixel map cache
-    uint32_t *pixel_map = nullptr;
+    ScratchBuf<uint32_t> pixel_map;
     uint32_t pm_key[5] = {0, 0, 0, 0, 0};
     uint32_t pm_count = 0;
     // stats
-    unsigned long long *trace_counters = nullptr;  // [0] nodes [1] prims
+    ScratchBuf<unsigned long long> trace_counters;  // [0] nodes [1] prims
     // device running totals of the extension and shadow rays listed by the flags partitions
     // ([0..1]); the first partition of a render copies them to [2..3] before adding, so the
     // render's own counts are [0..1] - [2..3] without a per-render clear (snap_taken)
-    unsigned long long *ray_cum = nullptr;
+    ScratchBuf<unsigned long long> ray_cum;
     bool snap_taken = false;
     // Terminal-ray cull (pt_shade.h terminal_ray_culled; PUPIL_TERMINAL_CULL=0 turns it off,
     // PUPIL_TERMINAL_CULL_K sets the cap on the set).  d_cull: the scan's count, then the set
@@ -134,8 +134,8 @@ struct pupil_pt {
     // (cull_counted: some render has run with a set, the copies are being made)
     bool cull_on = true;
     uint32_t cull_k = 8;
-    uint32_t *d_cull = nullptr;
-    unsigned long long *cull_cum = nullptr;
+    ScratchBuf<uint32_t> d_cull;
+    ScratchBuf<unsigned long long> cull_cum;
     bool cull_counted = false;
     uint32_t cull_scanned = 0;  // entries of d_cull the last scan left, sorted (0: no scan holds for the records as they are)
     bool cull_last = false;  // the last counted work was a render (a ray query culls nothing)
@@ -146,11 +146,11 @@ struct pupil_pt {
     uint32_t last_paths = 0, last_iters = 0;
     uint64_t last_primary = 0;
     bool last_stats = false;
-    std::vector<hipEvent_t> trace_events;  // pairs
+    std::vector<Event> trace_events;       // pairs
     std::vector<uint8_t> pair_kind;        // per pair: 0 extend, 1 shadow / mixed traversal, 2 shade, 3 one-launch frame
     // ev_begin / ev_end bracket renders that collect counters or stage times only (each event
     // leaves a few us of stream gap); ev_sync orders another stream after the last render
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_sync = nullptr;
+    Event ev_begin, ev_end, ev_sync;
     bool last_timed = false;  // the last render recorded ev_begin / ev_end
     uint32_t trace_pairs = 0;
     bool pairs_keep = false;  // the pairs of PUPIL_STATS_TRACE_TIMING renders accumulate until read
@@ -158,7 +158,7 @@ struct pupil_pt {
     double kept_ms[4] = {0.0, 0.0, 0.0, 0.0};
     uint64_t kept_n[4] = {0, 0, 0, 0};
     // PUPIL_TRACE_TAIL: per-wave start / drained / exit times of each traversal launch of a stats render
-    unsigned long long *tail_buf = nullptr;
+    ScratchBuf<unsigned long long> tail_buf;
     uint32_t tail_waves = 0, tail_launches = 0;
     pupil_pt_counters totals{};
     // the instance table, its host mirror and the primitive -> instance tables: their one owner
@@ -167,13 +167,9 @@ struct pupil_pt {
     std::vector<DevInstance> &h_insts() { return tables.cur().mirror; }
     const std::vector<DevInstance> &h_insts() const { return tables.cur().mirror; }
     DevInstance *d_insts() const { return tables.cur().insts.get(); }
-    DevMaterial *d_mats = nullptr;
-    uint32_t num_mats = 0;
-    // material updates (pupil_pt_update_materials / _update_texture_device): the host mirror of
-    // d_mats -- descriptors and texel pointers; after a device texel update of a plastic its
-    // specular_sampling_weight is stale here, and an entry is written to the device only when its
-    // own material is replaced -- the successful calls and the host clock around the last one
-    std::vector<DevMaterial> h_mats;
+    // the materials' one owner (host/material_tables.h); the successful pupil_pt_update_materials /
+    // _update_texture_device calls and the host clock around the last one
+    EngineMaterials materials;
     uint64_t mat_updates = 0;
     double mat_ms = 0.0;
     // the emitter state's one owner (host/emitter_tables.h); the successful pupil_pt_update_env_* calls
@@ -184,35 +180,32 @@ struct pupil_pt {
     // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
     // and the event that orders a caller's stream before a device-to-device copy (vertices, texels)
     std::vector<ShapeDev> shapes;
-    hipEvent_t ev_verts = nullptr;
+    Event ev_verts;
     // flow pass scratch (pupil_pt_motion_vectors), sized on first use: the ray list (2 float4
-    // per pixel), the hit list, the previous instance transforms and their host staging copy;
-    // ev_flow: the upload of that copy has run (the next call may overwrite it)
-    float4 *flow_rays = nullptr, *flow_hits = nullptr;
-    float *flow_prev = nullptr;
-    std::vector<float> h_flow_prev;
-    hipEvent_t ev_flow = nullptr;
+    // per pixel), the hit list, the previous instance transforms and their host staging copy
+    // (per_inst); ev_flow: the upload of that copy has run (the next call may overwrite it)
+    ScratchBuf<float4> flow_rays, flow_hits;
+    InstanceScratch per_inst;
+    Event ev_flow;
     // vertex snapshots (ShapeDev::prev) as the flow pass reads them: per instance the snapshot of
     // its shape or null, uploaded by the first flow pass after the set of snapshots changed
     // (flow_verts_stale; staged like flow_prev, under ev_flow); ev_snap: the last snapshot copy
     // on the engine's stream, which every flow pass waits for while snapshots are held
-    const float **flow_verts = nullptr;
-    std::vector<const float *> h_flow_verts;
     uint32_t snapshots = 0;
     bool flow_verts_stale = false;
-    hipEvent_t ev_snap = nullptr;
+    Event ev_snap;
     // ray queries (pupil_pt_query_rays / _query_camera).  query_hits: the compact hits of a call that
     // wants resolved outputs but not the hits themselves; grown geometrically, never shrunk
     // (query_cap rays, query_grows growths; the first build of query_slot counts as one).
     // query_slot: flat BVH only, global primitive id -> record slot for the resolve kernel,
     // rebuilt from the records by the first such query after they moved (query_slot_valid is
     // cleared with the cull set's scan).  ev_q0 / ev_q1 bracket the last query on its stream
-    float4 *query_hits = nullptr;
+    ScratchBuf<float4> query_hits;
     size_t query_cap = 0;
-    uint32_t *query_slot = nullptr;
+    ScratchBuf<uint32_t> query_slot;
     bool query_slot_valid = false;
     uint64_t queries = 0, query_rays = 0, query_grows = 0;
-    hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
+    Event ev_q0, ev_q1;
     // radiance along rays (pupil_pt_radiance_rays): a path state, queues and identity id list of
     // its own, carved from one block (rad_block) of rad_cap paths, which grows geometrically up to
     // rad_chunk (PUPIL_RADIANCE_CHUNK, read at create) and never shrinks.  rad_cum: its own device
@@ -222,24 +215,20 @@ struct pupil_pt {
     // ev_r0 / ev_r1 bracket the last call on its stream
     size_t rad_chunk = (size_t)1 << 24;
     size_t rad_cap = 0;
-    void *rad_block = nullptr;
+    ScratchBuf<char> rad_block;
     PathState rad_ps{};
     Queues rad_q{};
     uint32_t *rad_ids = nullptr;
     static constexpr uint32_t kRadTotals = kCullShards * kCullStride;  // words of rad_cum before the two totals
-    unsigned long long *rad_cum = nullptr;
+    ScratchBuf<unsigned long long> rad_cum;
     uint64_t rad_calls = 0, rad_rays = 0, rad_grows = 0;
-    hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
-    // instances from device memory (pupil_pt_update_instances_device).  d_move_stage: kMoveHeader
+    Event ev_r0, ev_r1;
+    // instances from device memory (pupil_pt_update_instances_device).  per_inst.move_stage: kMoveHeader
     // floats whose first word counts the skipped ids (a running total the kernel adds to), then
     // kMoveStageFloats per list entry (pt_kernels.h MoveInstancesJob), sized for every instance on
     // the first call; the host's copies of the id list and of the block; the totals since create
     // and what the last call launched, synchronised and took
     static constexpr uint32_t kMoveHeader = 8;
-    float *d_move_stage = nullptr;
-    std::vector<uint32_t> h_move_ids;
-    std::vector<uint8_t> h_move_seen;
-    std::vector<float> h_move_stage;
     uint64_t inst_dev_updates = 0, inst_dev_moved = 0, inst_dev_skipped = 0;
     uint32_t inst_dev_launches = 0, inst_dev_syncs = 0;
     double inst_dev_ms = 0.0;
@@ -253,91 +242,41 @@ struct pupil_pt {
     uint32_t inst_set_blas_builds = 0, inst_set_whole = 0;
     double inst_set_ms = 0.0;
 
-    template <typename T>
-    hipError_t alloc(T **p, size_t count) {
-        hipError_t e = hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-        if (e == hipSuccess) allocs.push_back(*p);
-        return e;
-    }
-    template <typename T>
-    hipError_t upload(T **p, const T *src, size_t count) {
-        hipError_t e = alloc(p, count);
-        if (e == hipSuccess && count) e = hipMemcpy(*p, src, sizeof(T) * count, hipMemcpyHostToDevice);
-        return e;
-    }
-    void release(void *p) {
-        if (!p) return;
-        for (auto it = allocs.begin(); it != allocs.end(); ++it)
-            if (*it == p) {
-                allocs.erase(it);
-                break;
-            }
-        (void)hipFree(p);
+    void point_at_ring() {  // ps and q name the arrays `ring` holds now, or none
+        ps = PathState{ring.ray_o.get(), ring.ray_d.get(), ring.hit.get(),  ring.thr.get(),  ring.rad.get(),
+                       ring.misc.get(),  ring.sh_d.get(),  ring.sh_c.get(), ring.mbin.get(), ring.sflags.get()};
+        q.bins = ring.bins.get(), q.nxsh = ring.nxsh.get(), q.hist = ring.hist.get();
     }
     void release_state() {
         ring_bytes = 0;
         ring_fresh = true;
-        void *bufs[] = {ps.ray_o, ps.ray_d, ps.hit,  ps.thr,  ps.rad,    ps.misc,
-                        ps.sh_d, ps.sh_c, ps.mbin, ps.sflags, q.bins, q.nxsh, q.hist};
-        for (void *b : bufs)
-            if (b) (void)hipFree(b);
-        ps = PathState{};
-        q.bins = q.nxsh = q.hist = nullptr;
+        ring = Ring{};
+        point_at_ring();
         cap = 0;
         pipe.ring_lost();
     }
     ~pupil_pt() {
-        (void)hipSetDevice(device);
-        release_state();
-        if (aov_scratch) (void)hipFree(aov_scratch);
-        for (void *p : allocs) (void)hipFree(p);
+        (void)hipSetDevice(device);  // before any member is destroyed
         accel.free();
-        if (pixel_map) (void)hipFree(pixel_map);
-        for (auto e : trace_events) (void)hipEventDestroy(e);
-        if (ev_begin) (void)hipEventDestroy(ev_begin);
-        if (ev_end) (void)hipEventDestroy(ev_end);
-        if (ev_sync) (void)hipEventDestroy(ev_sync);
-        if (ev_flow) (void)hipEventDestroy(ev_flow);
-        if (ev_snap) (void)hipEventDestroy(ev_snap);
-        if (ev_q0) (void)hipEventDestroy(ev_q0);
-        if (ev_q1) (void)hipEventDestroy(ev_q1);
-        if (rad_block) (void)hipFree(rad_block);
-        if (ev_r0) (void)hipEventDestroy(ev_r0);
-        if (ev_r1) (void)hipEventDestroy(ev_r1);
-        if (ev_verts) (void)hipEventDestroy(ev_verts);
-        if (own_stream) (void)hipStreamDestroy(own_stream);
     }
 };
 
 namespace {
 
-int upload_texture(pupil_pt *pt, const pupil_texture &t, DevTexture &d) {
-    if (const int rc = texture_desc(t, d)) return rc;
-    if (t.type == PUPIL_TEX_BITMAP) {
-        float4 *texels = nullptr;
-        HIP_TRY(pt->upload(&texels, reinterpret_cast<const float4 *>(t.rgba), (size_t)t.width * t.height));
-        d.data = texels;
-    }
-    return PUPIL_OK;
-}
-
-int ensure_state(pupil_pt *pt, size_t paths) {
-    if (paths <= pt->cap) return PUPIL_OK;
+int ensure_state(pupil_pt *pt, size_t n) {
+    if (n <= pt->cap) return PUPIL_OK;
     pt->release_state();
-    const size_t n = paths;
-    HIP_TRY(hipMalloc((void **)&pt->ps.ray_o, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.ray_d, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.hit, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.thr, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.rad, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.misc, sizeof(uint4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.sh_d, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.sh_c, sizeof(float4) * n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.mbin, n));
-    HIP_TRY(hipMalloc((void **)&pt->ps.sflags, n));
-    HIP_TRY(hipMalloc((void **)&pt->q.bins, sizeof(uint32_t) * n));
-    HIP_TRY(hipMalloc((void **)&pt->q.nxsh, sizeof(uint32_t) * 2 * n));
-    HIP_TRY(hipMalloc((void **)&pt->q.hist, sizeof(uint32_t) * partition_hist_entries((uint32_t)n)));
+    Ring &r = pt->ring;
+    hipError_t e = hipSuccess;
+    auto take = [&e](auto &b, size_t count) {  // nothing more once one has failed
+        if (e == hipSuccess) e = b.alloc(count);
+    };
+    for (auto *b : {&r.ray_o, &r.ray_d, &r.hit, &r.thr, &r.rad, &r.sh_d, &r.sh_c}) take(*b, n);
+    take(r.misc, n), take(r.mbin, n), take(r.sflags, n), take(r.bins, n), take(r.nxsh, 2 * n);
+    take(r.hist, partition_hist_entries((uint32_t)n));
+    if (e != hipSuccess) pt->release_state();  // a ring that cannot be allocated whole is freed
+    HIP_TRY(e);
+    pt->point_at_ring();
     pt->q.capacity = (uint32_t)n;
     pt->cap = n;
     pt->ring_bytes = n * (8 * 16 + 2 + 4 + 8) + sizeof(uint32_t) * (size_t)partition_hist_entries((uint32_t)n);
@@ -387,18 +326,15 @@ int local_pixel_map(pupil_pt *pt, const uint32_t key[5], const uint32_t **map, u
     *map = nullptr;
     *num_local = pt->width * pt->height;
     if (key[4] <= 1) return PUPIL_OK;
-    if (!pt->pixel_map || std::memcmp(key, pt->pm_key, sizeof(pt->pm_key)) != 0) {
+    if (!pt->pixel_map.get() || std::memcmp(key, pt->pm_key, sizeof(pt->pm_key)) != 0) {
         const uint32_t n = local_pixels(pt->width, pt->height, key[2], key[3], key[4], nullptr);
         std::vector<uint32_t> host(n ? n : 1);
         local_pixels(pt->width, pt->height, key[2], key[3], key[4], host.data());
-        if (pt->pixel_map) (void)hipFree(pt->pixel_map);
-        pt->pixel_map = nullptr;
-        HIP_TRY(hipMalloc((void **)&pt->pixel_map, sizeof(uint32_t) * host.size()));
-        HIP_TRY(hipMemcpy(pt->pixel_map, host.data(), sizeof(uint32_t) * host.size(), hipMemcpyHostToDevice));
+        HIP_TRY(upload(pt->pixel_map, host.data(), host.size()));
         std::memcpy(pt->pm_key, key, sizeof(pt->pm_key));
         pt->pm_count = n;
     }
-    *map = pt->pixel_map;
+    *map = pt->pixel_map.get();
     *num_local = pt->pm_count;
     return PUPIL_OK;
 }
@@ -460,7 +396,7 @@ struct RenderCtx {
     }
     void tail_slot() {  // wave-time slice of the next traversal launch (PUPIL_TRACE_TAIL)
         if (tail && pt->tail_launches < kMaxDepth + 1)
-            ts_dev.wave_times = pt->tail_buf + (size_t)pt->tail_launches++ * pt->tail_waves * 4;
+            ts_dev.wave_times = pt->tail_buf.get() + (size_t)pt->tail_launches++ * pt->tail_waves * 4;
         else
             ts_dev.wave_times = nullptr;
     }
@@ -497,10 +433,8 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
     }
     if (plan.aov_floats() > pt->aov_cap) {
         grew = true;
-        if (pt->aov_scratch) (void)hipFree(pt->aov_scratch);
-        pt->aov_scratch = nullptr;
         pt->aov_cap = 0;
-        HIP_TRY(hipMalloc((void **)&pt->aov_scratch, sizeof(float) * plan.aov_floats()));
+        HIP_TRY(pt->aov_scratch.alloc(plan.aov_floats()));
         pt->aov_cap = plan.aov_floats();
     }
     const PathState ring = pt->ps;
@@ -519,12 +453,12 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
     const uint32_t interleave0 = pt->primary_interleave;
     if (st.one_launch_frame(kn) && frame_kernel_supported(pt->sc)) {
         // this render's extension / shadow rays = the growth of the running totals from here
-        HIP_TRY(hipMemcpyAsync(pt->ray_cum + 2, pt->ray_cum, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(pt->ray_cum.get() + 2, pt->ray_cum.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
         pt->snap_taken = true;
         FrameParams fs = fp;
         fs.group = 1;
         cx.ev0(3);  // traversal and shading in one kernel: timed apart from trace_ms (frame_ms)
-        launch_frame(pt->sc, fs, ring, pt->q.work + kWorkFrame, pt->ray_cum, pt->ovf, pt->ovf_threads,
+        launch_frame(pt->sc, fs, ring, pt->q.work + kWorkFrame, pt->ray_cum.get(), pt->ovf.get(), pt->ovf_threads,
                      interleave0 && fp.spp > 1 ? fp.spp : 0u, s);
         cx.ev1();
         launch_accumulate(fp, ring, nullptr, true, s);
@@ -536,7 +470,7 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
         return PUPIL_OK;
     }
     // AOV scratch of frame `index` of the ring (slot-major): 7 floats per local pixel
-    auto scratch = [&](uint32_t index) { return pt->aov_scratch + (size_t)index * 7 * nl; };
+    auto scratch = [&](uint32_t index) { return pt->aov_scratch.get() + (size_t)index * 7 * nl; };
     pt->snap_taken = false;
     // 1 = an early-exit check found nothing left to trace or shade: the frame is complete
     auto trace = [&](const PipeTrace &t) -> int {
@@ -551,8 +485,8 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
             // the rays the previous iteration's shade spawned, over the slots in use, in
             // increasing path id: next (bit 0) and shadow (bit 1) lists -> q.nxsh
             launch_partition(ring.sflags, t.ring_extent, 2, kPartFlags, t.read_tag, q.nxsh, q.hist, q.counts + kCntNext,
-                             q.counts + kStartNext, nullptr, nullptr, s, pt->ray_cum,
-                             pt->snap_taken ? nullptr : pt->ray_cum + 2);
+                             q.counts + kStartNext, nullptr, nullptr, s, pt->ray_cum.get(),
+                             pt->snap_taken ? nullptr : pt->ray_cum.get() + 2);
             pt->snap_taken = true;
             if (t.check_exit) {
                 uint32_t c[2] = {1, 1};
@@ -563,15 +497,15 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
             cx.ev0(1);
             cx.tail_slot();
             if (t.inject)  // + the new group's camera rays, dequeued first in every chunk (pixel-major)
-                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, t.nfp, 0u, t.base, interleave, nl,
+                launch_trace_mixed(pt->sc, ring, q, pt->ovf.get(), pt->ovf_threads, cx.tsp(), s, t.nfp, 0u, t.base, interleave, nl,
                                    pt->any_overlap);
             else
-                launch_trace_mixed(pt->sc, ring, q, pt->ovf, pt->ovf_threads, cx.tsp(), s, 0u, 0u, 0u, 0u, 0u, pt->any_overlap);
+                launch_trace_mixed(pt->sc, ring, q, pt->ovf.get(), pt->ovf_threads, cx.tsp(), s, 0u, 0u, 0u, 0u, 0u, pt->any_overlap);
             cx.ev1();
         } else {
             cx.ev0(0);
             cx.tail_slot();
-            launch_extend(pt->sc, cx.view(t.nf.slot, st.cap), q, nullptr, nullptr, t.nfp, pt->ovf, pt->ovf_threads,
+            launch_extend(pt->sc, cx.view(t.nf.slot, st.cap), q, nullptr, nullptr, t.nfp, pt->ovf.get(), pt->ovf_threads,
                           cx.tsp(), s, interleave, nl);
             cx.ev1();
         }
@@ -630,7 +564,7 @@ int render_pipelined(RenderCtx &cx, const FrameParams &fp, const pupil_pt_launch
 // shapes: validated, their arrays copied to engine-owned HBM
 int upload_shapes(pupil_pt *pt, const pupil_scene_desc *scene) {
     std::vector<ShapeDev> &shapes = pt->shapes;
-    shapes.assign(scene->num_shapes, ShapeDev{});
+    shapes = std::vector<ShapeDev>(scene->num_shapes);
     for (uint32_t s = 0; s < scene->num_shapes; s++) {
         const pupil_shape &sh = scene->shapes[s];
         shapes[s].kind = sh.kind;
@@ -641,10 +575,10 @@ int upload_shapes(pupil_pt *pt, const pupil_scene_desc *scene) {
                 return fail(PUPIL_ERR_INVALID, "mesh without positions/indices");
             for (size_t i = 0; i < 3 * (size_t)sh.num_faces; i++)
                 if (sh.indices[i] >= sh.num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
-            if (pt->upload(&shapes[s].pos, sh.positions, 3 * (size_t)sh.num_vertices) ||
-                (sh.normals && pt->upload(&shapes[s].nrm, sh.normals, 3 * (size_t)sh.num_vertices)) ||
-                (sh.texcoords && pt->upload(&shapes[s].tex, sh.texcoords, 2 * (size_t)sh.num_vertices)) ||
-                pt->upload(&shapes[s].idx, sh.indices, 3 * (size_t)sh.num_faces))
+            if (upload(shapes[s].pos, sh.positions, 3 * (size_t)sh.num_vertices) ||
+                (sh.normals && upload(shapes[s].nrm, sh.normals, 3 * (size_t)sh.num_vertices)) ||
+                (sh.texcoords && upload(shapes[s].tex, sh.texcoords, 2 * (size_t)sh.num_vertices)) ||
+                upload(shapes[s].idx, sh.indices, 3 * (size_t)sh.num_faces))
                 return fail(PUPIL_ERR_OOM, "mesh upload failed");
         } else if (sh.kind != PUPIL_SHAPE_SPHERE) {
             return fail(PUPIL_ERR_INVALID, "unknown shape kind");
@@ -653,55 +587,10 @@ int upload_shapes(pupil_pt *pt, const pupil_scene_desc *scene) {
     return PUPIL_OK;
 }
 
-// one material (optix_material.cpp:39-132 host precompute) with its texture descriptors; the
-// texels are placed by the caller (create: convert_materials; pupil_pt_update_materials).
-// Touches nothing of an engine: it is also the validation of an update
-int convert_material(const pupil_material &src, DevMaterial &d) {
-    std::memset(&d, 0, sizeof(d));
-    d.type = src.type <= 7u ? src.type : 0u;
-    d.twosided = src.twosided;
-    d.nonlinear = src.nonlinear;
-    if (d.type == PUPIL_MAT_DIELECTRIC || d.type == PUPIL_MAT_ROUGH_DIELECTRIC || d.type == PUPIL_MAT_PLASTIC ||
-        d.type == PUPIL_MAT_ROUGH_PLASTIC)
-        d.eta = src.int_ior / src.ext_ior;
-    for (int k = 0; k < 4; k++)
-        if (const int rc = texture_desc(src.tex[k], d.tex[k])) return rc;
-    if (d.type == PUPIL_MAT_PLASTIC || d.type == PUPIL_MAT_ROUGH_PLASTIC) {
-        const pupil_texture &dt = d.type == PUPIL_MAT_PLASTIC ? src.tex[0] : src.tex[1];
-        const pupil_texture &stx = d.type == PUPIL_MAT_PLASTIC ? src.tex[1] : src.tex[2];
-        d.specular_sampling_weight = specular_sampling_weight(pixel_average(dt), pixel_average(stx));
-        d.int_fdr = diffuse_reflectance(1.f / d.eta);
-    }
-    return PUPIL_OK;
-}
-
-// the scene's materials; their bitmap textures are uploaded here
-int convert_materials(pupil_pt *pt, const pupil_scene_desc *scene, std::vector<DevMaterial> &mats) {
-    mats.resize(scene->num_materials);
-    for (uint32_t m = 0; m < scene->num_materials; m++) {
-        const pupil_material &src = scene->materials[m];
-        DevMaterial &d = mats[m];
-        if (const int rc = convert_material(src, d)) return rc;
-        for (int k = 0; k < 4; k++)
-            if (src.tex[k].type == PUPIL_TEX_BITMAP) {
-                float4 *texels = nullptr;
-                HIP_TRY(pt->upload(&texels, reinterpret_cast<const float4 *>(src.tex[k].rgba),
-                                   (size_t)src.tex[k].width * src.tex[k].height));
-                d.tex[k].data = texels;
-            }
-    }
-    if (mats.empty()) {  // keep a valid pointer for instances without material
-        DevMaterial d;
-        std::memset(&d, 0, sizeof(d));
-        mats.push_back(d);
-    }
-    return PUPIL_OK;
-}
-
 // The scene's instances, validated, as the first generation of the tables -- staged and adopted
-// as an update's are (host/scene_tables.h), the records by fill_instance_record -- and the
-// materials.
-int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector<DevMaterial> &mats) {
+// as an update's are (host/scene_tables.h), the records by fill_instance_record.
+int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene) {
+    const std::vector<DevMaterial> &mats = pt->materials.mirror();
     const uint32_t n = scene->num_instances;
     // an instance's emitter range lies within the triangle and sphere emitters: the delta lights
     // behind them belong to no primitive
@@ -721,11 +610,6 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
         if (src.emitter_offset >= 0 && (size_t)src.emitter_offset + counts[i] > true_areas)
             return fail(PUPIL_ERR_INVALID, "emitter offset out of range");
     }
-    if (pt->upload(&pt->d_mats, mats.data(), mats.size())) return fail(PUPIL_ERR_OOM, "scene upload failed");
-    pt->num_mats = (uint32_t)mats.size();
-    pt->h_mats = mats;
-    pt->sc.materials = pt->d_mats;
-    pt->sc.num_materials = (uint32_t)mats.size();
     hipStream_t s = pt->own_stream;
     EngineTables::Generation gen;
     // the flattened BVH's limit: SceneAccel::build, which chooses the mode
@@ -733,7 +617,7 @@ int upload_tables(pupil_pt *pt, const pupil_scene_desc *scene, const std::vector
     for (uint32_t i = 0; i < n; i++) {
         const pupil_instance &src = scene->instances[i];
         const ShapeDev &sd = pt->shapes[src.shape];
-        const InstShape shape{scene->shapes[src.shape].kind, counts[i], sd.pos, sd.nrm, sd.tex, sd.idx};
+        const InstShape shape{scene->shapes[src.shape].kind, counts[i], sd.pos.get(), sd.nrm.get(), sd.tex.get(), sd.idx.get()};
         const InstBinding bind{src.shape,          src.material, src.flip_normals, src.flip_tex_coords,
                                src.emitter_offset, 0u,           material_bin(mats[src.material].type)};
         fill_instance_record(gen.mirror[i], shape, bind, gen.first[i], src.to_world, src.to_object, false);
@@ -813,19 +697,19 @@ void read_knobs(pupil_pt *pt) {
 // traversal overflow stacks, counters, events
 int alloc_workspace(pupil_pt *pt) {
     pt->ovf_threads = trace_grid_blocks() * (uint32_t)kTraceBlock;
-    if (pt->alloc(&pt->ovf, (size_t)pt->ovf_threads * kStackOvf) || pt->alloc(&pt->trace_counters, 32) ||
-        pt->alloc(&pt->ray_cum, 4) || pt->alloc(&pt->q.counts, kCountSlots) || pt->alloc(&pt->q.work, kWorkSlots) ||
-        pt->alloc(&pt->d_cull, 1 + kCullSetMax) || pt->alloc(&pt->cull_cum, 2 * kCullShards * kCullStride) ||
-        pt->alloc(&pt->rad_cum, pupil_pt::kRadTotals + 2))
+    if (pt->ovf.alloc((size_t)pt->ovf_threads * kStackOvf) || pt->trace_counters.alloc(32) || pt->ray_cum.alloc(4) ||
+        pt->q_counts.alloc(kCountSlots) || pt->q_work.alloc(kWorkSlots) || pt->d_cull.alloc(1 + kCullSetMax) ||
+        pt->cull_cum.alloc(2 * kCullShards * kCullStride) || pt->rad_cum.alloc(pupil_pt::kRadTotals + 2))
         return fail(PUPIL_ERR_OOM, "workspace allocation failed");
+    pt->q.counts = pt->q_counts.get(), pt->q.work = pt->q_work.get();
     if (hipMemset(pt->q.work, 0, kWorkSlots * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(pt->rad_cum, 0, (pupil_pt::kRadTotals + 2) * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(pt->cull_cum, 0, 2 * kCullShards * kCullStride * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(pt->ray_cum, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
+        hipMemset(pt->rad_cum.get(), 0, (pupil_pt::kRadTotals + 2) * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(pt->cull_cum.get(), 0, 2 * kCullShards * kCullStride * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(pt->ray_cum.get(), 0, 4 * sizeof(unsigned long long)) != hipSuccess)
         return fail(PUPIL_ERR_HIP, "workspace clear failed");
-    if (hipEventCreate(&pt->ev_begin) != hipSuccess || hipEventCreate(&pt->ev_end) != hipSuccess ||
-        hipEventCreateWithFlags(&pt->ev_sync, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&pt->ev_verts, hipEventDisableTiming) != hipSuccess)
+    if (hipEventCreate(pt->ev_begin.put()) != hipSuccess || hipEventCreate(pt->ev_end.put()) != hipSuccess ||
+        hipEventCreateWithFlags(pt->ev_sync.put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(pt->ev_verts.put(), hipEventDisableTiming) != hipSuccess)
         return fail(PUPIL_ERR_HIP, "event creation failed");
     return PUPIL_OK;
 }
@@ -836,29 +720,18 @@ int alloc_workspace(pupil_pt *pt) {
 // map itself, sized by the primitive count, and the vertex snapshot of the shape that was
 // `replaced`, sized by its old vertex count -- the flow pass sees none.  instances: the instance
 // count changed too, which sized the flow scratch and the device move's staging block.
-void drop_stale(pupil_pt *pt, bool tables = false, bool instances = false, ShapeDev *replaced = nullptr) {
+void drop_stale(pupil_pt *pt, bool tables = false, bool instances = false, const ShapeDev *replaced = nullptr) {
     pt->cull_scanned = 0;
     pt->query_slot_valid = false;
     if (!tables) return;
-    pt->release(pt->query_slot);
-    pt->query_slot = nullptr;
-    if (replaced) {
-        pt->release(replaced->prev);
-        replaced->prev = nullptr;
-        if (replaced->prev_valid) {
-            pt->snapshots--;
-            pt->flow_verts_stale = true;
-        }
-        replaced->prev_valid = false;
+    pt->query_slot.reset();
+    if (replaced && replaced->prev_valid) {  // the snapshot itself goes with the replaced value
+        pt->snapshots--;
+        pt->flow_verts_stale = true;
     }
     if (!instances) return;
-    for (void *p : {(void *)pt->flow_prev, (void *)pt->flow_verts, (void *)pt->d_move_stage}) pt->release(p);
-    pt->flow_prev = nullptr;
-    pt->flow_verts = nullptr;
+    pt->per_inst = InstanceScratch{};
     pt->flow_verts_stale = true;
-    pt->h_flow_prev.clear(), pt->h_flow_verts.clear();
-    pt->d_move_stage = nullptr;
-    pt->h_move_ids.clear(), pt->h_move_seen.clear(), pt->h_move_stage.clear();
 }
 
 // ------------------------------------------------------------------ terminal-ray cull set
@@ -880,7 +753,7 @@ void drop_stale(pupil_pt *pt, bool tables = false, bool instances = false, Shape
 // shade.  A scene lit by delta lights alone therefore has no set (and traces every ray).
 int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
     DeviceScene &sc = pt->sc;
-    sc.cull_set = pt->d_cull + 1;
+    sc.cull_set = pt->d_cull.get() + 1;
     sc.cull_n = 0;
     if (records_changed) drop_stale(pt);
     if (!pt->cull_on || sc.has_env || !sc.prims || (sc.two_level && !sc.tl_world)) return PUPIL_OK;
@@ -896,16 +769,16 @@ int derive_cull_set(pupil_pt *pt, bool records_changed = true) {
         return PUPIL_OK;
     }
     uint32_t found[1 + kCullSetMax] = {};
-    HIP_TRY(hipMemsetAsync(pt->d_cull, 0, sizeof(found), pt->own_stream));
-    launch_cull_scan(sc.prims, pt->accel.world_record_slots(), pt->d_insts(), (uint32_t)pt->h_insts().size(), pt->d_cull,
+    HIP_TRY(hipMemsetAsync(pt->d_cull.get(), 0, sizeof(found), pt->own_stream));
+    launch_cull_scan(sc.prims, pt->accel.world_record_slots(), pt->d_insts(), (uint32_t)pt->h_insts().size(), pt->d_cull.get(),
                      kCullSetMax, pt->own_stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(found, pt->d_cull, sizeof(found), hipMemcpyDeviceToHost, pt->own_stream));
+    HIP_TRY(hipMemcpyAsync(found, pt->d_cull.get(), sizeof(found), hipMemcpyDeviceToHost, pt->own_stream));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     pt->accel.counts.launches++, pt->accel.counts.syncs++;  // pupil_pt_instances_device_info
     if (found[0] != emissive) return PUPIL_OK;  // the records do not show what the tables say: no set
     std::sort(found + 1, found + 1 + found[0]);
-    HIP_TRY(hipMemcpyAsync(pt->d_cull, found, sizeof(found), hipMemcpyHostToDevice, pt->own_stream));
+    HIP_TRY(hipMemcpyAsync(pt->d_cull.get(), found, sizeof(found), hipMemcpyHostToDevice, pt->own_stream));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     pt->accel.counts.syncs++;
     sc.cull_n = pt->cull_scanned = found[0];
@@ -1047,15 +920,14 @@ int pupil_pt_create(const pupil_scene_desc *scene, int device, pupil_pt **out) {
     pt->max_depth = scene->max_depth ? scene->max_depth : 1;
     std::memcpy(pt->sc.camera.s2c, scene->sample_to_camera, sizeof(pt->sc.camera.s2c));
     std::memcpy(pt->sc.camera.c2w, scene->camera_to_world, sizeof(pt->sc.camera.c2w));
-    std::vector<DevMaterial> mats;
-    int rc = hipStreamCreateWithFlags(&pt->own_stream, hipStreamNonBlocking) == hipSuccess
+    int rc = hipStreamCreateWithFlags(pt->own_stream.put(), hipStreamNonBlocking) == hipSuccess
                  ? PUPIL_OK
                  : fail(PUPIL_ERR_HIP, "stream creation failed");
     if (!rc) rc = upload_shapes(pt, scene);
-    if (!rc) rc = convert_materials(pt, scene, mats);
-    if (!rc) rc = upload_tables(pt, scene, mats);
+    if (!rc) rc = pt->materials.create(scene->materials, scene->num_materials, pt->sc);
+    if (!rc) rc = upload_tables(pt, scene);
     if (!rc) rc = pt->emitters.update(scene, pt->own_stream, pt->sc);
-    if (!rc) rc = pt->accel.build({pt->own_stream, &pt->tables, pt->d_mats, &pt->sc, &pt->totals}, scene, pt->shapes);
+    if (!rc) rc = pt->accel.build({pt->own_stream, &pt->tables, &pt->materials, &pt->sc, &pt->totals}, scene, pt->shapes);
     if (!rc) read_knobs(pt);
     if (!rc) rc = alloc_workspace(pt);
     if (!rc) rc = pt->accel.publish();
@@ -1149,7 +1021,7 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     if (shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "shape index out of range");
     const ShapeDev &sd = pt->shapes[shape];
     if (sd.kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
-    if (normals && !sd.nrm) return fail(PUPIL_ERR_INVALID, "the shape was created without normals");
+    if (normals && !sd.nrm.get()) return fail(PUPIL_ERR_INVALID, "the shape was created without normals");
     if (flags & ~(PUPIL_VERTS_DEVICE | PUPIL_VERTS_REBUILD)) return fail(PUPIL_ERR_INVALID, "unknown flags");
     const bool device = (flags & PUPIL_VERTS_DEVICE) != 0u, rebuild = (flags & PUPIL_VERTS_REBUILD) != 0u;
     std::vector<uint32_t> changed;
@@ -1168,8 +1040,8 @@ int pupil_pt_update_shape_vertices(pupil_pt *pt, uint32_t shape, const float *po
     const size_t bytes = sizeof(float) * 3 * (size_t)sd.num_vertices;
     if (device) HIP_TRY(order_after_caller(pt, hip_stream));
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIP_TRY(hipMemcpyAsync(sd.pos, positions, bytes, kind, pt->own_stream));
-    if (normals) HIP_TRY(hipMemcpyAsync(sd.nrm, normals, bytes, kind, pt->own_stream));
+    HIP_TRY(hipMemcpyAsync(sd.pos.get(), positions, bytes, kind, pt->own_stream));
+    if (normals) HIP_TRY(hipMemcpyAsync(sd.nrm.get(), normals, bytes, kind, pt->own_stream));
     // From here the shape's arrays hold the new vertices.  After a failure below the structure
     // still bounds the OLD vertices, and the engine must not render until an update of this shape
     // succeeds (the header says so).
@@ -1195,14 +1067,11 @@ int pupil_pt_snapshot_shape_vertices(pupil_pt *pt, uint32_t shape) {
     ShapeDev &sd = pt->shapes[shape];
     if (sd.kind != PUPIL_SHAPE_MESH) return fail(PUPIL_ERR_INVALID, "shape is not a mesh");
     HIP_TRY(hipSetDevice(pt->device));
-    if (!pt->ev_snap) HIP_TRY(hipEventCreateWithFlags(&pt->ev_snap, hipEventDisableTiming));
-    if (!sd.prev && pt->alloc(&sd.prev, 3 * (size_t)sd.num_vertices) != hipSuccess) {
-        (void)hipGetLastError();
-        sd.prev = nullptr;
+    if (!pt->ev_snap) HIP_TRY(hipEventCreateWithFlags(pt->ev_snap.put(), hipEventDisableTiming));
+    if (!sd.prev.get() && sd.prev.alloc(3 * (size_t)sd.num_vertices) != hipSuccess)
         return fail(PUPIL_ERR_OOM, "vertex snapshot allocation failed");
-    }
     HIP_TRY(order_after_renders(pt));
-    HIP_TRY(hipMemcpyAsync(sd.prev, sd.pos, sizeof(float) * 3 * (size_t)sd.num_vertices, hipMemcpyDeviceToDevice,
+    HIP_TRY(hipMemcpyAsync(sd.prev.get(), sd.pos.get(), sizeof(float) * 3 * (size_t)sd.num_vertices, hipMemcpyDeviceToDevice,
                            pt->own_stream));
     HIP_TRY(hipEventRecord(pt->ev_snap, pt->own_stream));
     if (!sd.prev_valid) {
@@ -1258,30 +1127,33 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     // limits refuse the call before anything is allocated; from there a failure lets the stream pass
     EngineTables::Generation gen;
     if (const int rc = EngineTables::stage(counts.data(), ni, !pt->accel.two_level, s, gen)) return drained(s, rc);
-    ScratchBuf<float> pos, nrm, tex;
-    ScratchBuf<uint32_t> idx, idx_max;
-    if (pos.alloc(3 * nv) || (mesh->normals && nrm.alloc(3 * nv)) || (mesh->texcoords && tex.alloc(2 * nv)) ||
-        idx.alloc(3 * nf) || idx_max.alloc(1))
+    ShapeDev fresh;  // the new shape: swapped in on success, else it goes with the call, once the stream has passed
+    fresh.num_vertices = mesh->num_vertices, fresh.num_faces = mesh->num_faces;
+    ScratchBuf<uint32_t> idx_max;
+    if (fresh.pos.alloc(3 * nv) || (mesh->normals && fresh.nrm.alloc(3 * nv)) || (mesh->texcoords && fresh.tex.alloc(2 * nv)) ||
+        fresh.idx.alloc(3 * nf) || idx_max.alloc(1))
         return drained(s, fail(PUPIL_ERR_OOM, "mesh replacement: allocation failed"));
     if (device) HIP_TRY_DRAINED(s, order_after_caller(pt, hip_stream));
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIP_TRY_DRAINED(s, hipMemcpyAsync(idx.get(), mesh->indices, sizeof(uint32_t) * 3 * nf, kind, s));
+    float *const pos = fresh.pos.get(), *const nrm = fresh.nrm.get(), *const tex = fresh.tex.get();
+    uint32_t *const idx = fresh.idx.get();
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(idx, mesh->indices, sizeof(uint32_t) * 3 * nf, kind, s));
     if (device) {  // the index check of the host path, as a reduction: 4 bytes come back
         uint32_t largest = 0;
         HIP_TRY_DRAINED(s, hipMemsetAsync(idx_max.get(), 0, sizeof(uint32_t), s));
-        launch_index_max(idx.get(), 3 * nf, idx_max.get(), s);
+        launch_index_max(idx, 3 * nf, idx_max.get(), s);
         HIP_TRY_DRAINED(s, hipGetLastError());
         HIP_TRY_DRAINED(s, hipMemcpyAsync(&largest, idx_max.get(), sizeof(largest), hipMemcpyDeviceToHost, s));
         HIP_TRY_DRAINED(s, hipStreamSynchronize(s));
         pt->accel.counts.launches++, pt->accel.counts.syncs++;
         if (largest >= mesh->num_vertices) return fail(PUPIL_ERR_INVALID, "index out of range");
     }
-    HIP_TRY_DRAINED(s, hipMemcpyAsync(pos.get(), mesh->positions, sizeof(float) * 3 * nv, kind, s));
-    if (mesh->normals) HIP_TRY_DRAINED(s, hipMemcpyAsync(nrm.get(), mesh->normals, sizeof(float) * 3 * nv, kind, s));
-    if (mesh->texcoords) HIP_TRY_DRAINED(s, hipMemcpyAsync(tex.get(), mesh->texcoords, sizeof(float) * 2 * nv, kind, s));
+    HIP_TRY_DRAINED(s, hipMemcpyAsync(pos, mesh->positions, sizeof(float) * 3 * nv, kind, s));
+    if (mesh->normals) HIP_TRY_DRAINED(s, hipMemcpyAsync(nrm, mesh->normals, sizeof(float) * 3 * nv, kind, s));
+    if (mesh->texcoords) HIP_TRY_DRAINED(s, hipMemcpyAsync(tex, mesh->texcoords, sizeof(float) * 2 * nv, kind, s));
     // the second instance table: the engine's own, then the prim offsets and the shape's pointers
     HIP_TRY_DRAINED(s, hipMemcpyAsync(gen.insts.get(), pt->d_insts(), sizeof(DevInstance) * ni, hipMemcpyDeviceToDevice, s));
-    const ReplaceMeshJob job{gen.insts.get(), ni, gen.inst_first.get(), sd.pos, pos.get(), nrm.get(), tex.get(), idx.get()};
+    const ReplaceMeshJob job{gen.insts.get(), ni, gen.inst_first.get(), sd.pos.get(), pos, nrm, tex, idx};
     launch_patch_instances(job, s);
     HIP_TRY_DRAINED(s, hipGetLastError());
     pt->accel.counts.launches += 2;  // with the tables' fill
@@ -1290,28 +1162,20 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
         DevInstance &d = gen.mirror[i];
         d.prim_offset = gen.first[i];
         if (d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape) {
-            d.positions = pos.get();
-            d.normals = nrm.get();
-            d.texcoords = tex.get();
-            d.indices = idx.get();
+            d.positions = pos;
+            d.normals = nrm;
+            d.texcoords = tex;
+            d.indices = idx;
         }
     }
     // ---- build: after the renders enqueued so far (the builders share the engine's stream with
     // nothing of theirs, but the swap below frees what they read)
     HIP_TRY_DRAINED(s, order_after_renders(pt));
-    ShapeDev fresh = sd;
-    fresh.num_vertices = mesh->num_vertices;
-    fresh.num_faces = mesh->num_faces;
-    fresh.pos = pos.get(), fresh.nrm = nrm.get(), fresh.tex = tex.get(), fresh.idx = idx.get();
-    fresh.prev = nullptr, fresh.prev_valid = false;
     if (const int rc = pt->accel.replace_shape(shape, fresh, used, gen)) return drained(s, rc);
     // ---- swap: the structure is published and the stream idle
     pt->pipe.invalidate();  // frames in flight were traced against the old geometry
     drop_stale(pt, true, false, &sd);
-    for (void *p : {(void *)sd.pos, (void *)sd.nrm, (void *)sd.tex, (void *)sd.idx}) pt->release(p);
-    for (void *p : {(void *)pos.release(), (void *)nrm.release(), (void *)tex.release(), (void *)idx.release()})
-        if (p) pt->allocs.push_back(p);
-    sd = fresh;
+    sd = std::move(fresh);  // the old arrays and the old snapshot go with the replaced value
     pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
     pt->accel.refits++;
     if (const int rc = derive_cull_set(pt)) return rc;  // the rebuild moved the records
@@ -1347,7 +1211,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     for (uint32_t i = 0; i < n; i++) {
         const pupil_instance &src = instances[i];
         if (src.shape >= pt->shapes.size()) return fail(PUPIL_ERR_INVALID, "instance shape out of range");
-        if (src.material >= pt->num_mats) return fail(PUPIL_ERR_INVALID, "instance material out of range");
+        if (src.material >= pt->materials.count()) return fail(PUPIL_ERR_INVALID, "instance material out of range");
         const ShapeDev &sd = pt->shapes[src.shape];
         counts[i] = sd.kind == PUPIL_SHAPE_SPHERE ? 1u : sd.num_faces;
         new_shape[i] = src.shape;
@@ -1358,7 +1222,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         b.flip_tex_coords = src.flip_tex_coords;
         b.emitter_offset = src.emitter_offset;
         b.hidden = visibility_mask && (visibility_mask[i] & 0xFFu) == 0u ? 1u : 0u;
-        b.bin = material_bin(pt->h_mats[src.material].type);
+        b.bin = material_bin(pt->materials.mirror()[src.material].type);
     }
     // the emitter table stays: the emissive instances are the old ones, in their order (so every
     // emitter range is one create checked against the table)
@@ -1374,8 +1238,9 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         const DevInstance &o = pt->h_insts()[old_em[k]];
         const pupil_instance &c = instances[new_em[k]];
         // the same material: its slot, or another slot of the same content
-        const bool same_material = o.material == c.material ||
-                                   std::memcmp(&pt->h_mats[o.material], &pt->h_mats[c.material], sizeof(DevMaterial)) == 0;
+        const std::vector<DevMaterial> &mats = pt->materials.mirror();
+        const bool same_material =
+            o.material == c.material || std::memcmp(&mats[o.material], &mats[c.material], sizeof(DevMaterial)) == 0;
         if (pt->accel.inst_shape[old_em[k]] != c.shape || !same_material || o.flip_normals != c.flip_normals ||
             o.flip_tex_coords != c.flip_tex_coords || o.emitter_offset != c.emitter_offset)
             return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances reordered or rebound: the emitter table would change");
@@ -1389,7 +1254,7 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     std::vector<InstShape> shape_tab(pt->shapes.size());  // the per-shape table
     for (size_t k = 0; k < pt->shapes.size(); k++) {
         const ShapeDev &sd = pt->shapes[k];
-        shape_tab[k] = InstShape{sd.kind, sd.num_faces, sd.pos, sd.nrm, sd.tex, sd.idx};
+        shape_tab[k] = InstShape{sd.kind, sd.num_faces, sd.pos.get(), sd.nrm.get(), sd.tex.get(), sd.idx.get()};
     }
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
@@ -1538,18 +1403,16 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
     const auto t0 = std::chrono::steady_clock::now();
     SceneAccel::Counts &cnt = pt->accel.counts;
     cnt = SceneAccel::Counts{};
-    if (!pt->d_move_stage) {  // the first call: the staging block (a header line, then one line per instance)
-        if (pt->alloc(&pt->d_move_stage, pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * ni) != hipSuccess) {
-            (void)hipGetLastError();
-            pt->d_move_stage = nullptr;
+    ScratchBuf<float> &move_stage = pt->per_inst.move_stage;
+    if (!move_stage.get()) {  // the first call: the staging block (a header line, then one line per instance)
+        if (move_stage.alloc(pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * ni) != hipSuccess)
             return fail(PUPIL_ERR_OOM, "instance staging allocation failed");
-        }
-        HIP_TRY(hipMemset(pt->d_move_stage, 0, sizeof(float) * pupil_pt::kMoveHeader));  // [0]: the skipped ids, a running total
+        HIP_TRY(hipMemset(move_stage.get(), 0, sizeof(float) * pupil_pt::kMoveHeader));  // [0]: the skipped ids, a running total
         const uint32_t so_far = (uint32_t)pt->inst_dev_skipped;  // pupil_pt_set_instances dropped an earlier block
-        if (so_far) HIP_TRY(hipMemcpy(pt->d_move_stage, &so_far, sizeof(so_far), hipMemcpyHostToDevice));
+        if (so_far) HIP_TRY(hipMemcpy(move_stage.get(), &so_far, sizeof(so_far), hipMemcpyHostToDevice));
     }
     HIP_TRY(order_after_caller(pt, hip_stream));
-    std::vector<uint32_t> &ids = pt->h_move_ids;  // the list as the caller gave it
+    std::vector<uint32_t> &ids = pt->per_inst.h_move_ids;  // the list as the caller gave it
     ids.resize(n);
     if (ids_device) {
         HIP_TRY(hipMemcpyAsync(ids.data(), ids_device, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, pt->own_stream));
@@ -1559,7 +1422,7 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
         for (uint32_t k = 0; k < n; k++) ids[k] = k;
     }
     std::vector<uint32_t> changed;  // the ids in range, each once
-    std::vector<uint8_t> &seen = pt->h_move_seen;
+    std::vector<uint8_t> &seen = pt->per_inst.h_move_seen;
     seen.assign(ni, 0);
     bool emissive = false;
     for (uint32_t id : ids) {
@@ -1582,8 +1445,8 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
     job.to_object = (const float *)to_object_device;
     job.margins = pt->accel.two_level ? 1u : 0u;
     job.fallback = changed.empty() ? 0u : changed[0];
-    job.stage = pt->d_move_stage + pupil_pt::kMoveHeader;
-    job.skipped = reinterpret_cast<uint32_t *>(pt->d_move_stage);
+    job.stage = move_stage.get() + pupil_pt::kMoveHeader;
+    job.skipped = reinterpret_cast<uint32_t *>(move_stage.get());
     if (!changed.empty())
         if (const int rc = pt->accel.move_begin(&job.list, &job.moved)) return rc;
     launch_move_instances(job, pt->own_stream);
@@ -1591,9 +1454,9 @@ int pupil_pt_update_instances_device(pupil_pt *pt, uint32_t n, const uint32_t *i
     cnt.launches++;
     if (!changed.empty()) pt->accel.move_boxes(n, job.stage + kMoveStageBox, kMoveStageFloats);
     // the host mirror: what the device computed, in one copy
-    std::vector<float> &st = pt->h_move_stage;
+    std::vector<float> &st = pt->per_inst.h_move_stage;
     st.resize(pupil_pt::kMoveHeader + (size_t)kMoveStageFloats * n);
-    HIP_TRY(hipMemcpyAsync(st.data(), pt->d_move_stage, sizeof(float) * st.size(), hipMemcpyDeviceToHost, pt->own_stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), move_stage.get(), sizeof(float) * st.size(), hipMemcpyDeviceToHost, pt->own_stream));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     cnt.syncs++;
     uint32_t skipped_total = 0;
@@ -1714,86 +1577,46 @@ int pupil_pt_device_emitters_info(pupil_pt *pt, uint32_t *enabled, uint64_t *ref
     return PUPIL_OK;
 }
 
-// Materials replaced in place: convert_material is the host precompute of create, so d_mats[ids[k]]
-// becomes what a fresh engine would hold.  Everything that can refuse the call runs first; then,
-// on the engine's stream after the renders enqueued so far, the texels (a bitmap slot of an
-// unchanged texel count keeps its allocation), the changed DevMaterial entries and -- when a type
-// changed -- the bins of the instances that use it, the records' bin words and the shading
-// schedule derived from the bins.  No box or link of the acceleration structure depends on a
-// material: accel_refits stays.  Returns once the stream has passed the copies, and frees the
-// replaced texels then.
+// Materials replaced in place: convert_material is the host precompute of create, so each named
+// material becomes what a fresh engine would hold.  Stage: everything that can refuse the call,
+// the fresh texels included (a bitmap slot of an unchanged texel count keeps its allocation), runs
+// before anything of the engine changes.  Commit: on the engine's stream after the renders enqueued
+// so far, the texels, the changed DevMaterial entries and -- when a type changed -- the bins of the
+// instances that use it, the records' bin words and the shading schedule derived from the bins.
+// No box or link of the acceleration structure depends on a material: accel_refits stays.
+// Returns once the stream has passed the copies, and frees the replaced texels then.
 int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, const pupil_material *materials) {
     if (!pt || (n && (!ids || !materials))) return fail(PUPIL_ERR_INVALID, "null argument");
-    std::vector<DevMaterial> conv(n);
-    for (uint32_t k = 0; k < n; k++) {
-        if (ids[k] >= pt->num_mats) return fail(PUPIL_ERR_INVALID, "material index out of range");
-        if (const int rc = convert_material(materials[k], conv[k])) return rc;
-    }
     if (n == 0) return PUPIL_OK;
     HIP_TRY(hipSetDevice(pt->device));
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint8_t> last(n, 1);  // an id named twice: its last material is the one that counts
-    for (uint32_t k = 0; k < n; k++)
-        for (uint32_t j = k + 1; j < n && last[k]; j++) last[k] = ids[j] != ids[k];
-    std::vector<void *> fresh, stale;
-    for (uint32_t k = 0; k < n; k++) {
-        if (!last[k]) continue;
-        for (int s = 0; s < 4; s++) {
-            DevTexture &nt = conv[k].tex[s];
-            const DevTexture &ot = pt->h_mats[ids[k]].tex[s];
-            const bool had = ot.type == PUPIL_TEX_BITMAP && ot.data;
-            const size_t count = (size_t)nt.width * nt.height;
-            if (nt.type == PUPIL_TEX_BITMAP && had && (size_t)ot.width * ot.height == count) {
-                nt.data = ot.data;
-                continue;
-            }
-            if (had) stale.push_back((void *)ot.data);
-            if (nt.type != PUPIL_TEX_BITMAP) continue;
-            float4 *texels = nullptr;
-            if (pt->alloc(&texels, count) != hipSuccess) {  // nothing of the engine has changed yet
-                (void)hipGetLastError();
-                for (void *p : fresh) pt->release(p);
-                return fail(PUPIL_ERR_OOM, "texel allocation failed");
-            }
-            fresh.push_back(texels);
-            nt.data = texels;
-        }
-    }
+    hipStream_t s = pt->own_stream;
+    EngineMaterials::Staged staged_mats;
+    if (const int rc = pt->materials.stage(n, ids, materials, staged_mats)) return rc;
     HIP_TRY(order_after_renders(pt));  // no render may still read the old materials
     pt->pipe.invalidate();          // frames in flight were shaded with them
+    std::vector<EngineMaterials::Texels> replaced;
     bool type_changed = false;
-    for (uint32_t k = 0; k < n; k++) {
-        if (!last[k]) continue;
-        for (int s = 0; s < 4; s++)
-            if (conv[k].tex[s].type == PUPIL_TEX_BITMAP)
-                HIP_TRY(hipMemcpyAsync((void *)conv[k].tex[s].data, materials[k].tex[s].rgba,
-                                       sizeof(float4) * (size_t)conv[k].tex[s].width * conv[k].tex[s].height,
-                                       hipMemcpyHostToDevice, pt->own_stream));
-        DevMaterial &h = pt->h_mats[ids[k]];
-        type_changed = type_changed || h.type != conv[k].type;
-        h = conv[k];
-        HIP_TRY(hipMemcpyAsync(pt->d_mats + ids[k], &h, sizeof(DevMaterial), hipMemcpyHostToDevice, pt->own_stream));
-    }
+    if (const int rc = pt->materials.commit(staged_mats, s, replaced, type_changed)) return drained(s, rc);
     std::vector<DevInstance> staged;  // outlives the copies (synchronised below)
     if (type_changed) {
         staged.reserve(pt->h_insts().size());
         for (size_t i = 0; i < pt->h_insts().size(); i++) {
             DevInstance &d = pt->h_insts()[i];
-            const uint32_t bin = material_bin(pt->h_mats[d.material].type);
+            const uint32_t bin = material_bin(pt->materials.mirror()[d.material].type);
             if (bin == d.bin) continue;
             d.bin = bin;
             staged.push_back(device_instance(d));
-            HIP_TRY(hipMemcpyAsync(pt->d_insts() + i, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice,
-                                   pt->own_stream));
+            HIP_TRY_DRAINED(s, hipMemcpyAsync(pt->d_insts() + i, &staged.back(), sizeof(DevInstance), hipMemcpyHostToDevice, s));
         }
         if (!staged.empty()) {
             pt->accel.update_bins();
-            HIP_TRY(hipGetLastError());
+            HIP_TRY_DRAINED(s, hipGetLastError());
             derive_bins(pt);
         }
     }
-    HIP_TRY(hipStreamSynchronize(pt->own_stream));
-    for (void *p : stale) pt->release(p);  // the stream has passed them
+    HIP_TRY(hipStreamSynchronize(s));
+    replaced.clear();  // the stream has passed them
     pt->mat_updates++;
     pt->mat_ms = ms_since(t0);
     return derive_cull_set(pt, false);
@@ -1806,8 +1629,8 @@ int pupil_pt_update_materials(pupil_pt *pt, uint32_t n, const uint32_t *ids, con
 int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slot, const void *rgba_device,
                                    uint32_t width, uint32_t height, void *hip_stream) {
     if (!pt || !rgba_device) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (material >= pt->num_mats || slot >= 4u) return fail(PUPIL_ERR_INVALID, "no such material texture");
-    const DevMaterial &m = pt->h_mats[material];
+    if (material >= pt->materials.count() || slot >= 4u) return fail(PUPIL_ERR_INVALID, "no such material texture");
+    const DevMaterial &m = pt->materials.mirror()[material];
     const DevTexture &t = m.tex[slot];
     if (t.type != PUPIL_TEX_BITMAP || !t.data)
         return fail(PUPIL_ERR_INVALID, "the slot holds no bitmap: make it one with pupil_pt_update_materials first");
@@ -1824,7 +1647,7 @@ int pupil_pt_update_texture_device(pupil_pt *pt, uint32_t material, uint32_t slo
     const uint32_t diffuse_slot = m.type == PUPIL_MAT_PLASTIC ? 0u : 1u;
     if ((m.type == PUPIL_MAT_PLASTIC || m.type == PUPIL_MAT_ROUGH_PLASTIC) &&
         (slot == diffuse_slot || slot == diffuse_slot + 1u)) {
-        launch_specular_weight(pt->d_mats + material, pt->own_stream);  // h_mats keeps the stale weight
+        launch_specular_weight(pt->materials.device() + material, pt->own_stream);  // the mirror keeps the stale weight
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
@@ -1931,18 +1754,18 @@ int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_laun
     fp.albedo = (float *)out->albedo;
     fp.normal = (float *)out->normal;
     fp.test = (float *)out->test;
-    fp.nee_count = stats ? pt->trace_counters + 16 : nullptr;
-    fp.cull_cum = pt->sc.cull_n ? pt->cull_cum : nullptr;
+    fp.nee_count = stats ? pt->trace_counters.get() + 16 : nullptr;
+    fp.cull_cum = pt->sc.cull_n ? pt->cull_cum.get() : nullptr;
     // the culled-ray totals as they are before this render (pupil_pt_stats: its own count)
     pt->cull_counted = pt->cull_counted || pt->sc.cull_n != 0u;
     if (pt->cull_counted)
-        HIP_TRY(hipMemcpyAsync(pt->cull_cum + kCullShards * kCullStride, pt->cull_cum,
+        HIP_TRY(hipMemcpyAsync(pt->cull_cum.get() + kCullShards * kCullStride, pt->cull_cum.get(),
                                sizeof(unsigned long long) * kCullShards * kCullStride, hipMemcpyDeviceToDevice, s));
 
     // PUPIL_STATS_TRACE_TIMING: events around the traversal launches only, summed over
     // every render since pupil_pt_stats last read them (a timed sequence of renders)
     const bool trace_timing = (launch->collect_stats & PUPIL_STATS_TRACE_TIMING) != 0 && !timing;
-    RenderCtx cx{pt, s, stats, timing || trace_timing, TraceStats{pt->trace_counters}, key};
+    RenderCtx cx{pt, s, stats, timing || trace_timing, TraceStats{pt->trace_counters.get()}, key};
     cx.trace_only = trace_timing;
     if (!(trace_timing && pt->pairs_keep)) {  // a new sum
         pt->trace_pairs = 0;
@@ -1961,11 +1784,11 @@ int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_laun
     cx.pair = trace_timing ? pt->trace_pairs : 0u;
     pt->pairs_keep = trace_timing;
     const bool tail = stats && std::getenv("PUPIL_TRACE_TAIL");
-    if (tail && !pt->tail_buf) {
+    if (tail && !pt->tail_buf.get()) {
         pt->tail_waves = pt->ovf_threads / 64u;
-        if (pt->alloc(&pt->tail_buf, (size_t)(kMaxDepth + 1) * pt->tail_waves * 4)) return fail(PUPIL_ERR_OOM, "tail buffer");
+        if (pt->tail_buf.alloc((size_t)(kMaxDepth + 1) * pt->tail_waves * 4)) return fail(PUPIL_ERR_OOM, "tail buffer");
     }
-    if (tail) HIP_TRY(hipMemsetAsync(pt->tail_buf, 0, sizeof(unsigned long long) * (kMaxDepth + 1) * pt->tail_waves * 4, s));
+    if (tail) HIP_TRY(hipMemsetAsync(pt->tail_buf.get(), 0, sizeof(unsigned long long) * (kMaxDepth + 1) * pt->tail_waves * 4, s));
     cx.tail = tail;
     pt->tail_launches = 0;
     // events only when times are asked for: one pair per stage launch (kind 0 primary extend,
@@ -1976,13 +1799,13 @@ int pupil_pt_render(pupil_pt *pt, const pupil_pt_frame *out, const pupil_pt_laun
         while (pt->trace_events.size() < 2 * pairs_needed) {
             hipEvent_t e;
             HIP_TRY(hipEventCreate(&e));
-            pt->trace_events.push_back(e);
+            pt->trace_events.emplace_back(e);
         }
         if (pt->pair_kind.size() < pairs_needed) pt->pair_kind.resize(pairs_needed, 0);
     }
     pt->last_timed = stats || timing;
     if (pt->last_timed) HIP_TRY(hipEventRecord(pt->ev_begin, s));
-    if (stats) HIP_TRY(hipMemsetAsync(pt->trace_counters, 0, 32 * sizeof(unsigned long long), s));
+    if (stats) HIP_TRY(hipMemsetAsync(pt->trace_counters.get(), 0, 32 * sizeof(unsigned long long), s));
     const int rc = render_pipelined(cx, fp, launch);
     if (rc) return rc;
     if (pt->last_timed) HIP_TRY(hipEventRecord(pt->ev_end, s));
@@ -2002,12 +1825,12 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
     if (pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
     pupil_pt_counters c = pt->totals;
     unsigned long long cum[4] = {0, 0, 0, 0};  // running totals, then their values before the last render
-    HIP_TRY(hipMemcpy(cum, pt->ray_cum, sizeof(cum), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cum, pt->ray_cum.get(), sizeof(cum), hipMemcpyDeviceToHost));
     // extension rays the terminal-ray cull resolved: in all, and before the last render
     unsigned long long culled[2] = {0, 0};
     if (pt->cull_counted) {
         std::vector<unsigned long long> shards(2 * kCullShards * kCullStride);
-        HIP_TRY(hipMemcpy(shards.data(), pt->cull_cum, sizeof(unsigned long long) * shards.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(shards.data(), pt->cull_cum.get(), sizeof(unsigned long long) * shards.size(), hipMemcpyDeviceToHost));
         for (uint32_t h = 0; h < 2; h++)
             for (uint32_t k = 0; k < kCullShards; k++) culled[h] += shards[(h * kCullShards + k) * kCullStride];
     }
@@ -2049,9 +1872,9 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
         c.extend_launches = kind_n[0];
         c.shade_ms = kind_ms[2];
         c.frame_ms = kind_ms[3];
-        if (pt->last_stats && pt->tail_buf && pt->tail_launches) {  // PUPIL_TRACE_TAIL summary on stderr
+        if (pt->last_stats && pt->tail_buf.get() && pt->tail_launches) {  // PUPIL_TRACE_TAIL summary on stderr
             std::vector<unsigned long long> tb((size_t)pt->tail_launches * pt->tail_waves * 4);
-            HIP_TRY(hipMemcpy(tb.data(), pt->tail_buf, sizeof(unsigned long long) * tb.size(), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(tb.data(), pt->tail_buf.get(), sizeof(unsigned long long) * tb.size(), hipMemcpyDeviceToHost));
             for (uint32_t l = 0; l < pt->tail_launches; l++) {
                 const unsigned long long *w = tb.data() + (size_t)l * pt->tail_waves * 4;
                 std::vector<double> st, dr, ex;
@@ -2079,7 +1902,7 @@ int pupil_pt_stats(pupil_pt *pt, pupil_pt_counters *out) {
         }
         if (pt->last_stats) {
             unsigned long long tc[32];
-            HIP_TRY(hipMemcpy(tc, pt->trace_counters, sizeof(tc), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(tc, pt->trace_counters.get(), sizeof(tc), hipMemcpyDeviceToHost));
             if (std::getenv("PUPIL_TRACE_DIAG") && tc[2]) {  // SIMD efficiency, persistent kernels
                 const unsigned long long *d = tc + 2;
                 const double visits = (double)std::max(1ull, tc[0] + tc[14]);
@@ -2126,7 +1949,7 @@ int pupil_pt_shadow_info(pupil_pt *pt, uint64_t *occluded_rays, uint64_t *occlud
     HIP_TRY(hipSetDevice(pt->device));
     if (pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
     unsigned long long tc[32] = {};
-    if (pt->last_stats) HIP_TRY(hipMemcpy(tc, pt->trace_counters, sizeof(tc), hipMemcpyDeviceToHost));
+    if (pt->last_stats) HIP_TRY(hipMemcpy(tc, pt->trace_counters.get(), sizeof(tc), hipMemcpyDeviceToHost));
     if (occluded_visits) *occluded_visits = tc[24];
     if (occluded_rays) *occluded_rays = tc[25];
     if (overlap_order) *overlap_order = pt->any_overlap;
@@ -2163,25 +1986,21 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
     if (n == 0) return PUPIL_OK;
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(hipDeviceSynchronize());  // no render on another stream may still use the shared overflow stacks
-    float *d_rays = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_rays, sizeof(float) * 8 * (size_t)n));
-    hipError_t e = hipMalloc((void **)&d_out, sizeof(float) * 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, sizeof(float) * 8 * (size_t)n, hipMemcpyHostToDevice);
+    ScratchBuf<float> d_rays, d_out;
+    HIP_TRY(upload(d_rays, rays, 8 * (size_t)n));
+    HIP_TRY(d_out.alloc(4 * (size_t)n));
     // PUPIL_TRACE_RAYS_STATS: the counter kernels (queue accounting, node visits), read back
     // by pupil_pt_stats like a collect_stats render's
     const bool stats = std::getenv("PUPIL_TRACE_RAYS_STATS") != nullptr;
-    TraceStats ts{pt->trace_counters};
-    if (e == hipSuccess) {
-        e = hipMemsetAsync(pt->q.work + kWorkRays, 0, kWorkKind * sizeof(uint32_t), pt->own_stream);
-        if (e == hipSuccess && stats) e = hipMemsetAsync(pt->trace_counters, 0, 32 * sizeof(unsigned long long), pt->own_stream);
-        if (e == hipSuccess) e = hipEventRecord(pt->ev_begin, pt->own_stream);
-        if (e == hipSuccess)
-            launch_trace_debug(pt->sc, d_rays, d_out, n, any_hit, pt->ovf, pt->ovf_threads, pt->q.work + kWorkRays,
-                               pt->own_stream, stats ? &ts : nullptr, pt->any_overlap);
-        if (e == hipSuccess) e = hipEventRecord(pt->ev_end, pt->own_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(pt->own_stream);
-    }
-    if (e == hipSuccess && stats) {
+    TraceStats ts{pt->trace_counters.get()};
+    HIP_TRY(hipMemsetAsync(pt->q.work + kWorkRays, 0, kWorkKind * sizeof(uint32_t), pt->own_stream));
+    if (stats) HIP_TRY(hipMemsetAsync(pt->trace_counters.get(), 0, 32 * sizeof(unsigned long long), pt->own_stream));
+    HIP_TRY(hipEventRecord(pt->ev_begin, pt->own_stream));
+    launch_trace_debug(pt->sc, d_rays.get(), d_out.get(), n, any_hit, pt->ovf.get(), pt->ovf_threads, pt->q.work + kWorkRays,
+                       pt->own_stream, stats ? &ts : nullptr, pt->any_overlap);
+    HIP_TRY(hipEventRecord(pt->ev_end, pt->own_stream));
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    if (stats) {
         pt->last_paths = n;
         pt->last_iters = 0;
         pt->last_primary = n;
@@ -2194,10 +2013,7 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
         pt->rendered = true;
         pt->last_stream = pt->own_stream;
     }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(d_rays);
-    if (d_out) (void)hipFree(d_out);
-    HIP_TRY(e);
+    HIP_TRY(hipMemcpy(out, d_out.get(), sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost));
     return PUPIL_OK;
 }
 
@@ -2233,10 +2049,10 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
     uint32_t num_local = 0;
     if (const int rc = local_pixel_map(pt, key, &job.pixel_map, &num_local)) return rc;
     if (num_local == 0) return PUPIL_OK;
-    if (!pt->flow_hits) {  // first use: lists for the whole image serve every tiling (num_local <= w * h)
+    if (!pt->flow_hits.get()) {  // first use: lists for the whole image serve every tiling (num_local <= w * h)
         const size_t cap = (size_t)pt->width * pt->height;
-        if (!pt->flow_rays) HIP_TRY(pt->alloc(&pt->flow_rays, 2 * cap));
-        HIP_TRY(pt->alloc(&pt->flow_hits, cap));
+        if (!pt->flow_rays.get()) HIP_TRY(pt->flow_rays.alloc(2 * cap));
+        HIP_TRY(pt->flow_hits.alloc(cap));
     }
     if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
         HIP_TRY(hipEventRecord(pt->ev_sync, pt->last_stream));
@@ -2244,41 +2060,42 @@ int pupil_pt_motion_vectors(pupil_pt *pt, const float prev_sample_to_camera[16],
     }
     // vertex snapshots held: after the last snapshot copy (the vertex update that followed it has
     // synchronised the engine's stream), with the per-instance table of snapshot arrays
+    InstanceScratch &in = pt->per_inst;
     const bool table = pt->snapshots > 0 && pt->flow_verts_stale;
     if (pt->snapshots > 0) HIP_TRY(hipStreamWaitEvent(s, pt->ev_snap, 0));
     if (prev_to_world || table) {
-        if (!pt->ev_flow) HIP_TRY(hipEventCreateWithFlags(&pt->ev_flow, hipEventDisableTiming));
+        if (!pt->ev_flow) HIP_TRY(hipEventCreateWithFlags(pt->ev_flow.put(), hipEventDisableTiming));
         else HIP_TRY(hipEventSynchronize(pt->ev_flow));  // the previous upload has left the staging copies
     }
     if (prev_to_world) {
         const size_t nf = 12 * pt->h_insts().size();
-        if (!pt->flow_prev) HIP_TRY(pt->alloc(&pt->flow_prev, nf));
-        pt->h_flow_prev.assign(prev_to_world, prev_to_world + nf);
-        if (nf) HIP_TRY(hipMemcpyAsync(pt->flow_prev, pt->h_flow_prev.data(), sizeof(float) * nf, hipMemcpyHostToDevice, s));
-        job.prev_to_world = pt->flow_prev;
+        if (!in.flow_prev.get()) HIP_TRY(in.flow_prev.alloc(nf));
+        in.h_flow_prev.assign(prev_to_world, prev_to_world + nf);
+        if (nf) HIP_TRY(hipMemcpyAsync(in.flow_prev.get(), in.h_flow_prev.data(), sizeof(float) * nf, hipMemcpyHostToDevice, s));
+        job.prev_to_world = in.flow_prev.get();
     }
     if (table) {
         const size_t ni = pt->h_insts().size();
-        if (!pt->flow_verts) HIP_TRY(pt->alloc(&pt->flow_verts, ni));
-        pt->h_flow_verts.assign(ni, nullptr);
+        if (!in.flow_verts.get()) HIP_TRY(in.flow_verts.alloc(ni));
+        in.h_flow_verts.assign(ni, nullptr);
         for (size_t i = 0; i < ni; i++) {
             const ShapeDev &sd = pt->shapes[pt->accel.inst_shape[i]];
-            if (sd.kind == PUPIL_SHAPE_MESH && sd.prev_valid) pt->h_flow_verts[i] = sd.prev;
+            if (sd.kind == PUPIL_SHAPE_MESH && sd.prev_valid) in.h_flow_verts[i] = sd.prev.get();
         }
-        HIP_TRY(hipMemcpyAsync(pt->flow_verts, pt->h_flow_verts.data(), sizeof(const float *) * ni, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(in.flow_verts.get(), in.h_flow_verts.data(), sizeof(const float *) * ni, hipMemcpyHostToDevice, s));
         pt->flow_verts_stale = false;
     }
     if (prev_to_world || table) HIP_TRY(hipEventRecord(pt->ev_flow, s));
-    const float *const *prev_verts = pt->snapshots > 0 ? pt->flow_verts : nullptr;
+    const float *const *prev_verts = pt->snapshots > 0 ? in.flow_verts.get() : nullptr;
     job.width = pt->width;
     job.height = pt->height;
     job.n = num_local;
     job.compact = compact;
     HIP_TRY(hipMemsetAsync(pt->q.work + kWorkFlow, 0, kWorkKind * sizeof(uint32_t), s));
-    launch_flow_rays(pt->sc, pt->width, pt->height, job.pixel_map, num_local, 0.5f, 0.5f, pt->flow_rays, s);
-    launch_trace_debug(pt->sc, (const float *)pt->flow_rays, (float *)pt->flow_hits, num_local, 0, pt->ovf,
+    launch_flow_rays(pt->sc, pt->width, pt->height, job.pixel_map, num_local, 0.5f, 0.5f, pt->flow_rays.get(), s);
+    launch_trace_debug(pt->sc, (const float *)pt->flow_rays.get(), (float *)pt->flow_hits.get(), num_local, 0, pt->ovf.get(),
                        pt->ovf_threads, pt->q.work + kWorkFlow, s);
-    launch_flow_project(pt->sc, job, pt->flow_rays, pt->flow_hits, (float2 *)out_flow, s, prev_verts);
+    launch_flow_project(pt->sc, job, pt->flow_rays.get(), pt->flow_hits.get(), (float2 *)out_flow, s, prev_verts);
     HIP_TRY(hipGetLastError());
     pt->last_stream = s;
     pt->rendered = true;
@@ -2324,27 +2141,26 @@ int run_query(pupil_pt *pt, uint32_t n, const float4 *rays, uint32_t flags, cons
     const bool geo = out->position || out->normal || out->texcoord;
     const bool resolved = geo || out->instance || out->primitive || out->material;
     if (!pt->ev_q0) {
-        HIP_TRY(hipEventCreate(&pt->ev_q0));
-        HIP_TRY(hipEventCreate(&pt->ev_q1));
+        HIP_TRY(hipEventCreate(pt->ev_q0.put()));
+        HIP_TRY(hipEventCreate(pt->ev_q1.put()));
     }
     float4 *hits = (float4 *)out->hit;
     if (!hits || scatter) {  // resolved outputs without the hits: the engine's scratch holds them
         if (pt->query_cap < n) {
             // the scratch a query still in flight reads is freed only once its stream has passed it
-            if (pt->query_hits && pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
+            if (pt->query_hits.get() && pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
             const size_t cap = std::max<size_t>(n, 2 * pt->query_cap);
-            float4 *grown = nullptr;
-            HIP_TRY(pt->alloc(&grown, cap));
-            pt->release(pt->query_hits);
-            pt->query_hits = grown;
+            ScratchBuf<float4> grown;  // the old block outlives the allocation of the new one
+            HIP_TRY(grown.alloc(cap));
+            pt->query_hits = std::move(grown);
             pt->query_cap = cap;
             pt->query_grows++;
         }
-        hits = pt->query_hits;
+        hits = pt->query_hits.get();
     }
     const bool slots = geo && !pt->sc.two_level;  // reconstruct() names flat records by slot
-    if (slots && !pt->query_slot) {
-        HIP_TRY(pt->alloc(&pt->query_slot, pt->tables.cur().num_prims));
+    if (slots && !pt->query_slot.get()) {
+        HIP_TRY(pt->query_slot.alloc(pt->tables.cur().num_prims));
         pt->query_grows++;
     }
     if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
@@ -2354,19 +2170,19 @@ int run_query(pupil_pt *pt, uint32_t n, const float4 *rays, uint32_t flags, cons
     HIP_TRY(hipEventRecord(pt->ev_q0, s));
     make_rays();
     HIP_TRY(hipMemsetAsync(pt->q.work + kWorkQuery, 0, kWorkKind * sizeof(uint32_t), s));
-    launch_trace_debug(pt->sc, (const float *)rays, (float *)hits, n, any ? 1 : 0, pt->ovf, pt->ovf_threads,
+    launch_trace_debug(pt->sc, (const float *)rays, (float *)hits, n, any ? 1 : 0, pt->ovf.get(), pt->ovf_threads,
                        pt->q.work + kWorkQuery, s, nullptr, pt->any_overlap);
     if (resolved || scatter) {
         const uint32_t rec_slots = slots ? pt->accel.world_record_slots() : 1u;
         if (slots && !pt->query_slot_valid) {
-            launch_query_prim_slots(pt->sc.prims, rec_slots, pt->tables.cur().num_prims, pt->query_slot, s);
+            launch_query_prim_slots(pt->sc.prims, rec_slots, pt->tables.cur().num_prims, pt->query_slot.get(), s);
             pt->query_slot_valid = true;
         }
         const QueryJob job{rays,
                            hits,
                            n,
                            rec_slots,
-                           slots ? pt->query_slot : nullptr,
+                           slots ? pt->query_slot.get() : nullptr,
                            (int32_t *)out->instance,
                            (int32_t *)out->primitive,
                            (int32_t *)out->material,
@@ -2429,8 +2245,8 @@ int pupil_pt_query_camera(pupil_pt *pt, float jitter_x, float jitter_y, uint32_t
     const uint32_t *scatter = compact ? nullptr : map;
     float4 *rays = (float4 *)rays_out_device;
     if (!rays) {  // the flow pass's list, sized for the whole image: it serves every tiling
-        if (!pt->flow_rays) HIP_TRY(pt->alloc(&pt->flow_rays, 2 * (size_t)pt->width * pt->height));
-        rays = pt->flow_rays;
+        if (!pt->flow_rays.get()) HIP_TRY(pt->flow_rays.alloc(2 * (size_t)pt->width * pt->height));
+        rays = pt->flow_rays.get();
     }
     return run_query(pt, num_local, rays, 0u, out, s, scatter, [&] {
         launch_flow_rays(pt->sc, pt->width, pt->height, map, num_local, jitter_x, jitter_y, rays, s);
@@ -2466,17 +2282,15 @@ namespace {
 // last_stream) and fills the id list on s.  A call that fits allocates and synchronises nothing.
 int ensure_radiance_state(pupil_pt *pt, size_t need, hipStream_t s) {
     if (need <= pt->rad_cap) return PUPIL_OK;
-    if (pt->rad_block && pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
+    if (pt->rad_block.get() && pt->rendered) HIP_TRY(hipStreamSynchronize(pt->last_stream));
     const size_t cap = std::min(pt->rad_chunk, std::max(need, 2 * pt->rad_cap));
     auto up = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
     const size_t rec = up(16 * cap), byte = up(cap);
     const size_t hist = up(sizeof(uint32_t) * partition_hist_entries((uint32_t)cap));
     const size_t total = 8 * rec + 2 * byte + up(4 * cap) + up(8 * cap) + up(4 * cap) + hist + up(4 * kCountSlots);
-    if (pt->rad_block) (void)hipFree(pt->rad_block);
-    pt->rad_block = nullptr;
     pt->rad_cap = 0;
-    HIP_TRY(hipMalloc(&pt->rad_block, total));
-    char *b = (char *)pt->rad_block;
+    HIP_TRY(pt->rad_block.alloc(total));
+    char *b = pt->rad_block.get();
     auto take = [&b](size_t bytes) {
         char *p = b;
         b += bytes;
@@ -2538,21 +2352,21 @@ int radiance_chunk(pupil_pt *pt, hipStream_t s, const float4 *rays, const uint32
     fp.accum = (float4 *)out->radiance + r0;
     fp.albedo = out->albedo ? (float *)out->albedo + 3 * (size_t)r0 : nullptr;
     fp.normal = out->normal ? (float *)out->normal + 3 * (size_t)r0 : nullptr;
-    fp.cull_cum = pt->sc.cull_n ? pt->rad_cum : nullptr;
+    fp.cull_cum = pt->sc.cull_n ? pt->rad_cum.get() : nullptr;
     for (uint32_t b = 0; b < depth; b++) {
         if (b == 0) {
-            launch_extend(pt->sc, ps, q, pt->rad_ids, nullptr, np, pt->ovf, pt->ovf_threads, nullptr, s);
+            launch_extend(pt->sc, ps, q, pt->rad_ids, nullptr, np, pt->ovf.get(), pt->ovf_threads, nullptr, s);
         } else {
             // the rays the last shade spawned, in increasing path id: next and shadow lists -> q.nxsh
             launch_partition(ps.sflags, np, 2, kPartFlags, sflag_tag(depth, b - 1), q.nxsh, q.hist, q.counts + kCntNext,
-                             q.counts + kStartNext, nullptr, nullptr, s, pt->rad_cum + pupil_pt::kRadTotals, nullptr);
+                             q.counts + kStartNext, nullptr, nullptr, s, pt->rad_cum.get() + pupil_pt::kRadTotals, nullptr);
             if (depth > 64 && b % 16 == 0) {  // as a render of such a depth: stop once no path is left
                 uint32_t c[2] = {1, 1};
                 HIP_TRY(hipMemcpyAsync(c, q.counts + kCntNext, sizeof(c), hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipStreamSynchronize(s));
                 if (c[0] == 0 && c[1] == 0) break;
             }
-            launch_trace_mixed(pt->sc, ps, q, pt->ovf, pt->ovf_threads, nullptr, s, 0u, 0u, 0u, 0u, 0u, pt->any_overlap);
+            launch_trace_mixed(pt->sc, ps, q, pt->ovf.get(), pt->ovf_threads, nullptr, s, 0u, 0u, 0u, 0u, 0u, pt->any_overlap);
         }
         if (!pt->shade_list)
             launch_partition(ps.mbin, np, kPartMaxBins, kPartExclusive, 0u, q.bins, q.hist, q.counts,
@@ -2593,8 +2407,8 @@ int pupil_pt_radiance_rays(pupil_pt *pt, uint32_t n, const void *rays_device, co
     const uint32_t sb = (uint32_t)std::min<size_t>(launch->spp, pt->rad_chunk);
     const uint32_t per = (uint32_t)std::min<size_t>(n, pt->rad_chunk / sb);
     if (!pt->ev_r0) {
-        HIP_TRY(hipEventCreate(&pt->ev_r0));
-        HIP_TRY(hipEventCreate(&pt->ev_r1));
+        HIP_TRY(hipEventCreate(pt->ev_r0.put()));
+        HIP_TRY(hipEventCreate(pt->ev_r1.put()));
     }
     if (const int rc = ensure_radiance_state(pt, (size_t)sb * per, s)) return rc;
     if (pt->rendered && s != pt->last_stream) {  // another stream: after everything the last one holds
@@ -2634,7 +2448,7 @@ int pupil_pt_radiance_info(pupil_pt *pt, uint64_t *calls, uint64_t *rays, uint64
     HIP_TRY(hipEventSynchronize(pt->ev_r1));
     if (extension_rays || shadow_rays) {
         std::vector<unsigned long long> cum(pupil_pt::kRadTotals + 2);
-        HIP_TRY(hipMemcpy(cum.data(), pt->rad_cum, sizeof(unsigned long long) * cum.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cum.data(), pt->rad_cum.get(), sizeof(unsigned long long) * cum.size(), hipMemcpyDeviceToHost));
         unsigned long long culled = 0;  // cast by the integrator and counted like a traced ray
         for (uint32_t k = 0; k < kCullShards; k++) culled += cum[k * kCullStride];
         if (extension_rays) *extension_rays = cum[pupil_pt::kRadTotals] + culled;
@@ -2653,19 +2467,13 @@ int pupil_debug_select_emitter(pupil_pt *pt, uint32_t n, const float *p, int32_t
     if (n == 0) return PUPIL_OK;
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(hipDeviceSynchronize());
-    float *dp = nullptr;
-    int *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&dp, sizeof(float) * n));
-    hipError_t err = hipMalloc((void **)&dout, sizeof(int) * n);
-    if (err == hipSuccess) err = hipMemcpy(dp, p, sizeof(float) * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        launch_debug_select(pt->sc, dp, dout, n, pt->own_stream);
-        err = hipStreamSynchronize(pt->own_stream);
-    }
-    if (err == hipSuccess) err = hipMemcpy(out, dout, sizeof(int) * n, hipMemcpyDeviceToHost);
-    (void)hipFree(dp);
-    if (dout) (void)hipFree(dout);
-    HIP_TRY(err);
+    ScratchBuf<float> dp;
+    ScratchBuf<int> dout;
+    HIP_TRY(upload(dp, p, n));
+    HIP_TRY(dout.alloc(n));
+    launch_debug_select(pt->sc, dp.get(), dout.get(), n, pt->own_stream);
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    HIP_TRY(hipMemcpy(out, dout.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
     return PUPIL_OK;
 }
 
@@ -2733,19 +2541,13 @@ template <typename Launch>
 int debug_probe(pupil_pt *pt, uint32_t n, const float *in, uint32_t in_w, float *out, uint32_t out_w, Launch launch) {
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&din, sizeof(float) * in_w * n));
-    hipError_t err = hipMalloc((void **)&dout, sizeof(float) * out_w * n);
-    if (err == hipSuccess) err = hipMemcpy(din, in, sizeof(float) * in_w * n, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        launch(din, dout);
-        err = hipGetLastError();
-        if (err == hipSuccess) err = hipStreamSynchronize(pt->own_stream);
-    }
-    if (err == hipSuccess) err = hipMemcpy(out, dout, sizeof(float) * out_w * n, hipMemcpyDeviceToHost);
-    (void)hipFree(din);
-    if (dout) (void)hipFree(dout);
-    HIP_TRY(err);
+    ScratchBuf<float> din, dout;
+    HIP_TRY(upload(din, in, (size_t)in_w * n));
+    HIP_TRY(dout.alloc((size_t)out_w * n));
+    launch(din.get(), dout.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(pt->own_stream));
+    HIP_TRY(hipMemcpy(out, dout.get(), sizeof(float) * out_w * n, hipMemcpyDeviceToHost));
     return PUPIL_OK;
 }
 }  // namespace
@@ -2803,7 +2605,7 @@ int pupil_debug_read_env_tables(pupil_pt *pt, uint32_t *width, uint32_t *height,
 
 int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint32_t n, const float *uv, float *out) {
     if (!pt || !uv || !out) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (material >= pt->num_mats || slot >= 4u) return fail(PUPIL_ERR_INVALID, "no such material texture");
+    if (material >= pt->materials.count() || slot >= 4u) return fail(PUPIL_ERR_INVALID, "no such material texture");
     if (n == 0) return PUPIL_OK;
     return debug_probe(pt, n, uv, 2, out, 3, [&](const float *din, float *dout) {
         launch_debug_tex(pt->sc, material, slot, din, dout, n, pt->own_stream);
@@ -2812,12 +2614,12 @@ int pupil_debug_tex_sample(pupil_pt *pt, uint32_t material, uint32_t slot, uint3
 
 int pupil_debug_read_material(pupil_pt *pt, uint32_t material, uint32_t *type, float out[3]) {
     if (!pt || !type || !out) return fail(PUPIL_ERR_INVALID, "null argument");
-    if (material >= pt->num_mats) return fail(PUPIL_ERR_INVALID, "material index out of range");
+    if (material >= pt->materials.count()) return fail(PUPIL_ERR_INVALID, "material index out of range");
     HIP_TRY(hipSetDevice(pt->device));
     HIP_TRY(order_after_renders(pt));
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
     DevMaterial d;
-    HIP_TRY(hipMemcpy(&d, pt->d_mats + material, sizeof(d), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&d, pt->materials.device() + material, sizeof(d), hipMemcpyDeviceToHost));
     *type = d.type;
     out[0] = d.eta;
     out[1] = d.int_fdr;
@@ -2928,18 +2730,13 @@ int pupil_debug_partition(int device, uint32_t n, uint32_t capacity, const uint8
 int pupil_debug_math(int device, uint32_t n, const float *x, const float *y2, float *out) {
     if (!x || !y2 || !out) return fail(PUPIL_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(device));
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&dx, sizeof(float) * (n ? n : 1)));
-    HIP_TRY(hipMalloc((void **)&dy, sizeof(float) * (n ? n : 1)));
-    HIP_TRY(hipMalloc((void **)&dout, sizeof(float) * 6 * (n ? n : 1)));
-    HIP_TRY(hipMemcpy(dx, x, sizeof(float) * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dy, y2, sizeof(float) * n, hipMemcpyHostToDevice));
-    launch_debug_math(dx, dy, dout, n, nullptr);
+    ScratchBuf<float> dx, dy, dout;
+    HIP_TRY(upload(dx, x, n));
+    HIP_TRY(upload(dy, y2, n));
+    HIP_TRY(dout.alloc(6 * (size_t)n));
+    launch_debug_math(dx.get(), dy.get(), dout.get(), n, nullptr);
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, dout, sizeof(float) * 6 * n, hipMemcpyDeviceToHost));
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    (void)hipFree(dout);
+    HIP_TRY(hipMemcpy(out, dout.get(), sizeof(float) * 6 * n, hipMemcpyDeviceToHost));
     return PUPIL_OK;
 }
 

@@ -275,7 +275,7 @@ private:
         if (t.type == PUPIL_TEX_BITMAP) {
             texels.emplace_back();
             if (const auto s = put(texels.back(), t.rgba, 4 * (size_t)t.width * t.height))
-                return Dev::failed(s, "pt->upload(&texels, reinterpret_cast<const float4 *>(t.rgba), (size_t)t.width * t.height)");
+                return Dev::failed(s, "upload(texels, t.rgba, 4 * t.width * t.height)");
             d.radiance.data = reinterpret_cast<const float4 *>(texels.back().get());
         }
         for (int k = 0; k < 3; k++) {
@@ -324,7 +324,7 @@ private:
             d.map_h = (uint32_t)h;
             texels.emplace_back();
             if (const auto s = put(texels.back(), tables.data(), tables.size()))
-                return Dev::failed(s, "pt->upload(&block, tables.data(), tables.size())");
+                return Dev::failed(s, "upload(block, tables.data(), tables.size())");
             const float *block = texels.back().get();
             d.col_cdf = block;
             d.row_cdf = block + (row_cdf - col_cdf);

@@ -4,6 +4,7 @@
 //   Alloc::alloc(void **p, size_t bytes) -> status (0 = success)      Alloc::free(void *p)
 #pragma once
 #include <cstddef>
+#include <utility>
 
 namespace pupil {
 
@@ -46,6 +47,34 @@ public:
 
 private:
     T *p_ = nullptr;
+};
+
+// The same for one handle (an event, a stream): Destroy::destroy(H) in the destructor.  Reads as
+// the handle it holds; put() is where a create call writes a new one.
+template <typename H, typename Destroy>
+class ScopedHandle {
+public:
+    ScopedHandle() = default;
+    explicit ScopedHandle(H h) : h_(h) {}
+    ScopedHandle(ScopedHandle &&o) noexcept : h_(o.release()) {}
+    ScopedHandle &operator=(ScopedHandle &&o) noexcept {
+        if (this != &o) *put() = o.release();
+        return *this;
+    }
+    ~ScopedHandle() { reset(); }
+
+    operator H() const { return h_; }
+    H *put() {
+        reset();
+        return &h_;
+    }
+    H release() { return std::exchange(h_, H{}); }
+    void reset() {
+        if (h_) Destroy::destroy(release());
+    }
+
+private:
+    H h_{};
 };
 
 }  // namespace pupil

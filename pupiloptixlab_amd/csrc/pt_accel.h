@@ -8,6 +8,7 @@
 #include "../../include/pupil_pt.h"
 #include "accel_two_level.h"
 #include "host/emitter_tables.h"
+#include "host/material_tables.h"
 #include "host/scene_tables.h"
 
 namespace pupil {
@@ -42,7 +43,8 @@ inline int drained(hipStream_t stream, int rc) {
                                         std::string(#expr) + ": " + hipGetErrorString(_e)));              \
     } while (0)
 
-// the device of the engine's tables (host/scene_tables.h, host/emitter_tables.h) and of a call's scratch
+// the device of the engine's tables (host/scene_tables.h, host/emitter_tables.h, host/material_tables.h),
+// of its shapes and of every scratch
 struct HipDevice {
     using Stream = hipStream_t;
     static hipError_t alloc(void **p, size_t bytes) {
@@ -51,6 +53,8 @@ struct HipDevice {
         return e;
     }
     static void free(void *p) { (void)hipFree(p); }
+    static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+    static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
     static int fill(const TableGeneration<HipDevice> &g, hipStream_t stream) {
         HIP_TRY(hipMemcpyAsync(g.inst_first.get(), g.first.data(), sizeof(uint32_t) * g.first.size(), hipMemcpyHostToDevice,
                                stream));
@@ -78,15 +82,17 @@ struct HipDevice {
 };
 using EngineTables = SceneTables<HipDevice>;
 using EngineEmitters = EmitterTables<HipDevice>;
+using EngineMaterials = MaterialTables<HipDevice>;
 
-// a shape's engine-owned device arrays (those the instances point at)
+// a shape and its device arrays (those the instances point at), a value: moving one over another
+// frees the old arrays
 struct ShapeDev {
     uint32_t kind = PUPIL_SHAPE_MESH, num_vertices = 0, num_faces = 0;
-    float *pos = nullptr, *nrm = nullptr, *tex = nullptr;
-    uint32_t *idx = nullptr;
+    ScopedBuffer<float, HipDevice> pos, nrm, tex;
+    ScopedBuffer<uint32_t, HipDevice> idx;
     // pupil_pt_snapshot_shape_vertices: the vertices from before an update (allocated on the
     // first snapshot and kept), and whether the flow pass uses them
-    float *prev = nullptr;
+    ScopedBuffer<float, HipDevice> prev;
     bool prev_valid = false;
 };
 
@@ -110,7 +116,7 @@ struct SceneAccel {
     struct Tables {
         hipStream_t stream;  // the engine's own
         EngineTables *tables;
-        const DevMaterial *d_mats;
+        const EngineMaterials *materials;
         DeviceScene *sc;
         pupil_pt_counters *totals;
     };

@@ -74,19 +74,19 @@ int SceneAccel::build(const Tables &tables, const pupil_scene_desc *scene, const
             if (sh.kind != PUPIL_SHAPE_MESH || !uses[k]) continue;
             ts.num_faces = sh.num_faces;
             ts.num_vertices = sh.num_vertices;
-            ts.positions = shapes[k].pos;
-            ts.normals = shapes[k].nrm;
-            ts.texcoords = shapes[k].tex;
-            ts.indices = shapes[k].idx;
+            ts.positions = shapes[k].pos.get();
+            ts.normals = shapes[k].nrm.get();
+            ts.texcoords = shapes[k].tex.get();
+            ts.indices = shapes[k].idx.get();
             float vmax = 0.f;
             for (size_t v = 0; v < 3 * (size_t)sh.num_vertices; v++) vmax = std::max(vmax, std::fabs(sh.positions[v]));
             ts.vmax = vmax;
         }
-        const int rc = build_two_level(tl_shapes, inst_shape, g().mirror, g().insts.get(), t.d_mats, leaf_size, t.stream, tl);
+        const int rc = build_two_level(tl_shapes, inst_shape, g().mirror, g().insts.get(), t.materials->device(), leaf_size, t.stream, tl);
         if (rc != 0) return builder_error(rc, true, "two-level acceleration build failed");
         ms = tl.build_ms;
     } else {
-        const BvhBuildInput bin{g().num_prims, g().prim_inst.get(), g().insts.get(), t.d_mats};
+        const BvhBuildInput bin{g().num_prims, g().prim_inst.get(), g().insts.get(), t.materials->device()};
         const int rc = build_bvh_bounded(bin, bvh, leaf_size, t.stream, &ms, 0);
         if (rc != 0) return builder_error(rc, false, "LBVH build failed");
     }
@@ -164,7 +164,7 @@ int SceneAccel::flag_instances(const std::vector<uint32_t> *changed, uint32_t no
 // place, or a rebuild with the masks applied to the new tree before it replaces the old one
 // (refit = false, PUPIL_FLAT_UPDATE=rebuild, a tree without a level order).
 int SceneAccel::update_flat(const std::vector<uint32_t> &changed, bool refit, bool attrs, bool flagged) {
-    const BvhBuildInput bin{g().num_prims, g().prim_inst.get(), g().insts.get(), t.d_mats};
+    const BvhBuildInput bin{g().num_prims, g().prim_inst.get(), g().insts.get(), t.materials->device()};
     if (refit && !is_rebuild(std::getenv("PUPIL_FLAT_UPDATE"))) {
         if (!flagged)
             if (const int rc = flag_instances(&changed, bvh.num_nodes4)) return rc;
@@ -296,7 +296,7 @@ int SceneAccel::update_shape(uint32_t shape, const std::vector<uint32_t> &change
     ts.vmax = vmax;
     std::vector<DevInstance> insts = g().mirror;  // build_two_level refills the two-level fields
     TwoLevelAccel ntl{};
-    int rc = build_two_level(tl_shapes, inst_shape, insts, g().insts.get(), t.d_mats, leaf_size, t.stream, ntl);
+    int rc = build_two_level(tl_shapes, inst_shape, insts, g().insts.get(), t.materials->device(), leaf_size, t.stream, ntl);
     rc = rc != 0 ? builder_error(rc, true, "two-level acceleration rebuild failed") : node_limit(nodes4_of(ntl));
     if (rc != PUPIL_OK) {  // the old structure stays
         free_two_level(ntl);
@@ -320,10 +320,10 @@ int SceneAccel::replace_shape(uint32_t shape, const ShapeDev &mesh, bool used, G
         old_shape = ts;
         ts.num_faces = mesh.num_faces;
         ts.num_vertices = mesh.num_vertices;
-        ts.positions = mesh.pos;
-        ts.normals = mesh.nrm;
-        ts.texcoords = mesh.tex;
-        ts.indices = mesh.idx;  // vmax: update_shape reduces it from the new array
+        ts.positions = mesh.pos.get();
+        ts.normals = mesh.nrm.get();
+        ts.texcoords = mesh.tex.get();
+        ts.indices = mesh.idx.get();  // vmax: update_shape reduces it from the new array
     }
     // both rebuilds build aside and swap on success: flat over the staged tables, two-level over
     // tl_shapes and a copy of the staged mirror, uploaded to the staged instance table
@@ -379,15 +379,15 @@ int SceneAccel::set_instances(Generation &staged, std::vector<uint32_t> &shape_o
             ts = TwoLevelShape{};
             ts.num_faces = shapes[k].num_faces;
             ts.num_vertices = shapes[k].num_vertices;
-            ts.positions = shapes[k].pos;
-            ts.normals = shapes[k].nrm;
-            ts.texcoords = shapes[k].tex;
-            ts.indices = shapes[k].idx;
+            ts.positions = shapes[k].pos.get();
+            ts.normals = shapes[k].nrm.get();
+            ts.texcoords = shapes[k].tex.get();
+            ts.indices = shapes[k].idx.get();
             if (shape_abs_max(tl, ts, &ts.vmax, t.stream) != 0) return undo(fail(PUPIL_ERR_HIP, "vertex reduction failed"));
         }
         copy = g().mirror;
         for (uint32_t id : hidden) copy[id].hidden = 0u;
-        rc = build_two_level(tl_shapes, inst_shape, copy, g().insts.get(), t.d_mats, leaf_size, t.stream, ntl);
+        rc = build_two_level(tl_shapes, inst_shape, copy, g().insts.get(), t.materials->device(), leaf_size, t.stream, ntl);
     }
     auto drop = [&]() {
         if (last_whole_rebuild) free_two_level(ntl);

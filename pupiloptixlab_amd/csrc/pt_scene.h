@@ -42,6 +42,30 @@ struct DevMaterial {
     DevTexture tex[4];
 };
 
+// GetPixelAverage (optix_material.cpp:15-42) in two halves the host (host/material_tables.h pixel_average) and
+// the device (pt_materials.hip) share: the average of a texture without texels, and of a bitmap
+// from the sequential float sums of its r, g, b (vec3 / float multiplies by the reciprocal)
+PT_HD vec3 texture_const_average(uint32_t type, const float *c0, const float *c1) {
+    if (type == PUPIL_TEX_RGB) return v3(c0[0], c0[1], c0[2]);
+    if (type == PUPIL_TEX_CHECKERBOARD) {
+        const float r = c0[0] + c1[0];
+        const float g = c0[1] + c1[1];
+        const float b = c0[2] + c1[2];
+        return v3(r, g, b) * 0.5f;
+    }
+    return v3(0.f);
+}
+PT_HD vec3 bitmap_average(vec3 sum, uint32_t width, uint32_t height) {
+    return sum / (1.f * (float)height * (float)width);
+}
+// plastic / rough_plastic (optix_material.cpp:106-116) from the averages of its diffuse and
+// specular reflectance
+PT_HD float specular_sampling_weight(vec3 diffuse_average, vec3 specular_average) {
+    const float diffuse_luminance = luminance(diffuse_average);
+    const float specular_luminance = luminance(specular_average);
+    return specular_luminance / (specular_luminance + diffuse_luminance);
+}
+
 // optix::Emitter (render/emitter.h:13-24)
 struct DevEmitter {
     uint32_t type;

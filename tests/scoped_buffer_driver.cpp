@@ -32,6 +32,24 @@ struct CountingAlloc {
 template <typename T>
 using Buf = pupil::ScopedBuffer<T, CountingAlloc>;
 
+static std::set<int *> open_handles;
+static int created = 0, destroyed = 0;
+static int *make_handle() {
+    created++;
+    return *open_handles.insert(new int(created)).first;
+}
+struct CountingDestroy {
+    static void destroy(int *h) {
+        if (!open_handles.erase(h)) {
+            std::printf("FAIL destroy of a handle that is not open\n");
+            std::exit(1);
+        }
+        delete h;
+        destroyed++;
+    }
+};
+using Handle = pupil::ScopedHandle<int *, CountingDestroy>;
+
 #define CHECK(c)                                           \
     do {                                                   \
         if (!(c)) {                                        \
@@ -98,6 +116,28 @@ int main() {
         fail_at = -1;
     }
     CHECK(live.empty() && allocs == frees);
+    {  // the handle holder (an event, a stream): destroyed once on every path
+        Handle a, c;
+        CHECK(!a && open_handles.empty());
+        *a.put() = make_handle();
+        *c.put() = make_handle();
+        int *ha = a;
+        Handle b(std::move(a));  // move construction
+        CHECK(!a && b == ha && open_handles.size() == 2);
+        c = std::move(b);  // move assignment over a held one destroys it
+        CHECK(!b && c == ha && open_handles.size() == 1);
+        c = std::move(c);  // self-move keeps it
+        CHECK(c == ha && open_handles.size() == 1);
+        *c.put() = make_handle();  // put over a held one destroys it first
+        CHECK(open_handles.size() == 1 && !open_handles.count(ha));
+        int *kept = c.release();  // release: the caller's to destroy
+        CHECK(!c && open_handles.count(kept));
+        c.reset();
+        CountingDestroy::destroy(kept);
+        Handle d(make_handle());  // destroyed with its scope
+        CHECK(open_handles.size() == 1);
+    }
+    CHECK(open_handles.empty() && created == destroyed && created == 4);
     std::printf("ok %d allocations\n", allocs);
     return 0;
 }

@@ -374,3 +374,54 @@ def test_abi_exposes_the_entry_points():
     n, ms = C.c_uint64(7), C.c_double(1.0)
     assert lib.pupil_pt_replace_info(None, C.byref(n), C.byref(ms)) == abi.ERR_INVALID
     assert lib.pupil_pt_replace_shape_mesh(None, 0, None, 0, None) == abi.ERR_INVALID
+
+
+# ------------------------------------------------------------------ 8. repeated replacements
+@pytest.mark.gpu
+def test_repeated_replacement_holds_no_memory(tmp_path):
+    """20 alternating 12- and 48-triangle replacements of the Cornell box's short box, a vertex
+    snapshot taken before every second one: the free device memory stays within one granule (upper
+    bound: what the engine's creation cost) of its value after the second replacement, and the
+    image after the last equals a fresh engine's bit for bit"""
+    import torch
+
+    import owner_cases
+
+    from pupiloptixlab_amd.pt_pass import PTPass
+
+    w, box, _, _ = owner_cases.cornell(tmp_path)
+    coarse, fine = owner_cases.box_meshes(w, box)
+    free = lambda: torch.cuda.mem_get_info(0)[0]  # noqa: E731
+
+    def image(p):
+        p.mark_dirty()
+        p.render(SPP)
+        torch.cuda.synchronize()
+        return {k: _bits(p.buffers.get(k)) for k in AOVS}
+
+    pt = PTPass(device=0)
+    f_before = free()
+    pt.set_scene(w)
+    granule = abs(f_before - free())
+    try:
+        image(pt)  # the ring and every lazily allocated buffer exist from here on
+        f2 = None
+        for k in range(20):
+            if k % 2 == 1:
+                abi.check(pt._lib.pupil_pt_snapshot_shape_vertices(pt._pt, box))
+            owner_cases.replace(pt, w, box, fine if k % 2 == 0 else coarse)
+            if k == 1:
+                f2 = free()
+        f20 = free()
+        print(f"creation cost {granule} B; free after the second replacement {f2}, after the 20th {f20}")
+        assert granule > 0 and abs(f20 - f2) <= granule
+        assert pt.replace_info()["replacements"] == 20 and w.desc().shapes[box].num_faces == 12
+        got = image(pt)
+    finally:
+        pt.close_engine()
+    fresh = PTPass(device=0)
+    fresh.set_scene(w)
+    try:
+        _same(got, image(fresh), "after 20 replacements")
+    finally:
+        fresh.close_engine()

@@ -1,6 +1,7 @@
 """csrc/host/scoped_buffer.h, the BVH builder's device-scratch holder, without a GPU: the stand-alone
 driver scoped_buffer_driver.cpp swaps hipMalloc / hipFree for a counting allocator and walks the
-destructor, move, release and failed-sequence paths.  It is built with
+destructor, move, release and failed-sequence paths, and the same paths of the handle holder beside
+it (events, the stream) with a counting destroy.  It is built with
 -fsanitize=address,undefined, so a leak, a double free or a use after free fails the run."""
 import os
 import subprocess
