@@ -536,10 +536,21 @@ int pupil_pt_clear_vertex_snapshots(pupil_pt *pt);
  * PUPIL_ERR_INVALID: NULL pt / mesh / positions / indices, shape out of range or a
  * PUPIL_SHAPE_SPHERE, mesh->kind not PUPIL_SHAPE_MESH, num_faces or num_vertices 0, unknown flags,
  * an index >= num_vertices.  PUPIL_ERR_UNSUPPORTED: an instance of the shape is emissive
- * (emitter_offset >= 0) -- its emitter count would change and with it every later instance's
- * emitter_offset; emissive replacement is not supported -- or a limit of the builders (2^31
+ * (emitter_offset >= 0) while the device-side emitter table is off -- its emitter count would
+ * change and with it every later instance's emitter_offset, which only the device-side mode
+ * follows (below) -- or a limit of the builders (2^31
  * primitives, 2^27 flattened primitives, the 28-bit leaf links, the node limit, the traversal
  * stacks).  PUPIL_ERR_OOM: the new arrays could not be allocated.
+ * Emissive shapes, with the device-side emitter table on (pupil_pt_enable_device_emitters): the
+ * shape's emissive instances get one emitter per new face.  The engine assigns every emissive
+ * instance its emitter_offset anew in instance order, as pupil_world_get_desc does, keeps each
+ * one's radiance (bitmap texels are moved into the new table, not uploaded again) and select
+ * weight, and rebuilds the area-emitter table at its new size on the device (pt_emitters.hip: the
+ * records with type, radiance and texcoords, then geometry, select probabilities, CDF and guide)
+ * inside the same transaction: the table is staged aside and adopted in the swap.  Afterwards the
+ * table equals, bit for bit, that of an engine created on the world's description of the new
+ * scene (pupil_world_replace_mesh with PUPIL_WORLD_MESH_EMISSIVE_OK keeps the world in step).
+ * Delta lights keep their records under their new indices; the env emitter carries over.
  * pupil_pt_replace_info: successful calls since create and the host clock around the last one;
  * either out pointer may be NULL.  No ABI bump: detect the symbols. */
 int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape *mesh, uint32_t flags,
@@ -578,7 +589,8 @@ int pupil_pt_replace_info(pupil_pt *pt, uint64_t *replacements, double *last_ms)
  * (pupil_pt_enable_device_emitters) -- its transform bit for bit.  Their indices may change; with
  * the device-side table on it is refreshed before the call returns.  Anything else (an emissive
  * instance added, removed, reordered, rebound, or moved with the device-side table off) returns
- * PUPIL_ERR_UNSUPPORTED before anything changes.
+ * PUPIL_ERR_UNSUPPORTED before anything changes; pupil_pt_set_instances_emitters (below) lifts
+ * this with the device-side table on.
  * PUPIL_ERR_INVALID: NULL pt or instances, n == 0 (as pupil_pt_create on a scene without
  * instances), a shape, material or emitter range out of range, unknown flags, the device pointer
  * missing or present without the flag, or not 4-byte aligned.  PUPIL_ERR_UNSUPPORTED: the
@@ -593,6 +605,44 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
                            void *hip_stream);
 int pupil_pt_set_instances_info(pupil_pt *pt, uint64_t *calls, uint32_t *last_blas_builds,
                                 uint32_t *last_whole_rebuild, double *last_ms);
+/* pupil_pt_set_instances with a free emissive set, for the device-side emitter table
+ * (pupil_pt_enable_device_emitters; PUPIL_ERR_UNSUPPORTED while it is off).  The instance list is
+ * scene->instances[0..num_instances); `material` names the engine's slots, as above.  Emissive
+ * instances may be added, removed, reordered, rebound to another shape or radiance, and moved:
+ * the area-emitter table is rebuilt at its new size on the device, inside the same transaction
+ * (staged aside, adopted with the instance table and the structure), and afterwards equals, bit
+ * for bit, that of an engine created on the scene.  Of scene->area_emitters the call reads, per
+ * emissive instance, the radiance of the first record of its range (descriptor, host texels of a
+ * bitmap -- uploaded once per instance -- and the select weight, as
+ * pupil_pt_enable_device_emitters reads it) and the delta-light records behind the ranges, whole;
+ * geometry, area, weight and select_probability of the triangle and sphere emitters are not read:
+ * they are derived on the device, with PUPIL_INSTANCES_DEVICE from transforms that never reach
+ * the host.  Everything else is pupil_pt_set_instances: flags, masks, ordering, accel_refits + 1,
+ * no BLAS build in two-level world mode while the set of shown shapes stays, and, with an
+ * unchanged emissive set, the same engine state.
+ * PUPIL_ERR_INVALID, before anything changes: a NULL pt, scene or instance list; emitter ranges
+ * that do not follow each other in instance order or are not the shape's face count (a sphere: 1)
+ * of the matching type; num_area_emitters that is not the ranges plus the delta lights; a table
+ * out of the order areas, point / spot, directional; an env emitter present in one of scene and
+ * engine only (the env changes through pupil_pt_update_emitters); everything
+ * pupil_pt_set_instances rejects.
+ * pupil_pt_emitter_resize_info: tables rebuilt at a new size since create (by this call and by
+ * pupil_pt_replace_shape_mesh on an emissive shape; successes only), the triangle and sphere
+ * emitters of the last one and the host clock around its call; any out pointer may be NULL.  A
+ * resize that leaves a triangle or sphere emitter in the table also counts as a rebuild in
+ * pupil_pt_device_emitters_info, as the refresh of pupil_pt_set_instances does.
+ * Out of scope: the mode-off path (both calls refuse as before), a single BLAS rebuilt alone, area
+ * radiance texels from device memory.  No ABI bump: detect the symbols. */
+int pupil_pt_set_instances_emitters(pupil_pt *pt, const pupil_scene_desc *scene,
+                                    const uint32_t *visibility_mask /* num_instances, or NULL */,
+                                    const void *to_world_device /* num_instances x 12 floats, or NULL */,
+                                    uint32_t flags, void *hip_stream);
+int pupil_pt_emitter_resize_info(pupil_pt *pt, uint64_t *resizes, uint32_t *last_true_areas, double *last_ms);
+/* The shape of the emitter table the engine holds now: its entries (delta lights included), the
+ * triangle and sphere emitters in front, and whether there is an env emitter -- what a caller
+ * compares a scene description with before pupil_pt_set_instances_emitters.  Any out pointer may
+ * be NULL.  No ABI bump: detect the symbol. */
+int pupil_pt_emitter_table_info(pupil_pt *pt, uint32_t *emitters, uint32_t *true_areas, uint32_t *has_env);
 /* Shadow rays of the last render with PUPIL_STATS_COUNTERS (zeros otherwise), beside
  * pupil_pt_counters: those that found an occluder and the node visits they took; the others took
  * node_visits - extend_node_visits minus these.  overlap_order: 1 when the engine's any-hit rays
@@ -1126,6 +1176,15 @@ int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *p
 int pupil_world_set_mesh(pupil_world *w, uint32_t shape, uint32_t num_vertices, uint32_t num_faces,
                          const float *positions, const float *normals, const float *texcoords,
                          const uint32_t *indices);
+/* pupil_world_set_mesh with flags: 0 = the same call; PUPIL_WORLD_MESH_EMISSIVE_OK = a shape that
+ * emissive instances show is accepted, and pupil_world_get_desc afterwards describes the re-meshed
+ * emitter: one area emitter per new face, later instances' emitter_offset shifted, the select
+ * probabilities of the new table (the world-side half of pupil_pt_replace_shape_mesh with the
+ * device-side emitter table on).  PUPIL_ERR_INVALID for unknown flags. */
+#define PUPIL_WORLD_MESH_EMISSIVE_OK 1u
+int pupil_world_replace_mesh(pupil_world *w, uint32_t shape, uint32_t num_vertices, uint32_t num_faces,
+                             const float *positions, const float *normals, const float *texcoords,
+                             const uint32_t *indices, uint32_t flags);
 /* A material replaced on the host side: `material` is an index into pupil_scene_desc.materials
  * (the world flattens one material per instance, in instance order, so it is the material of
  * desc instance `material`); the next pupil_world_get_desc carries *m there, and

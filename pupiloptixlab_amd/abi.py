@@ -164,6 +164,10 @@ SIGNATURES = {
     "pupil_pt_set_instances": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Instance), u32p, C.c_void_p, C.c_uint32,
                                          C.c_void_p]),
     "pupil_pt_set_instances_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u32p, u32p, C.POINTER(C.c_double)]),
+    "pupil_pt_set_instances_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), u32p, C.c_void_p, C.c_uint32,
+                                                  C.c_void_p]),
+    "pupil_pt_emitter_table_info": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
+    "pupil_pt_emitter_resize_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u32p, C.POINTER(C.c_double)]),
     "pupil_pt_shadow_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), u32p]),
     "pupil_debug_read_prim_tables": (C.c_int, [C.c_void_p, u32p, u32p, u32p, u32p, u32p, u32p]),
     "pupil_pt_update_emitters": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
@@ -233,6 +237,8 @@ SIGNATURES = {
     "pupil_world_get_instance_visibility": (C.c_int, [C.c_void_p, C.c_uint32, u32p]),
     "pupil_world_set_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p]),
     "pupil_world_set_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p, f32p, u32p]),
+    "pupil_world_replace_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, f32p, f32p, u32p,
+                                           C.c_uint32]),
     "pupil_world_set_material": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Material)]),
     "pupil_world_get_desc": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pupil_world_destroy": (None, [C.c_void_p]),
@@ -248,6 +254,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libpupil_pt.so")
 
 
 INSTANCES_DEVICE = 1  # pupil_pt_set_instances: transforms from device memory
+WORLD_MESH_EMISSIVE_OK = 1  # pupil_world_replace_mesh: a shape emissive instances show is accepted
 
 
 class PupilError(RuntimeError):

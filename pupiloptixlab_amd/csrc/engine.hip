@@ -177,6 +177,11 @@ struct pupil_pt {
     EngineEmitters emitters;
     uint64_t env_updates = 0, emit_refreshes = 0;
     double env_ms = 0.0, emit_ms = 0.0;
+    // emitter tables rebuilt at a new size (device-side mode: an emissive mesh replaced, the emissive
+    // set changed): the successful calls, the last one's triangle and sphere emitters and host clock
+    uint64_t emit_resizes = 0;
+    uint32_t emit_resize_areas = 0;
+    double emit_resize_ms = 0.0;
     // vertex updates (pupil_pt_update_shape_vertices): each shape's engine-owned device arrays
     // and the event that orders a caller's stream before a device-to-device copy (vertices, texels)
     std::vector<ShapeDev> shapes;
@@ -858,11 +863,12 @@ int rebuild_emitters(pupil_pt *pt) {
     job.weight = book.weight.get();
     job.select = book.select.get();
     job.sum = book.sum.get();
-    launch_emitter_rebuild(job, pt->own_stream);
+    const uint32_t launches = launch_emitter_rebuild(job, pt->own_stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(pt->own_stream));
-    // four stages and the guide's (pt_emitters.hip), one synchronisation: pupil_pt_instances_device_info
-    pt->accel.counts.launches += job.count ? (job.guide ? 5u : 4u) : 0u;
+    // the stages launch_emitter_rebuild ran (four and the guide's; over delta lights alone, two and the
+    // guide's; an empty table, none), one synchronisation: pupil_pt_instances_device_info
+    pt->accel.counts.launches += launches;
     pt->accel.counts.syncs++;
     pt->emit_refreshes++;
     pt->emit_ms = ms_since(t0);
@@ -878,6 +884,85 @@ int keep_device_emitters(pupil_pt *pt, const pupil_scene_desc *scene) {
         pt->emitters.book().enabled = false;
         g_last_error = "device-side emitter table switched off: " + g_last_error;
     }
+    return PUPIL_OK;
+}
+
+// A staged, resized emitter table (EmitterTables::stage_resize) filled on the stream from `insts`,
+// the staged instance table it belongs to, which the stream has filled: k_emit_fill writes the
+// records and emit_inst, the five stages everything derived.  Returns once the stream has passed
+// them, so a failure shows before anything is swapped.  Nothing the engine reads is touched.
+int fill_resized_emitters(pupil_pt *pt, const EngineEmitters::Resize &r, const DevInstance *insts, hipStream_t s) {
+    const EngineEmitters::Generation &g = r.gen;
+    const uint32_t total = (uint32_t)g.types.size();
+    launch_emitter_fill({g.areas.get(), r.book.emit_inst.get(), g.num_true_areas, r.sources.get(), r.num_sources, insts}, s);
+    EmitterJob job{};
+    job.areas = g.areas.get();
+    job.cdf = g.cdf.get();
+    job.guide = g.guide.get();
+    job.guide_bits = g.guide_bits;
+    job.count = g.num_true_areas;
+    job.total = total;
+    job.emitter_num = total + (g.env.get() ? 1u : 0u);
+    job.instances = insts;
+    job.emit_inst = r.book.emit_inst.get();
+    job.inst_weight = r.book.inst_weight.get();
+    job.weight = r.book.weight.get();
+    job.select = r.book.select.get();
+    job.sum = r.book.sum.get();
+    const uint32_t launches = launch_emitter_rebuild(job, s) + (g.num_true_areas ? 1u : 0u);
+    HIP_TRY_DRAINED(s, hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    pt->accel.counts.launches += launches;
+    pt->accel.counts.syncs++;
+    return PUPIL_OK;
+}
+
+// the swap of a resize and its counters; t0: the start of the call that resized
+void adopt_resized_emitters(pupil_pt *pt, EngineEmitters::Resize &&r, std::chrono::steady_clock::time_point t0) {
+    pt->emit_resize_areas = r.gen.num_true_areas;
+    pt->emitters.adopt_resize(std::move(r), pt->sc);
+    pt->emit_resizes++;
+    pt->emit_resize_ms = ms_since(t0);
+    // a resize is a rebuild too: pupil_pt_device_emitters_info counts it where pupil_pt_set_instances
+    // counts its refresh, i.e. when the table holds a triangle or sphere emitter
+    if (pt->emit_resize_areas) {
+        pt->emit_refreshes++;
+        pt->emit_ms = pt->emit_resize_ms;
+    }
+}
+
+// The emissive instances of the table pupil_pt_set_instances_emitters is given, from the scene that
+// describes it: validates the emitter ranges and the table's shape against the engine (header) and
+// fills one source per emissive instance; counts: the new instances' primitive counts.
+int scene_emitter_sources(const pupil_pt *pt, const pupil_scene_desc *scene, const std::vector<uint32_t> &counts,
+                          std::vector<EmitterSource> &sources, uint32_t &true_areas) {
+    if (scene->num_area_emitters && !scene->area_emitters) return fail(PUPIL_ERR_INVALID, "missing emitter array");
+    std::vector<uint32_t> types;
+    if (const int rc = emitter_table_shape(scene, types, true_areas)) return rc;
+    const bool env = scene->env && scene->env->type != PUPIL_EMITTER_NONE;
+    if (env != (pt->emitters.cur().env.get() != nullptr))
+        return fail(PUPIL_ERR_INVALID, "the scene's env emitter is not the engine's: change it with pupil_pt_update_emitters");
+    uint32_t next = 0;  // emitter ranges follow each other in instance order (World::Build)
+    for (uint32_t i = 0; i < scene->num_instances; i++) {
+        const pupil_instance &in = scene->instances[i];
+        if (in.emitter_offset < 0) continue;
+        const bool sphere = pt->shapes[in.shape].kind == PUPIL_SHAPE_SPHERE;
+        if ((uint32_t)in.emitter_offset != next || counts[i] > true_areas - next)
+            return fail(PUPIL_ERR_INVALID, "an emissive instance's emitter range is not its face count, in instance order");
+        for (uint32_t k = 0; k < counts[i]; k++)
+            if (types[next + k] != (sphere ? PUPIL_EMITTER_SPHERE : PUPIL_EMITTER_TRI_AREA))
+                return fail(PUPIL_ERR_INVALID, "an emissive instance's emitter range is not its face count, in instance order");
+        EmitterSource s;
+        s.inst = i, s.offset = next, s.range = counts[i];
+        s.type = sphere ? PUPIL_EMITTER_SPHERE : PUPIL_EMITTER_TRI_AREA;
+        s.radiance = scene->area_emitters[next].radiance;
+        if (s.radiance.type == PUPIL_TEX_BITMAP && (!s.radiance.rgba || !s.radiance.width || !s.radiance.height))
+            return fail(PUPIL_ERR_INVALID, "bitmap texture without texels");
+        s.weight = Pupil::world::GetWeight(s.radiance);
+        sources.push_back(s);
+        next += counts[i];
+    }
+    if (next != true_areas) return fail(PUPIL_ERR_INVALID, "the emitter ranges and the delta lights do not make up the emitter table");
     return PUPIL_OK;
 }
 
@@ -1107,14 +1192,39 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     const size_t nv = mesh->num_vertices, nf = mesh->num_faces;
     const uint32_t ni = (uint32_t)pt->h_insts().size();
     std::vector<uint32_t> counts(ni);
-    bool used = false;
+    bool used = false, emissive = false;
     for (uint32_t i = 0; i < ni; i++) {
         const DevInstance &d = pt->h_insts()[i];
         const bool shows = d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape;
-        if (shows && d.emitter_offset >= 0)
-            return fail(PUPIL_ERR_UNSUPPORTED, "an instance of the shape is emissive: its emitter range would change");
+        if (shows && d.emitter_offset >= 0) {
+            if (!pt->emitters.book().enabled)
+                return fail(PUPIL_ERR_UNSUPPORTED, "an instance of the shape is emissive: its emitter range would change");
+            emissive = true;
+        }
         used = used || shows;
         counts[i] = shows ? mesh->num_faces : d.kind == PUPIL_SHAPE_MESH ? pt->shapes[pt->accel.inst_shape[i]].num_faces : 1u;
+    }
+    // device-side emitter table: the emitter ranges anew in instance order, as World::Build assigns
+    // them; each emissive instance keeps its radiance (the record at its old offset) and select weight
+    std::vector<EmitterSource> sources;
+    std::vector<int32_t> offsets;
+    if (emissive) {
+        offsets.assign(ni, -1);
+        uint64_t next = 0;
+        for (uint32_t i = 0; i < ni; i++) {
+            const DevInstance &d = pt->h_insts()[i];
+            if (d.emitter_offset < 0) continue;
+            EmitterSource src;
+            src.inst = i, src.offset = (uint32_t)next, src.range = counts[i];
+            src.type = d.kind == PUPIL_SHAPE_SPHERE ? PUPIL_EMITTER_SPHERE : PUPIL_EMITTER_TRI_AREA;
+            src.weight = pt->emitters.book().h_inst_weight[i];
+            src.kept = d.emitter_offset;
+            sources.push_back(src);
+            offsets[i] = (int32_t)next;
+            next += counts[i];
+        }
+        if (next + (pt->sc.num_areas - pt->emitters.cur().num_true_areas) > 0x7FFFFFFFull)
+            return fail(PUPIL_ERR_UNSUPPORTED, "more than 2^31 emitters");
     }
     if (!device)
         for (size_t i = 0; i < 3 * nf; i++)
@@ -1153,14 +1263,26 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     if (mesh->texcoords) HIP_TRY_DRAINED(s, hipMemcpyAsync(tex, mesh->texcoords, sizeof(float) * 2 * nv, kind, s));
     // the second instance table: the engine's own, then the prim offsets and the shape's pointers
     HIP_TRY_DRAINED(s, hipMemcpyAsync(gen.insts.get(), pt->d_insts(), sizeof(DevInstance) * ni, hipMemcpyDeviceToDevice, s));
-    const ReplaceMeshJob job{gen.insts.get(), ni, gen.inst_first.get(), sd.pos.get(), pos, nrm, tex, idx};
+    ScratchBuf<int32_t> d_offsets;  // emissive: every instance's new emitter_offset
+    if (emissive) {
+        if (d_offsets.alloc(ni)) return drained(s, fail(PUPIL_ERR_OOM, "mesh replacement: allocation failed"));
+        HIP_TRY_DRAINED(s, hipMemcpyAsync(d_offsets.get(), offsets.data(), sizeof(int32_t) * ni, hipMemcpyHostToDevice, s));
+    }
+    const ReplaceMeshJob job{gen.insts.get(), ni, gen.inst_first.get(), sd.pos.get(), pos, nrm, tex, idx, d_offsets.get()};
     launch_patch_instances(job, s);
     HIP_TRY_DRAINED(s, hipGetLastError());
     pt->accel.counts.launches += 2;  // with the tables' fill
+    // the emitter table at its new size, aside too, from the patched instance table and the new arrays
+    EngineEmitters::Resize resized;
+    if (emissive) {
+        if (const int rc = pt->emitters.stage_resize(sources, ni, nullptr, 0, true, resized)) return drained(s, rc);
+        if (const int rc = fill_resized_emitters(pt, resized, gen.insts.get(), s)) return rc;
+    }
     gen.mirror = pt->h_insts();  // the same patch on the host mirror
     for (uint32_t i = 0; i < ni; i++) {
         DevInstance &d = gen.mirror[i];
         d.prim_offset = gen.first[i];
+        if (emissive) d.emitter_offset = offsets[i];
         if (d.kind == PUPIL_SHAPE_MESH && pt->accel.inst_shape[i] == shape) {
             d.positions = pos;
             d.normals = nrm;
@@ -1177,6 +1299,7 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
     drop_stale(pt, true, false, &sd);
     sd = std::move(fresh);  // the old arrays and the old snapshot go with the replaced value
     pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
+    if (emissive) adopt_resized_emitters(pt, std::move(resized), t0);
     pt->accel.refits++;
     if (const int rc = derive_cull_set(pt)) return rc;  // the rebuild moved the records
     pt->replacements++;
@@ -1193,8 +1316,10 @@ int pupil_pt_replace_shape_mesh(pupil_pt *pt, uint32_t shape, const pupil_shape 
 // structure over the staged tables and swaps it in, or leaves the old one.  Swap: the staged
 // generation is adopted, and whatever was sized by the old instance or primitive count is dropped
 // and re-allocated by its next user (drop_stale).
-int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
-                           const void *to_world_device, uint32_t flags, void *hip_stream) {
+// scene: null, or (pupil_pt_set_instances_emitters) the description the instances are taken from,
+// whose emissive set is free: the emitter table is rebuilt at its new size inside the transaction
+static int set_instances_impl(pupil_pt *pt, uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
+                              const void *to_world_device, uint32_t flags, void *hip_stream, const pupil_scene_desc *scene) {
     if (!pt || !instances) return fail(PUPIL_ERR_INVALID, "null argument");
     if (flags & ~PUPIL_INSTANCES_DEVICE) return fail(PUPIL_ERR_INVALID, "unknown flags");
     const bool device = (flags & PUPIL_INSTANCES_DEVICE) != 0u;
@@ -1224,31 +1349,42 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         b.hidden = visibility_mask && (visibility_mask[i] & 0xFFu) == 0u ? 1u : 0u;
         b.bin = material_bin(pt->materials.mirror()[src.material].type);
     }
-    // the emitter table stays: the emissive instances are the old ones, in their order (so every
-    // emitter range is one create checked against the table)
+    // the new entry: the emitter table follows the scene's emissive set
+    std::vector<EmitterSource> sources;
+    uint32_t true_areas = 0;
+    if (scene) {
+        if (!pt->emitters.book().enabled)
+            return fail(PUPIL_ERR_UNSUPPORTED,
+                        "the emitter table is resized on the device: switch the mode on with pupil_pt_enable_device_emitters");
+        if (const int rc = scene_emitter_sources(pt, scene, counts, sources, true_areas)) return rc;
+    }
+    // the old entry: the emitter table stays: the emissive instances are the old ones, in their order
+    // (so every emitter range is one create checked against the table)
     std::vector<uint32_t> old_em, new_em;
-    for (uint32_t i = 0; i < old_n; i++)
-        if (pt->h_insts()[i].emitter_offset >= 0) old_em.push_back(i);
-    for (uint32_t i = 0; i < n; i++)
-        if (instances[i].emitter_offset >= 0) new_em.push_back(i);
-    if (old_em.size() != new_em.size())
-        return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances added or removed: the emitter table would change");
     bool emitters_moved = false;
-    for (size_t k = 0; k < old_em.size(); k++) {
-        const DevInstance &o = pt->h_insts()[old_em[k]];
-        const pupil_instance &c = instances[new_em[k]];
-        // the same material: its slot, or another slot of the same content
-        const std::vector<DevMaterial> &mats = pt->materials.mirror();
-        const bool same_material =
-            o.material == c.material || std::memcmp(&mats[o.material], &mats[c.material], sizeof(DevMaterial)) == 0;
-        if (pt->accel.inst_shape[old_em[k]] != c.shape || !same_material || o.flip_normals != c.flip_normals ||
-            o.flip_tex_coords != c.flip_tex_coords || o.emitter_offset != c.emitter_offset)
-            return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances reordered or rebound: the emitter table would change");
-        if (!device && (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) != 0 ||
-                        std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) != 0)) {
-            if (!pt->emitters.book().enabled)
-                return fail(PUPIL_ERR_UNSUPPORTED, "an emissive instance moved: the emitter table needs the device-side mode");
-            emitters_moved = true;
+    if (!scene) {
+        for (uint32_t i = 0; i < old_n; i++)
+            if (pt->h_insts()[i].emitter_offset >= 0) old_em.push_back(i);
+        for (uint32_t i = 0; i < n; i++)
+            if (instances[i].emitter_offset >= 0) new_em.push_back(i);
+        if (old_em.size() != new_em.size())
+            return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances added or removed: the emitter table would change");
+        for (size_t k = 0; k < old_em.size(); k++) {
+            const DevInstance &o = pt->h_insts()[old_em[k]];
+            const pupil_instance &c = instances[new_em[k]];
+            // the same material: its slot, or another slot of the same content
+            const std::vector<DevMaterial> &mats = pt->materials.mirror();
+            const bool same_material =
+                o.material == c.material || std::memcmp(&mats[o.material], &mats[c.material], sizeof(DevMaterial)) == 0;
+            if (pt->accel.inst_shape[old_em[k]] != c.shape || !same_material || o.flip_normals != c.flip_normals ||
+                o.flip_tex_coords != c.flip_tex_coords || o.emitter_offset != c.emitter_offset)
+                return fail(PUPIL_ERR_UNSUPPORTED, "emissive instances reordered or rebound: the emitter table would change");
+            if (!device && (std::memcmp(o.to_world, c.to_world, sizeof(o.to_world)) != 0 ||
+                            std::memcmp(o.to_object, c.to_object, sizeof(o.to_object)) != 0)) {
+                if (!pt->emitters.book().enabled)
+                    return fail(PUPIL_ERR_UNSUPPORTED, "an emissive instance moved: the emitter table needs the device-side mode");
+                emitters_moved = true;
+            }
         }
     }
     std::vector<InstShape> shape_tab(pt->shapes.size());  // the per-shape table
@@ -1271,7 +1407,12 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
         return drained(s, fail(PUPIL_ERR_OOM, "instance table: allocation failed"));
     // the device-side emitter bookkeeping: the emitters' instances under their new indices
     EngineEmitters::Bookkeeping book;
-    const bool remap = pt->emitters.book().enabled;
+    EngineEmitters::Resize resized;  // the new entry: the table at its new size, with its own bookkeeping
+    const bool remap = pt->emitters.book().enabled && !scene;
+    if (scene)
+        if (const int rc = pt->emitters.stage_resize(sources, n, scene->area_emitters + true_areas,
+                                                     scene->num_area_emitters - true_areas, false, resized))
+            return drained(s, rc);
     if (remap)
         if (const int rc = pt->emitters.book().restage(old_em, new_em, n, book, "instance table: allocation failed"))
             return drained(s, rc);
@@ -1299,6 +1440,8 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     launch_fill_instances(job, s);
     HIP_TRY_DRAINED(s, hipGetLastError());
     pt->accel.counts.launches += 2;  // with the tables' fill
+    if (scene)  // emissive instances' transforms are read from the new table, on the device
+        if (const int rc = fill_resized_emitters(pt, resized, gen.insts.get(), s)) return rc;
     if (device) {  // one contiguous readback
         HIP_TRY_DRAINED(s, hipMemcpyAsync(gen.mirror.data(), gen.insts.get(), sizeof(DevInstance) * n, hipMemcpyDeviceToHost, s));
         HIP_TRY_DRAINED(s, hipStreamSynchronize(s));
@@ -1326,7 +1469,8 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     // ---- swap: the structure is published and the stream idle
     pt->pipe.invalidate();  // frames in flight were traced against the old table
     drop_stale(pt, true, true);
-    pt->emitters.book() = std::move(book);  // switched off: dropped, the next enable sizes its bookkeeping anew
+    if (scene) adopt_resized_emitters(pt, std::move(resized), t0);
+    else pt->emitters.book() = std::move(book);  // switched off: dropped, the next enable sizes its bookkeeping anew
     pt->tables.adopt(std::move(gen), pt->sc, pt->totals);
     pt->accel.refits++;
     derive_bins(pt);
@@ -1337,6 +1481,38 @@ int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *insta
     pt->inst_set_blas_builds = pt->accel.last_blas_builds;
     pt->inst_set_whole = pt->accel.last_whole_rebuild;
     pt->inst_set_ms = pt->totals.build_ms = ms_since(t0);
+    return PUPIL_OK;
+}
+
+int pupil_pt_set_instances(pupil_pt *pt, uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
+                           const void *to_world_device, uint32_t flags, void *hip_stream) {
+    return set_instances_impl(pt, n, instances, visibility_mask, to_world_device, flags, hip_stream, nullptr);
+}
+
+// pupil_pt_set_instances with the instance list of `scene` and a free emissive set (header: the
+// contract): the phases above, with the emitter table staged at its new size beside the instance
+// table (EmitterTables::stage_resize), filled on the device from the staged instance table
+// (pt_emitters.hip) and adopted in the same swap.
+int pupil_pt_set_instances_emitters(pupil_pt *pt, const pupil_scene_desc *scene, const uint32_t *visibility_mask,
+                                    const void *to_world_device, uint32_t flags, void *hip_stream) {
+    if (!pt || !scene || !scene->instances) return fail(PUPIL_ERR_INVALID, "null argument");
+    return set_instances_impl(pt, scene->num_instances, scene->instances, visibility_mask, to_world_device, flags, hip_stream,
+                              scene);
+}
+
+int pupil_pt_emitter_table_info(pupil_pt *pt, uint32_t *emitters, uint32_t *true_areas, uint32_t *has_env) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (emitters) *emitters = pt->sc.num_areas;
+    if (true_areas) *true_areas = pt->emitters.cur().num_true_areas;
+    if (has_env) *has_env = pt->emitters.cur().env.get() ? 1u : 0u;
+    return PUPIL_OK;
+}
+
+int pupil_pt_emitter_resize_info(pupil_pt *pt, uint64_t *resizes, uint32_t *last_true_areas, double *last_ms) {
+    if (!pt) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (resizes) *resizes = pt->emit_resizes;
+    if (last_true_areas) *last_true_areas = pt->emit_resize_areas;
+    if (last_ms) *last_ms = pt->emit_resize_ms;
     return PUPIL_OK;
 }
 

@@ -123,12 +123,138 @@ struct EmitterBookkeeping {
     }
 };
 
+// One emissive instance of a table that is being resized (EmitterTables::stage_resize), in instance
+// order: its index in the new instance table, its emitter range, the select weight of its radiance,
+// and the radiance itself -- that of record `kept` of the current table (its texels are moved, not
+// uploaded again), or, kept < 0, `radiance`, whose bitmap is uploaded once
+struct EmitterSource {
+    uint32_t inst = 0, offset = 0, range = 0;
+    uint32_t type = PUPIL_EMITTER_TRI_AREA;  // or PUPIL_EMITTER_SPHERE (range 1)
+    float weight = 0.f;
+    int64_t kept = -1;
+    pupil_texture radiance{};
+};
+
+// A resized table, staged: the generation and the bookkeeping sized for the new count, built aside.
+// The records of gen.areas are filled on the device (pt_emitters.hip: k_emit_fill from `sources`,
+// then the five stages) but for the delta lights' at [num_true_areas, total), which are staged here.
+template <typename Dev>
+struct EmitterResize {
+    EmitterGeneration<Dev> gen;
+    EmitterBookkeeping<Dev> book;
+    ScopedBuffer<DevEmitSource, Dev> sources;  // the fill kernel's input; goes with the call
+    uint32_t num_sources = 0;
+    std::vector<const float *> moved;  // texels of the current generation that gen's records point at: they move at adoption
+};
+
 template <typename Dev>
 class EmitterTables {
 public:
     using Generation = EmitterGeneration<Dev>;
     using Bookkeeping = EmitterBookkeeping<Dev>;
+    using Resize = EmitterResize<Dev>;
     using Texels = std::vector<ScopedBuffer<float, Dev>>;
+
+    // The "aside" step of a resize (device-side mode).  sources: the emissive instances of the new
+    // table of n_instances, their ranges following each other from 0.  deltas: the delta lights
+    // behind them, or, keep_deltas: those of the current generation, copied on the device.  The env record
+    // carries over (its own copy, with the select probability of the new count); its texels and
+    // tables move at adoption.  Also needs Dev::download(dst, src, bytes) and Dev::copy(dst, src,
+    // bytes), synchronous like Dev::upload.  After a failure `out` frees what it took; nothing the
+    // engine reads has changed, and no texel has left the current generation.
+    int stage_resize(const std::vector<EmitterSource> &sources, uint32_t n_instances, const pupil_emitter *deltas,
+                     uint32_t num_deltas, bool keep_deltas, Resize &out) {
+        Generation &g = out.gen;
+        std::vector<DevEmitSource> dev(sources.size());
+        std::vector<float> inst_weight(n_instances, 0.f);
+        std::vector<uint32_t> emit_inst;
+        g.types.clear();
+        for (size_t k = 0; k < sources.size(); k++) {
+            const EmitterSource &s = sources[k];
+            if (s.offset != g.types.size() || s.range == 0 || s.inst >= n_instances)
+                return fail(PUPIL_ERR_INVALID, "emitter ranges do not follow each other in instance order");
+            DevEmitter rec{};
+            if (s.kept >= 0) {
+                if ((uint64_t)s.kept >= cur_.num_true_areas) return fail(PUPIL_ERR_INVALID, "kept emitter out of range");
+                if (const auto e = Dev::download(&rec, cur_.areas.get() + s.kept, sizeof(rec)))
+                    return Dev::failed(e, "download(record, areas + kept, sizeof(DevEmitter))");
+                if (rec.radiance.data && !keep(reinterpret_cast<const float *>(rec.radiance.data), out.moved))
+                    return fail(PUPIL_ERR_INVALID, "kept emitter's texels are not the current generation's");
+            } else {
+                if (const int rc = texture_desc(s.radiance, rec.radiance)) return rc;
+                if (s.radiance.type == PUPIL_TEX_BITMAP) {
+                    g.texels.emplace_back();
+                    if (const auto e = put(g.texels.back(), s.radiance.rgba, 4 * (size_t)s.radiance.width * s.radiance.height))
+                        return Dev::failed(e, "upload(texels, t.rgba, 4 * t.width * t.height)");
+                    rec.radiance.data = reinterpret_cast<const float4 *>(g.texels.back().get());
+                }
+            }
+            dev[k] = DevEmitSource{s.inst, s.offset, rec.radiance};
+            inst_weight[s.inst] = s.weight;
+            g.types.insert(g.types.end(), s.range, s.type);
+            emit_inst.insert(emit_inst.end(), s.range, s.inst);
+        }
+        g.num_true_areas = (uint32_t)g.types.size();
+        const uint32_t old_deltas = (uint32_t)cur_.types.size() - cur_.num_true_areas;
+        if (!keep_deltas) {
+            for (uint32_t k = 0; k < num_deltas; k++) g.types.push_back(deltas[k].type);
+        } else {
+            num_deltas = old_deltas;
+            g.types.insert(g.types.end(), cur_.types.begin() + cur_.num_true_areas, cur_.types.end());
+        }
+        const uint32_t total = (uint32_t)g.types.size();
+        g.guide_bits = 0;
+        while ((1u << g.guide_bits) < total && g.guide_bits < 20) g.guide_bits++;
+        const char *sel = std::getenv("PUPIL_EMITTER_SELECT");
+        const bool guide = total > 1 && !(sel && std::strcmp(sel, "binary") == 0);  // as emitter_tables()
+        if (g.areas.alloc(total) || g.cdf.alloc(total) || (guide && g.guide.alloc((1u << g.guide_bits) + 1u)))
+            return fail(PUPIL_ERR_OOM, "emitter table allocation failed");
+        if (out.sources.alloc(dev.size())) return fail(PUPIL_ERR_OOM, "emitter table allocation failed");
+        out.num_sources = (uint32_t)dev.size();
+        if (!dev.empty())
+            if (const auto e = Dev::upload(out.sources.get(), dev.data(), sizeof(DevEmitSource) * dev.size()))
+                return Dev::failed(e, "upload(sources, dev.data(), sizeof(DevEmitSource) * dev.size())");
+        if (!keep_deltas && num_deltas) {
+            std::vector<DevEmitter> recs(num_deltas);
+            for (uint32_t k = 0; k < num_deltas; k++)
+                if (const int rc = convert_emitter(deltas[k], recs[k], g.texels)) return rc;
+            if (const auto e = Dev::upload(g.areas.get() + g.num_true_areas, recs.data(), sizeof(DevEmitter) * num_deltas))
+                return Dev::failed(e, "upload(areas + num_true_areas, recs.data(), sizeof(DevEmitter) * num_deltas)");
+        } else if (num_deltas) {
+            if (const auto e = Dev::copy(g.areas.get() + g.num_true_areas, cur_.areas.get() + cur_.num_true_areas,
+                                         sizeof(DevEmitter) * num_deltas))
+                return Dev::failed(e, "copy(areas + num_true_areas, cur.areas + cur.num_true_areas, sizeof(DevEmitter) * num_deltas)");
+        }
+        if (cur_.env.get()) {  // its own record: ComputeProbability's env weight / emitter_num under the new count
+            g.h_env = cur_.h_env;
+            g.env_src = cur_.env_src;
+            g.env_src_valid = cur_.env_src_valid, g.env_stale = cur_.env_stale;
+            g.h_env.select_probability = g.env_src.select_probability = 1.f / (float)((size_t)total + 1);
+            if (g.env.alloc(1)) return fail(PUPIL_ERR_OOM, "env allocation failed");
+            // from the device: the table kernels write the env map's normalization there, not into h_env
+            if (const auto e = Dev::copy(g.env.get(), cur_.env.get(), sizeof(DevEmitter)))
+                return Dev::failed(e, "copy(env, cur.env, sizeof(DevEmitter))");
+            if (const auto e = Dev::upload(&g.env.get()->select_probability, &g.h_env.select_probability, sizeof(float)))
+                return Dev::failed(e, "upload(&env->select_probability, &h_env.select_probability, sizeof(float))");
+            keep(reinterpret_cast<const float *>(g.h_env.radiance.data), out.moved);
+            keep(g.h_env.col_cdf, out.moved);
+        }
+        g.texels.reserve(g.texels.size() + out.moved.size());  // adoption allocates nothing
+        out.book.enabled = true;
+        if (const int rc = Bookkeeping::stage({}, std::move(inst_weight), total, out.book)) return rc;
+        out.book.h_emit_inst = std::move(emit_inst);  // the device's copy is k_emit_fill's
+        return PUPIL_OK;
+    }
+
+    // the swap of a resize: the texels the staged records share with the current generation move
+    // over, everything else of the current generation and the old bookkeeping is freed
+    void adopt_resize(Resize &&staged, DeviceScene &sc) {
+        for (const float *p : staged.moved)
+            for (auto &t : cur_.texels)
+                if (t.get() == p) staged.gen.texels.push_back(std::move(t));
+        adopt(std::move(staged.gen), sc);
+        book_ = std::move(staged.book);
+    }
 
     // The "aside" step: the tables derived once, into the staging vectors, and uploaded into `out`, which
     // frees what it took after a failure; nothing the engine reads changes.  With `fits`: tables that keep
@@ -257,6 +383,16 @@ public:
     }
 
 private:
+    // p is an allocation of the current generation's texels: listed once in `moved`
+    bool keep(const float *p, std::vector<const float *> &moved) const {
+        for (const auto &t : cur_.texels)
+            if (p && t.get() == p) {
+                if (std::find(moved.begin(), moved.end(), p) == moved.end()) moved.push_back(p);
+                return true;
+            }
+        return false;
+    }
+
     template <typename T>
     static auto put(ScopedBuffer<T, Dev> &b, const T *src, size_t count) {
         auto e = b.alloc(count);

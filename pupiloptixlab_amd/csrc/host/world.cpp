@@ -1180,14 +1180,22 @@ int pupil_world_set_mesh_vertices(pupil_world *w, uint32_t shape, const float *p
 
 int pupil_world_set_mesh(pupil_world *w, uint32_t shape, uint32_t nv, uint32_t nf, const float *positions,
                          const float *normals, const float *texcoords, const uint32_t *indices) {
+    return pupil_world_replace_mesh(w, shape, nv, nf, positions, normals, texcoords, indices, 0u);
+}
+
+int pupil_world_replace_mesh(pupil_world *w, uint32_t shape, uint32_t nv, uint32_t nf, const float *positions,
+                             const float *normals, const float *texcoords, const uint32_t *indices, uint32_t flags) {
     if (!w || !positions || !indices || nv == 0 || nf == 0) return Pupil::werr(PUPIL_ERR_INVALID, "bad mesh");
+    if (flags & ~PUPIL_WORLD_MESH_EMISSIVE_OK) return Pupil::werr(PUPIL_ERR_INVALID, "unknown flags");
     if (shape >= w->w.scene.shapes.size()) return Pupil::werr(PUPIL_ERR_INVALID, "shape out of range");
     Pupil::resource::Shape &s = w->w.scene.shapes[shape];
     if (s.kind != PUPIL_SHAPE_MESH || !s.mesh) return Pupil::werr(PUPIL_ERR_INVALID, "shape is not a mesh");
     // an emissive instance's emitter range is its face count, and every later instance's
-    // emitter_offset follows it: pupil_pt_replace_shape_mesh refuses the same shapes
+    // emitter_offset follows it: pupil_pt_replace_shape_mesh refuses the same shapes unless its
+    // device-side emitter table is on.  With the flag: World::Build derives the emitters from the
+    // mesh on every pupil_world_get_desc, so the new ranges and probabilities follow by themselves
     for (const auto &ins : w->w.scene.instances)
-        if (ins.shape == (int)shape && ins.is_emitter)
+        if (!(flags & PUPIL_WORLD_MESH_EMISSIVE_OK) && ins.shape == (int)shape && ins.is_emitter)
             return Pupil::werr(PUPIL_ERR_UNSUPPORTED, "an emissive instance shows the shape");
     for (size_t i = 0; i < 3 * (size_t)nf; i++)
         if (indices[i] >= nv) return Pupil::werr(PUPIL_ERR_INVALID, "mesh index out of range");

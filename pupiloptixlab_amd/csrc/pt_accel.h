@@ -63,6 +63,11 @@ struct HipDevice {
         return PUPIL_OK;
     }
     static hipError_t upload(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+    static hipError_t download(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost); }
+    static hipError_t copy(void *dst, const void *src, size_t bytes) {  // device to device, complete on return
+        const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice);
+        return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
+    }
     static int failed(hipError_t e, const char *what) {  // what HIP_TRY(what) returns
         if (e == hipSuccess) return PUPIL_OK;
         return fail(e == hipErrorOutOfMemory ? PUPIL_ERR_OOM : PUPIL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));

@@ -19,6 +19,13 @@
 // geometry to rebuild: stages 1 and 2 run over the area emitters alone (`count` in stage 3 is the
 // true area count), stage 3 rewrites a delta light's select_probability = 1 / emitter_num and
 // stages 4 and 5 span the whole table, as the host's CDF does.
+//
+// A table of a new size (an emissive mesh replaced, emissive instances added or removed) has no
+// records yet: k_emit_fill runs in front of the five stages and writes, per triangle or sphere
+// emitter, the whole DevEmitter that EmitterTables::convert_emitter writes from the world's
+// AddAreaEmitter record -- zero but for type, the instance's radiance and a triangle's texcoords
+// -- and emit_inst[e], the emitter's instance: a search over the emissive instances' offsets, so
+// no per-face array comes from the host.
 #include <hip/hip_runtime.h>
 
 #include "pt_kernels.h"
@@ -90,6 +97,38 @@ __global__ __launch_bounds__(kEmitBlock) void k_emit_geometry(EmitterJob job) {
     }
     d.area = area;
     job.weight[e] = select_weight * area;
+}
+
+// In front of stage 1 for a table of a new size.  sources[k].offset increases with k from 0, so the
+// emitter's instance is the last source whose offset is <= e.
+__global__ __launch_bounds__(kEmitBlock) void k_emit_fill(EmitterFillJob job) {
+    const uint32_t e = blockIdx.x * kEmitBlock + threadIdx.x;
+    if (e >= job.count) return;
+    uint32_t lo = 0, hi = job.num_sources;  // the first source whose offset is > e, in [1, num_sources]
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (job.sources[mid].offset <= e) lo = mid + 1u;
+        else hi = mid;
+    }
+    const DevEmitSource &src = job.sources[lo - 1u];
+    const DevInstance &in = job.instances[src.inst];
+    DevEmitter d;
+    __builtin_memset(&d, 0, sizeof(d));
+    d.radiance = src.radiance;
+    if (in.kind == PUPIL_SHAPE_SPHERE) {
+        d.type = PUPIL_EMITTER_SPHERE;
+    } else {
+        d.type = PUPIL_EMITTER_TRI_AREA;
+        if (in.texcoords) {  // AddAreaEmitter: the shape's own, no flip
+            const uint32_t f = e - src.offset;
+            for (int v = 0; v < 3; v++) {
+                const uint32_t idx = in.indices[3 * (size_t)f + v];
+                d.tex[v] = v2(in.texcoords[2 * (size_t)idx], in.texcoords[2 * (size_t)idx + 1]);
+            }
+        }
+    }
+    job.areas[e] = d;
+    job.emit_inst[e] = src.inst;
 }
 
 // stages 2 and 4: out = the running sum of in[0..n) in index order, starting from 0.f.  SCAN:
@@ -174,18 +213,29 @@ __global__ __launch_bounds__(kEmitBlock) void k_cull_scan(const float4 *recs, ui
 
 }  // namespace
 
-void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s) {
-    if (job.count == 0) return;
-    const dim3 grid((job.count + kEmitBlock - 1) / kEmitBlock);
+uint32_t launch_emitter_rebuild(const EmitterJob &job, hipStream_t s) {
+    if (job.total == 0) return 0u;
+    uint32_t launches = 2u;
     const dim3 grid_all((job.total + kEmitBlock - 1) / kEmitBlock);
-    hipLaunchKernelGGL(k_emit_geometry, grid, dim3(kEmitBlock), 0, s, job);
-    hipLaunchKernelGGL(k_emit_chain<false>, dim3(1), dim3(64), 0, s, (const float *)job.weight, job.count, job.sum);
+    if (job.count) {  // none: delta lights alone, whose select probability needs no weight
+        const dim3 grid((job.count + kEmitBlock - 1) / kEmitBlock);
+        hipLaunchKernelGGL(k_emit_geometry, grid, dim3(kEmitBlock), 0, s, job);
+        hipLaunchKernelGGL(k_emit_chain<false>, dim3(1), dim3(64), 0, s, (const float *)job.weight, job.count, job.sum);
+        launches += 2u;
+    }
     hipLaunchKernelGGL(k_emit_select, grid_all, dim3(kEmitBlock), 0, s, job);
     hipLaunchKernelGGL(k_emit_chain<true>, dim3(1), dim3(64), 0, s, (const float *)job.select, job.total, job.cdf);
     if (job.guide) {
         const uint32_t entries = (1u << job.guide_bits) + 1u;
         hipLaunchKernelGGL(k_emit_guide, dim3((entries + kEmitBlock - 1) / kEmitBlock), dim3(kEmitBlock), 0, s, job);
+        launches++;
     }
+    return launches;
+}
+
+void launch_emitter_fill(const EmitterFillJob &job, hipStream_t s) {
+    if (job.count == 0 || job.num_sources == 0) return;
+    hipLaunchKernelGGL(k_emit_fill, dim3((job.count + kEmitBlock - 1) / kEmitBlock), dim3(kEmitBlock), 0, s, job);
 }
 
 void launch_cull_scan(const float4 *recs, uint32_t slots, const DevInstance *instances, uint32_t num_instances,

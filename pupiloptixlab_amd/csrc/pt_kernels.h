@@ -312,7 +312,22 @@ struct EmitterJob {
     float *weight, *select;     // scratch, one float per table entry
     float *sum;                 // scratch, one float
 };
-void launch_emitter_rebuild(const EmitterJob &job, hipStream_t s);
+// returns the kernels it launched.  No triangle or sphere emitter (count == 0) but delta lights:
+// the stages from the select probabilities on still run, over the delta lights alone
+uint32_t launch_emitter_rebuild(const EmitterJob &job, hipStream_t s);
+// A table of a new size (pt_emitters.hip k_emit_fill): every byte of areas[0, count) that the
+// rebuild above does not write -- zero but for type, radiance and a triangle's tex -- and
+// emit_inst[0, count), from the emissive instances' emitter ranges.  sources: num_sources entries
+// in instance order, their offsets increasing from 0; count = the end of the last range
+struct EmitterFillJob {
+    DevEmitter *areas;
+    uint32_t *emit_inst;
+    uint32_t count;
+    const DevEmitSource *sources;
+    uint32_t num_sources;
+    const DevInstance *instances;
+};
+void launch_emitter_fill(const EmitterFillJob &job, hipStream_t s);
 // the cull set's scan (pt_emitters.hip): out[0] (zero at launch) counts the record slots of `recs`
 // whose instance is emissive, out[1 + k] holds the k-th found for k < cap, in no order
 void launch_cull_scan(const float4 *recs, uint32_t slots, const DevInstance *instances, uint32_t num_instances,
@@ -366,7 +381,8 @@ void launch_move_instances(const MoveInstancesJob &job, hipStream_t s);
 // launch_prim_tables: prim_inst (num_prims entries) and inst_guide (guide_entries entries) from
 // inst_first (num_instances + 1 entries), all device arrays (host/prim_tables.h: the geometry).
 // launch_patch_instances: instances[i].prim_offset = inst_first[i], and the mesh instances whose
-// positions are old_positions get the four new array pointers.
+// positions are old_positions get the four new array pointers; with emitter_offsets (one per
+// instance, or null) instances[i].emitter_offset = emitter_offsets[i] as well.
 void launch_index_max(const uint32_t *idx, size_t n, uint32_t *out, hipStream_t s);
 void launch_prim_tables(const uint32_t *inst_first, uint32_t num_instances, uint32_t num_prims, uint32_t shift,
                         uint32_t guide_entries, uint32_t *prim_inst, uint32_t *inst_guide, hipStream_t s);
@@ -377,6 +393,7 @@ struct ReplaceMeshJob {
     const float *old_positions;
     const float *positions, *normals, *texcoords;
     const uint32_t *indices;
+    const int32_t *emitter_offsets;
 };
 void launch_patch_instances(const ReplaceMeshJob &job, hipStream_t s);
 // A new instance table (pt_instance_set.hip, pupil_pt_set_instances): out[i] for i < n from

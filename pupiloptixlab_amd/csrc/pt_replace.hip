@@ -52,6 +52,7 @@ __global__ __launch_bounds__(kBlock) void k_patch_instances(ReplaceMeshJob j) {
     if (i >= j.num_instances) return;
     DevInstance &d = j.instances[i];
     d.prim_offset = j.inst_first[i];
+    if (j.emitter_offsets) d.emitter_offset = j.emitter_offsets[i];
     // a shape's instances all point at the shape's one position array, and no other shape's do
     if (d.kind == PUPIL_SHAPE_MESH && d.positions == j.old_positions) {
         d.positions = j.positions;

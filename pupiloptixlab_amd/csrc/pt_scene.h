@@ -92,6 +92,19 @@ struct DevEmitter {
     const float *row_weight;  // map_h (+ the zero)
 };
 
+// no padding: its members sum to its size, so a record assigned as a struct is written whole
+// (pt_emitters.hip k_emit_fill: every byte zero but for the fields it names)
+static_assert(sizeof(DevTexture) == 80 && sizeof(DevEmitter) == 16 + 80 + 4 * (9 + 9 + 6 + 3 + 3 + 4 + 9 + 9) + 3 * 8,
+              "DevEmitter has padding");
+
+// One emissive instance of a resized emitter table (pt_emitters.hip k_emit_fill), in instance
+// order: its index in the instance table, its first emitter and the radiance all of its emitters
+// share (`data`: texels the table's generation owns)
+struct DevEmitSource {
+    uint32_t inst, offset;
+    DevTexture radiance;
+};
+
 struct DevInstance {
     float to_world[12];
     float to_object[12];

@@ -84,14 +84,18 @@ public:
     // shape is dropped (the world's vertices it would hand over have the old count until
     // pupil_world_set_mesh brings the world in step) and so is the shape's vertex snapshot.
     // Restarts accumulation at the next OnRun.  False: no scene, or the engine refused -- a sphere,
-    // a shape an emissive instance shows, an index out of range -- and then nothing has changed.
+    // a shape an emissive instance shows while SetDeviceEmitters is off (on: the engine rebuilds its
+    // emitter table at the new size; World::SetMesh(..., true) keeps the world in step), an index
+    // out of range -- and then nothing has changed.
     bool ReplaceShapeMesh(uint32_t shape, const pupil_shape &mesh, bool device = false, void *stream = nullptr) noexcept;
     // The instance table as a whole (pupil_pt_set_instances), applied now, under the same threading
     // rule: the engine's instances become instances[0..n) -- added, removed, or bound to another
     // shape or material slot of the scene the pass was set on -- with visibility_mask (n masks, or
     // null: all visible).  Transforms from the structs, or, with to_world_device, from n x 12
     // device floats read after the work enqueued so far on `stream` (a hipStream_t) and inverted
-    // on the device.  Emissive instances must stay the old ones, in order.  The pass's own
+    // on the device.  With SetDeviceEmitters(true) the call goes to pupil_pt_set_instances_emitters
+    // with the world's Desc() (its radiances and delta lights): emissive instances may be added,
+    // removed, reordered, rebound or moved.  Otherwise they must stay the old ones, in order.  The pass's own
     // per-instance state follows: recorded instance updates are dropped, and the flow of the next
     // ComputeMotionVectors covers the camera only.  Restarts accumulation at the next OnRun.
     // False: no scene, or the engine refused (pupil_last_error()) -- then nothing has changed.

@@ -80,6 +80,13 @@ public:
     // area emitters of emissive instances) and fires EWorldEvent::RenderInstanceUpdate with
     // InstanceUpdate::shape set; the pass refits once at the top of its next OnRun.
     bool SetMeshVertices(uint32_t shape, const float *positions, const float *normals = nullptr) noexcept;
+    // New topology for mesh shape `shape` (pupil_world_set_mesh / _replace_mesh): the arrays are
+    // copied, *mesh is a PUPIL_SHAPE_MESH as PTPass::ReplaceShapeMesh takes it.  allow_emissive: a
+    // shape emissive instances show is accepted, and Desc() then carries the re-meshed emitter (new
+    // ranges, later offsets shifted, new probabilities), which a pass with SetDeviceEmitters(true)
+    // follows in place.  Refreshes Desc() and fires no event: PTPass::ReplaceShapeMesh hands the
+    // mesh to the engine.
+    bool SetMesh(uint32_t shape, const pupil_shape &mesh, bool allow_emissive = false) noexcept;
     // Replaces material `material` (index into Desc().materials: one per instance, in instance
     // order) and refreshes Desc().  The reference has no event for a material edit and fires
     // none: PTPass::UpdateMaterials hands the material to the engine.

@@ -394,8 +394,23 @@ bool PTPass::ReplaceShapeMesh(uint32_t shape, const pupil_shape &mesh, bool devi
 bool PTPass::SetInstances(uint32_t n, const pupil_instance *instances, const uint32_t *visibility_mask,
                           const void *to_world_device, void *stream) noexcept {
     if (!m_engine) return false;
-    if (pupil_pt_set_instances(m_engine, n, instances, visibility_mask, to_world_device,
-                               to_world_device ? (uint32_t)PUPIL_INSTANCES_DEVICE : 0u, stream) != PUPIL_OK) {
+    const uint32_t flags = to_world_device ? (uint32_t)PUPIL_INSTANCES_DEVICE : 0u;
+    int rc;
+    uint32_t has_env = 0;
+    std::unique_lock<std::mutex> lock;
+    if (m_world) lock = std::unique_lock<std::mutex>(m_world->Mutex());
+    // the emissive set is free when the world describes the engine's emitter table (the same env
+    // presence); else -- the emitters were set from another description -- the old entry keeps it
+    if (m_device_emitters && m_world && pupil_pt_emitter_table_info(m_engine, nullptr, nullptr, &has_env) == PUPIL_OK &&
+        (has_env != 0u) == (m_world->Desc().env != nullptr && m_world->Desc().env->type != PUPIL_EMITTER_NONE)) {
+        pupil_scene_desc d = m_world->Desc();
+        d.instances = instances;
+        d.num_instances = n;
+        rc = pupil_pt_set_instances_emitters(m_engine, &d, visibility_mask, to_world_device, flags, stream);
+    } else {
+        rc = pupil_pt_set_instances(m_engine, n, instances, visibility_mask, to_world_device, flags, stream);
+    }
+    if (rc != PUPIL_OK) {
         Log("%s: instance table update failed: %s", name.c_str(), pupil_last_error());
         return false;
     }

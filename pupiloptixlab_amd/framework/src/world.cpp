@@ -109,6 +109,21 @@ bool World::SetMeshVertices(uint32_t shape, const float *positions, const float 
     return true;
 }
 
+bool World::SetMesh(uint32_t shape, const pupil_shape &mesh, bool allow_emissive) noexcept {
+    std::scoped_lock lock(m_mutex);
+    if (!m_world || pupil_world_replace_mesh(m_world, shape, mesh.num_vertices, mesh.num_faces, mesh.positions, mesh.normals,
+                                             mesh.texcoords, mesh.indices,
+                                             allow_emissive ? (uint32_t)PUPIL_WORLD_MESH_EMISSIVE_OK : 0u) != PUPIL_OK) {
+        Log("mesh replacement failed: %s", pupil_last_error());
+        return false;
+    }
+    if (pupil_world_get_desc(m_world, &m_desc) != PUPIL_OK) {
+        Log("scene description failed: %s", pupil_last_error());
+        return false;
+    }
+    return true;
+}
+
 bool World::SetMaterial(uint32_t material, const pupil_material &m) noexcept {
     std::scoped_lock lock(m_mutex);
     if (!m_world || pupil_world_set_material(m_world, material, &m) != PUPIL_OK) {

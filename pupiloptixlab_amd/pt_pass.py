@@ -370,8 +370,11 @@ class PTPass(Pass):
         present or not whatever the old mesh had.  Every instance of the shape shows the new mesh
         and the engine equals one created on the updated scene (World.set_mesh keeps the world in
         step).  The whole acceleration structure is rebuilt; the shape's vertex snapshot is
-        dropped; restarts accumulation.  Refused, with the engine untouched: spheres, shapes an
-        emissive instance shows (PUPIL_ERR_UNSUPPORTED), an index >= nv."""
+        dropped; restarts accumulation.  A shape an emissive instance shows needs device_emitters
+        on: the engine then rebuilds its emitter table at the new size (World.set_mesh with
+        allow_emissive=True keeps the world in step).  Refused, with the engine untouched: spheres,
+        shapes an emissive instance shows with device_emitters off (PUPIL_ERR_UNSUPPORTED), an
+        index >= nv."""
         import numpy as np
 
         p = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1))
@@ -470,13 +473,39 @@ class PTPass(Pass):
         """The engine's instance table becomes the world's (pupil_pt_set_instances, host path):
         instances added with World.add_instance, removed with World.remove_instance, or bound to
         another shape or material of the scene the engine was created on, with the world's
-        visibility masks.  Shapes, materials and emitters stay: emissive instances must be the old
-        ones, in order (PUPIL_ERR_UNSUPPORTED otherwise).  Restarts accumulation."""
+        visibility masks.  Shapes and materials stay.  With device_emitters on
+        (pupil_pt_set_instances_emitters) the emissive set is free -- lamps added, removed,
+        reordered, rebound, moved -- and the engine rebuilds its emitter table at the new size;
+        with it off the emitters stay: emissive instances must be the old ones, in order
+        (PUPIL_ERR_UNSUPPORTED otherwise).  Restarts accumulation."""
         if not self._pt:
             raise abi.PupilError(abi.ERR_INVALID, "no scene set")
         n, arr, vis = self._bindings(world)
-        check(self._lib.pupil_pt_set_instances(self._pt, n, arr, vis.ctypes.data_as(abi.u32p), None, 0, None))
+        self._set_instances(world, n, arr, vis, None, 0, None)
         self._after_set_instances(world)
+
+    def _set_instances(self, world, n, arr, vis, to_world, flags, stream):
+        """device_emitters on and the world describes the engine's emitter table (the same env
+        presence: pupil_pt_emitter_table_info): pupil_pt_set_instances_emitters with the world's desc,
+        whose instance array is the _bindings copy -- the emissive set is free.  Otherwise
+        pupil_pt_set_instances, which keeps the table: the mode is off, or the engine's emitters were
+        set from another description than this world's."""
+        src = world.desc()  # its arrays live in the world
+        env = bool(src.env) and src.env.contents.type != abi.EMITTER_NONE
+        if not self.device_emitters or env != self.emitter_table_info()["has_env"]:
+            check(self._lib.pupil_pt_set_instances(self._pt, n, arr, vis.ctypes.data_as(abi.u32p), to_world, flags, stream))
+            return
+        desc = abi.SceneDesc()
+        C.memmove(C.byref(desc), C.byref(src), C.sizeof(abi.SceneDesc))
+        desc.instances = C.cast(arr, C.POINTER(abi.Instance))
+        check(self._lib.pupil_pt_set_instances_emitters(self._pt, C.byref(desc), vis.ctypes.data_as(abi.u32p), to_world,
+                                                        flags, stream))
+
+    def emitter_table_info(self) -> dict:
+        """The engine's emitter table: its entries, the triangle and sphere emitters among them, an env or none."""
+        n, a, e = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        check(self._lib.pupil_pt_emitter_table_info(self._pt, C.byref(n), C.byref(a), C.byref(e)))
+        return {"emitters": n.value, "true_areas": a.value, "has_env": bool(e.value)}
 
     def set_instances_device(self, world, to_world, stream=None):
         """As set_instances, with the transforms from `to_world`, an (n, 12) or (n, 3, 4) float32
@@ -494,9 +523,8 @@ class PTPass(Pass):
         if to_world.numel() != 12 * n:
             raise ValueError(f"set_instances_device needs 12 floats for each of the world's {n} instances")
         s = stream if stream is not None else torch.cuda.current_stream(self.device_index)
-        check(self._lib.pupil_pt_set_instances(self._pt, n, arr, vis.ctypes.data_as(abi.u32p),
-                                               C.c_void_p(to_world.data_ptr()), abi.INSTANCES_DEVICE,
-                                               C.c_void_p(s.cuda_stream)))
+        self._set_instances(world, n, arr, vis, C.c_void_p(to_world.data_ptr()), abi.INSTANCES_DEVICE,
+                            C.c_void_p(s.cuda_stream))
         self._after_set_instances(world)
 
     def set_instances_info(self) -> dict:
@@ -505,6 +533,14 @@ class PTPass(Pass):
         n, b, w, ms = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0.0)
         check(self._lib.pupil_pt_set_instances_info(self._pt, C.byref(n), C.byref(b), C.byref(w), C.byref(ms)))
         return {"calls": n.value, "last_blas_builds": b.value, "last_whole_rebuild": w.value, "last_ms": ms.value}
+
+    def emitter_resize_info(self) -> dict:
+        """Emitter tables rebuilt at a new size since the scene was set (set_instances* and
+        replace_shape* with device_emitters on), the triangle and sphere emitters of the last one
+        and the host time of its call."""
+        n, a, ms = C.c_uint64(0), C.c_uint32(0), C.c_double(0.0)
+        check(self._lib.pupil_pt_emitter_resize_info(self._pt, C.byref(n), C.byref(a), C.byref(ms)))
+        return {"resizes": n.value, "last_true_areas": a.value, "last_ms": ms.value}
 
     def replace_info(self) -> dict:
         """Meshes replaced since the scene was set and the host time of the last call."""

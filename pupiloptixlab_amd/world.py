@@ -269,12 +269,15 @@ class World:
         check(self._lib.pupil_world_set_mesh_vertices(self._h, int(shape), _ptr(p), _ptr(n)))
         self._desc = None
 
-    def set_mesh(self, shape: int, positions, indices, normals=None, texcoords=None):
+    def set_mesh(self, shape: int, positions, indices, normals=None, texcoords=None, allow_emissive: bool = False):
         """Replace mesh shape `shape` (index into desc().shapes) by a mesh of new topology: new
         vertex and face counts, normals and texcoords present or not whatever the old mesh had.
         The shape's instances keep material, transform and flags; the next desc() describes the
         scene a fresh engine is created from, and PTPass.replace_shape hands the mesh to the
-        engine.  Refuses spheres and shapes an emissive instance shows."""
+        engine.  Refuses spheres and, unless allow_emissive, shapes an emissive instance shows.
+        allow_emissive (pupil_world_replace_mesh): the next desc() describes the re-meshed emitter
+        -- one area emitter per new face, later instances' emitter offsets shifted, new select
+        probabilities -- which an engine with device_emitters on follows in place."""
         p = _f32(positions)
         i = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32).reshape(-1))
         n = _f32(normals) if normals is not None else None
@@ -283,8 +286,12 @@ class World:
         if p.size != 3 * nv or i.size != 3 * nf or (n is not None and n.size != 3 * nv) or \
                 (t is not None and t.size != 2 * nv):
             raise ValueError(f"arrays do not describe a mesh of {nv} vertices and {nf} faces")
-        check(self._lib.pupil_world_set_mesh(self._h, int(shape), nv, nf, _ptr(p), _ptr(n), _ptr(t),
-                                             _ptr(i, C.c_uint32)))
+        if allow_emissive:
+            check(self._lib.pupil_world_replace_mesh(self._h, int(shape), nv, nf, _ptr(p), _ptr(n), _ptr(t),
+                                                     _ptr(i, C.c_uint32), abi.WORLD_MESH_EMISSIVE_OK))
+        else:
+            check(self._lib.pupil_world_set_mesh(self._h, int(shape), nv, nf, _ptr(p), _ptr(n), _ptr(t),
+                                                 _ptr(i, C.c_uint32)))
         self._desc = None
 
     def add_const_env(self, radiance):
