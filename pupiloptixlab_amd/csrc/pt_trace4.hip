@@ -39,6 +39,14 @@ __device__ __forceinline__ void enter_instance(const DevInstance &in, const RayP
             slab_error_pad(bo.z, bi.z, bound[2], pad));
 }
 
+// a wave-uniform value the compiler cannot prove uniform, pinned to SGPRs (the builtin returns
+// an int: each half goes through uint32_t so that bit 31 is not sign-extended over the high half)
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // TL = two-level acceleration (DeviceScene::two_level): the TLAS leaves hold one
 // instance each; entering one pushes the pending TLAS link and kReturnLink and
 // switches the box tests to the instance's object-space ray; popping
@@ -131,10 +139,34 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
         }
         return f3(any ? ld_ps(ps.sh_d + p) : ld_ps(ps.ray_d + p));
     };
+    // mixed: lanes whose unoccluded shadow ray has finished and whose path still owes rad += sh_c
+    // (main.cu:124-139).  A wave-uniform ballot mask (SGPRs): the lanes idle until the next refill
+    // anyway and keep their path id in s_aux, so the two path-state loads (both HBM misses the
+    // in-order data return waits behind) are issued once per refill for all of them instead of in
+    // every outer iteration that retires one.  A path has one shadow ray per launch and nothing
+    // else touches its rad record there, so the sum is the same single L + c whenever it is formed.
+    unsigned long long owed = 0;
+    auto settle = [&]() {
+        if (__builtin_amdgcn_inverse_ballot_w64(owed)) {  // this lane's bit of the mask
+            const float4 c = ld_ps(ps.sh_c + p);
+            float4 L = ld_ps(ps.rad + p);
+            L.x = L.x + c.x;
+            L.y = L.y + c.y;
+            L.z = L.z + c.z;
+            st_ps(ps.rad + p, L);
+        }
+        owed = 0;
+    };
     for (;;) {
         // ---- refill idle lanes (one atomic per wave)
         const unsigned long long idle = __ballot(!active);
         const uint32_t n_idle = (uint32_t)__popcll(idle);
+        // settle before the refill reassigns any lane's path id; once the lists are drained no
+        // refill follows, so settle what the last iteration retired.  The condition is wave-uniform
+        // (`drained` too, which the compiler cannot see); read through an SGPR, so that the branch
+        // is uniform and `owed` stays in SGPRs instead of becoming a per-lane value in two VGPRs
+        const bool settle_now = owed != 0ull && (drained || n_idle >= job.refill);
+        if (kMixed && __builtin_amdgcn_readfirstlane(settle_now ? 1u : 0u)) settle();
         if (!drained && n_idle >= job.refill) {
             // chunk `shard`: list positions [lo, lo + len).  Mixed launches cut the
             // extension and the shadow list separately and give each chunk its
@@ -158,7 +190,10 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
             }
             uint32_t base = 0;
             if (lane_id() == 0) base = atomicAdd(job.work + shard * kWorkStride, n_idle);
-            base = __shfl(base, 0);
+            // mixed: lane 0's value through an SGPR (every lane is here).  That frees the VGPR holding
+            // the shuffle's lane address, which the mixed kernels otherwise spill once `owed` is live
+            // (profiles/trace_settle_ab.txt); the other modes keep the code they had
+            base = kMixed ? __builtin_amdgcn_readfirstlane(base) : __shfl(base, 0);
             if (STATS && lane_id() == 0) {
                 dg[4]++;
                 dg[5] += min(n_idle, base < len ? len - base : 0u);
@@ -384,14 +419,7 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
             }
         }
         if (kMixed) {
-            if (done && any && !found) {  // main.cu:124-139 (shadow rays share the origin record, w = tmax)
-                const float4 c = ld_ps(ps.sh_c + p);
-                float4 L = ld_ps(ps.rad + p);
-                L.x = L.x + c.x;
-                L.y = L.y + c.y;
-                L.z = L.z + c.z;
-                st_ps(ps.rad + p, L);
-            }
+            owed = uniform64(owed | __ballot(done && any && !found));  // settled at the next refill (settle())
             if (STATS && done && any && found) {
                 n_found_sh++;
                 nv_found_sh += nv_ray;
@@ -406,6 +434,7 @@ __device__ __forceinline__ void trace4_body(const DeviceScene &sc, const PathSta
         if (STATS) q_ret += (uint32_t)__popcll(__ballot(done));
         if (done) active = false;
     }
+    if (kMixed && owed != 0ull) settle();  // (the drained path above has settled every lane already)
     flush_stats<STATS>(&stats, nv, npt, 0);
     if (kMixed) flush_stats<STATS>(&stats, nv_sh, npt_sh, 14);
     flush_stats<STATS>(&stats, n_unique, 0u, 18);
