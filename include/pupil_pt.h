@@ -953,6 +953,18 @@ int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out,
  * counts.  PUPIL_ERR_UNSUPPORTED for the two-level structure. */
 int pupil_pt_export_bvh4(pupil_pt *pt, uint32_t *num_nodes, void *nodes, uint32_t *num_records, float *records,
                          int32_t *root_link);
+/* (tests; callers detect the symbol, the ABI version does not count it) copies the two-level
+ * structure of world mode (PUPIL_TL_MODE) to host memory, after everything enqueued so far: the
+ * node array [0, num_nodes) -- the TLAS in [0, tlas_nodes), its never-written reserve up to
+ * tlas_cap, then the per-instance world BLAS copies --, the world record slots as 12 floats each
+ * (the mesh instances' records, then one two-slot leaf per sphere), the per-instance world boxes
+ * (6 floats each: lo, hi), the root link and the braid depth.  Call with nodes = records =
+ * inst_boxes = NULL for the counts; the scalar out pointers after inst_boxes may be NULL.
+ * PUPIL_ERR_UNSUPPORTED for the flattened BVH and for object mode, PUPIL_ERR_INVALID for a NULL
+ * count pointer or arrays smaller than the counts. */
+int pupil_debug_export_world_bvh4(pupil_pt *pt, uint32_t *num_nodes, void *nodes, uint32_t *num_records, float *records,
+                                  uint32_t *num_instances, float *inst_boxes, int32_t *root_link, uint32_t *tlas_nodes,
+                                  uint32_t *tlas_cap, uint32_t *braid);
 /* evaluates the device's sin, cos, acos, atan2(x, y2), sqrt, 1/x on n inputs:
  * out[6*i + k] for k in that order (bit-exactness probe for the CPU oracle) */
 int pupil_debug_math(int device, uint32_t n, const float *x, const float *y2, float *out);

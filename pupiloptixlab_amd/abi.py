@@ -207,6 +207,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_double)]),
     "pupil_pt_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f32p, C.c_int]),
     "pupil_pt_export_bvh4": (C.c_int, [C.c_void_p, u32p, C.c_void_p, u32p, f32p, C.POINTER(C.c_int32)]),
+    "pupil_debug_export_world_bvh4": (C.c_int, [C.c_void_p, u32p, C.c_void_p, u32p, f32p, u32p, f32p,
+                                                C.POINTER(C.c_int32), u32p, u32p, u32p]),
     "pupil_debug_math": (C.c_int, [C.c_int, C.c_uint32, f32p, f32p, f32p]),
     "pupil_debug_bvh_reinsert": (C.c_int, [C.c_int, C.c_uint32, f32p, C.c_uint32, C.POINTER(C.c_double), u32p, u32p]),
     "pupil_debug_partition": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32,

@@ -2157,6 +2157,38 @@ int pupil_pt_export_bvh4(pupil_pt *pt, uint32_t *num_nodes, void *nodes, uint32_
     return PUPIL_OK;
 }
 
+// Read-only: no kernel, no launch order touched; the device synchronise puts it after everything
+// enqueued so far, like pupil_pt_export_bvh4.
+int pupil_debug_export_world_bvh4(pupil_pt *pt, uint32_t *num_nodes, void *nodes, uint32_t *num_records, float *records,
+                                  uint32_t *num_instances, float *inst_boxes, int32_t *root_link, uint32_t *tlas_nodes,
+                                  uint32_t *tlas_cap, uint32_t *braid) {
+    if (!pt || !num_nodes || !num_records || !num_instances) return fail(PUPIL_ERR_INVALID, "null argument");
+    if (!pt->accel.two_level || !pt->accel.tl.world)
+        return fail(PUPIL_ERR_UNSUPPORTED, "only the world-mode two-level structure is exported");
+    HIP_TRY(hipSetDevice(pt->device));
+    const TwoLevelAccel &tl = pt->accel.tl;
+    const uint32_t nn = tl.num_wnodes, nr = pt->accel.world_record_slots(), ni = (uint32_t)tl.inst_shape.size();
+    if (nodes || records || inst_boxes) {
+        if (*num_nodes < nn || *num_records < nr || *num_instances < ni) return fail(PUPIL_ERR_INVALID, "output too small");
+        HIP_TRY(hipDeviceSynchronize());
+        if (nodes && nn) HIP_TRY(hipMemcpy(nodes, tl.wnodes, sizeof(Bvh4Node) * nn, hipMemcpyDeviceToHost));
+        if (records && nr) {  // record slots as 12 floats each (the 4th float4 of a slot is unused)
+            std::vector<float4> h((size_t)kRecF4 * nr);
+            HIP_TRY(hipMemcpy(h.data(), tl.wprims, sizeof(float4) * h.size(), hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < nr; r++) std::memcpy(records + 12 * r, &h[kRecF4 * r], 3 * sizeof(float4));
+        }
+        if (inst_boxes && ni) HIP_TRY(hipMemcpy(inst_boxes, tl.d_boxes, sizeof(float) * 6 * ni, hipMemcpyDeviceToHost));
+    }
+    *num_nodes = nn;
+    *num_records = nr;
+    *num_instances = ni;
+    if (root_link) *root_link = (int32_t)tl.root_link4;
+    if (tlas_nodes) *tlas_nodes = tl.tlas_nodes;
+    if (tlas_cap) *tlas_cap = tl.tlas_cap;
+    if (braid) *braid = tl.braid;
+    return PUPIL_OK;
+}
+
 int pupil_pt_trace_rays(pupil_pt *pt, uint32_t n, const float *rays, float *out, int any_hit) {
     if (!pt || !rays || !out) return fail(PUPIL_ERR_INVALID, "null argument");
     if (n == 0) return PUPIL_OK;

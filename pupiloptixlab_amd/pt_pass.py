@@ -1214,6 +1214,30 @@ class PTPass(Pass):
                                              recs.ctypes.data_as(C.POINTER(C.c_float)), C.byref(root)))
         return nodes[: nn.value], recs[: nr.value], root.value
 
+    def export_world_bvh4(self):
+        """(tests) The world-mode two-level structure (pupil_debug_export_world_bvh4): a dict of
+        nodes (uint8 (n, 64): TLAS, reserve, world BLAS copies), recs (float32 (m, 12) world record
+        slots, the spheres' leaves last), boxes (float32 (instances, 6)), root, tlas_nodes, tlas_cap
+        and braid; None for the flattened BVH and for object mode."""
+        import numpy as np
+
+        nn, nr, ni = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        root, tn, tc, br = C.c_int32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        scalars = [C.byref(root), C.byref(tn), C.byref(tc), C.byref(br)]
+        rc = self._lib.pupil_debug_export_world_bvh4(self._pt, C.byref(nn), None, C.byref(nr), None, C.byref(ni), None,
+                                                     *scalars)
+        if rc == abi.ERR_UNSUPPORTED:
+            return None
+        check(rc)
+        nodes = np.zeros((max(1, nn.value), 64), np.uint8)
+        recs = np.zeros((max(1, nr.value), 12), np.float32)
+        boxes = np.zeros((max(1, ni.value), 6), np.float32)
+        check(self._lib.pupil_debug_export_world_bvh4(self._pt, C.byref(nn), nodes.ctypes.data_as(C.c_void_p), C.byref(nr),
+                                                      recs.ctypes.data_as(abi.f32p), C.byref(ni),
+                                                      boxes.ctypes.data_as(abi.f32p), *scalars))
+        return {"nodes": nodes[: nn.value], "recs": recs[: nr.value], "boxes": boxes[: ni.value], "root": root.value,
+                "tlas_nodes": tn.value, "tlas_cap": tc.value, "braid": br.value}
+
     def image(self, name: str = FINAL_RESULT):
         """Full-frame (h, w, c) numpy image, row 0 = bottom (reference pixel order)."""
         t = self.buffers.get(name).cpu().numpy()

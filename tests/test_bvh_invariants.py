@@ -87,6 +87,67 @@ def _record_boxes(recs):
     return ids, live, lo, hi
 
 
+def _check_planes(idx, o, s, qlo, qhi, used, clo, chi, nlo, nhi, fail, info, scale_bound=True,
+                  parts=("enclosure", "origin/scale", "tightness")):
+    """Invariants 2-4 of check_bvh4 on decoded nodes, one row per node; idx names the rows in the
+    messages.  used (n, 4) marks the children to check, clo / chi (n, 3, 4) are their reference
+    boxes and nlo / nhi (n, 3) the nodes'.  Updates info's slack_s / excess_s."""
+    u = used[:, None, :] & np.ones((1, 3, 1), bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        dlo = o[:, :, None] + qlo.astype(F32) * s[:, :, None]  # float32: q s exact, one rounding
+        dhi = o[:, :, None] + qhi.astype(F32) * s[:, :, None]
+    assert dlo.dtype == F32 and dhi.dtype == F32
+
+    def where(m):
+        j, a, k = (int(x[0]) for x in np.nonzero(m))
+        return j, a, k, f"node {idx[j]} child {k} axis {AXES[a]} (o {o[j, a]!r}, s {s[j, a]!r}, q {qlo[j, a, k]}..{qhi[j, a, k]})"
+
+    if "enclosure" in parts:  # ---- 2. enclosure
+        m = u & ~(dlo <= clo)
+        if m.any():
+            j, a, k, w = where(m)
+            fail("enclosure", f"{w}: decoded lo {dlo[j, a, k]!r} > reference {clo[j, a, k]!r}; {m.sum()} planes")
+        m = u & ~(dhi >= chi)
+        if m.any():
+            j, a, k, w = where(m)
+            fail("enclosure", f"{w}: decoded hi {dhi[j, a, k]!r} < reference {chi[j, a, k]!r}; {m.sum()} planes")
+    if "origin/scale" in parts:  # ---- 3. origin and scale
+        m = _bits(o) != _bits(nlo)
+        if m.any():
+            j, a = (int(x[0]) for x in np.nonzero(m))
+            fail("origin/scale", f"node {idx[j]} axis {AXES[a]}: origin {o[j, a]!r} is not the children's minimum "
+                                 f"{nlo[j, a]!r}; {m.sum()} origins")
+        sb = _bits(s)
+        ex = (sb >> 23) & 0xFF
+        m = ((sb & 0x807FFFFF) != 0) | (ex == 0) | (ex == 255)
+        if m.any():
+            j, a = (int(x[0]) for x in np.nonzero(m))
+            fail("origin/scale", f"node {idx[j]} axis {AXES[a]}: scale bits {sb[j, a]:#010x} are no normal power of two")
+        with np.errstate(invalid="ignore"):
+            ext = nhi.astype(F64) - nlo.astype(F64)
+        if scale_bound:
+            m = (ext > 0) & (s.astype(F64) > np.maximum(4.0 * ext / 254.0, S_MIN))
+            if m.any():
+                j, a = (int(x[0]) for x in np.nonzero(m))
+                fail("origin/scale", f"node {idx[j]} axis {AXES[a]}: scale {s[j, a]!r} > 4 ext / 254 with ext {ext[j, a]!r} "
+                                     f"(ratio {s[j, a] * 254.0 / ext[j, a]:.3f}); {m.sum()} scales")
+    if "tightness" in parts:  # ---- 4. tightness
+        s3 = s.astype(F64)[:, :, None] * np.ones((1, 1, 4))
+        with np.errstate(invalid="ignore", over="ignore"):
+            for dec, ref, side in ((dlo, clo, "lo"), (dhi, chi, "hi")):
+                slack = np.abs(ref.astype(F64) - dec.astype(F64))
+                ulp = _ulp(np.maximum(np.abs(dec), np.abs(ref)))
+                ok = u & np.isfinite(slack)
+                if ok.any():
+                    info["slack_s"] = max(info["slack_s"], float((slack[ok] / s3[ok]).max()))
+                    info["excess_s"] = max(info["excess_s"], float(((slack[ok] - ulp[ok]) / s3[ok]).max()))
+                m = u & ~(slack <= 2.0 * s3 + ulp)
+                if m.any():
+                    j, a, k, w = where(m)
+                    fail("tightness", f"{w}: decoded {side} {dec[j, a, k]!r} is {slack[j, a, k] / s3[j, a, k]:.3f} s from "
+                                      f"{ref[j, a, k]!r} (limit 2 s + ulp {ulp[j, a, k]!r}); {m.sum()} planes")
+
+
 def check_bvh4(nodes, recs, root, n_prims, leaf_size, sah_leaf=None, refit=False, stats=None):
     """Raises BvhViolation naming the invariant; returns dict(nodes, depth, leaves, slack_s, excess_s):
     slack_s the largest plane-to-bound distance in units of s, excess_s the same after one ulp."""
@@ -199,59 +260,7 @@ def check_bvh4(nodes, recs, root, n_prims, leaf_size, sah_leaf=None, refit=False
     info = {"nodes": n, "depth": depth, "leaves": int((child < 0).sum()) + (1 if root < 0 else 0),
             "slack_s": 0.0, "excess_s": 0.0}
     if n:
-        u = used[:, None, :] & np.ones((1, 3, 1), bool)
-        with np.errstate(invalid="ignore", over="ignore"):
-            dlo = o[:, :, None] + qlo.astype(F32) * s[:, :, None]  # float32: q s exact, one rounding
-            dhi = o[:, :, None] + qhi.astype(F32) * s[:, :, None]
-        assert dlo.dtype == F32 and dhi.dtype == F32
-
-        def where(m):
-            j, a, k = (int(x[0]) for x in np.nonzero(m))
-            return j, a, k, f"node {j} child {k} axis {AXES[a]} (o {o[j, a]!r}, s {s[j, a]!r}, q {qlo[j, a, k]}..{qhi[j, a, k]})"
-
-        # ---- 2. enclosure
-        m = u & ~(dlo <= clo)
-        if m.any():
-            j, a, k, w = where(m)
-            fail("enclosure", f"{w}: decoded lo {dlo[j, a, k]!r} > reference {clo[j, a, k]!r}; {m.sum()} planes")
-        m = u & ~(dhi >= chi)
-        if m.any():
-            j, a, k, w = where(m)
-            fail("enclosure", f"{w}: decoded hi {dhi[j, a, k]!r} < reference {chi[j, a, k]!r}; {m.sum()} planes")
-        # ---- 3. origin and scale
-        m = _bits(o) != _bits(nlo)
-        if m.any():
-            j, a = (int(x[0]) for x in np.nonzero(m))
-            fail("origin/scale", f"node {j} axis {AXES[a]}: origin {o[j, a]!r} is not the children's minimum "
-                                 f"{nlo[j, a]!r}; {m.sum()} origins")
-        sb = _bits(s)
-        ex = (sb >> 23) & 0xFF
-        m = ((sb & 0x807FFFFF) != 0) | (ex == 0) | (ex == 255)
-        if m.any():
-            j, a = (int(x[0]) for x in np.nonzero(m))
-            fail("origin/scale", f"node {j} axis {AXES[a]}: scale bits {sb[j, a]:#010x} are no normal power of two")
-        ext = nhi.astype(F64) - nlo.astype(F64)
-        if not refit:
-            m = (ext > 0) & (s.astype(F64) > np.maximum(4.0 * ext / 254.0, S_MIN))
-            if m.any():
-                j, a = (int(x[0]) for x in np.nonzero(m))
-                fail("origin/scale", f"node {j} axis {AXES[a]}: scale {s[j, a]!r} > 4 ext / 254 with ext {ext[j, a]!r} "
-                                     f"(ratio {s[j, a] * 254.0 / ext[j, a]:.3f}); {m.sum()} scales")
-        # ---- 4. tightness
-        s3 = s.astype(F64)[:, :, None] * np.ones((1, 1, 4))
-        with np.errstate(invalid="ignore", over="ignore"):
-            for dec, ref, side in ((dlo, clo, "lo"), (dhi, chi, "hi")):
-                slack = np.abs(ref.astype(F64) - dec.astype(F64))
-                ulp = _ulp(np.maximum(np.abs(dec), np.abs(ref)))
-                ok = u & np.isfinite(slack)
-                if ok.any():
-                    info["slack_s"] = max(info["slack_s"], float((slack[ok] / s3[ok]).max()))
-                    info["excess_s"] = max(info["excess_s"], float(((slack[ok] - ulp[ok]) / s3[ok]).max()))
-                m = u & ~(slack <= 2.0 * s3 + ulp)
-                if m.any():
-                    j, a, k, w = where(m)
-                    fail("tightness", f"{w}: decoded {side} {dec[j, a, k]!r} is {slack[j, a, k] / s3[j, a, k]:.3f} s from "
-                                      f"{ref[j, a, k]!r} (limit 2 s + ulp {ulp[j, a, k]!r}); {m.sum()} planes")
+        _check_planes(np.arange(n), o, s, qlo, qhi, used, clo, chi, nlo, nhi, fail, info, scale_bound=not refit)
     # ---- 5. statistics
     if stats is not None:
         if stats["bvh_nodes"] != n:
